@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""PFST train-step throughput on MI355X (BASELINE.json metric) + roofline of the dominant kernel + CPU baseline.
+"""PFST train-step throughput on MI355X (BASELINE.json metric); with --full also the roofline of the dominant kernel, kernel
+tables, the other two arithmetics and the CPU baseline.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...          (no WORLD_SIZE in the environment: starts exactly that torch.distributed.run command
@@ -11,10 +12,12 @@
 One "step" = one full PFGST.train_step (student fwd/bwd on source + mixed batch, EMA-teacher forward, pseudo labels,
 class mix, PFGSTLoss, backward, gradient all-reduce, AdamW) on a synthetic batch of 8 x 1024x1024x3 tiles per GPU that
 is resident in HBM before the timed region.  value = global images / s (one image = one source+target pair).
-Rank 0 prints ONE JSON line.  `value` is the product configuration (teacher pass and weight gradients on side streams); the
-dominant kernel's `roofline` comes from a second timed region of the same K steps on ONE stream (`alt_single_stream`), because a
-kernel's duration is only defined while nothing else shares the CUs.  `per_rank` / `rank_spread`: step time min / mean / max,
-the reducer's buckets, the all-reduce time the backward sweep did not hide, the host's wait in the step's one blocking read."""
+Rank 0 prints ONE JSON line.  `value` is the product configuration (teacher pass and weight gradients on side streams); with
+--full the dominant kernel's `roofline` comes from a second timed region of the same K steps on ONE stream (`alt_single_stream`),
+because a kernel's duration is only defined while nothing else shares the CUs.  `per_rank` / `rank_spread`: step time min / mean / max,
+the reducer's buckets, the all-reduce time the backward sweep did not hide, the host's wait in the step's one blocking read.
+Inputs are seeded (batch, weights, the step's random draws): the same arguments give the same inputs in every run, and
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) so that two builds can be compared output for output."""
 import argparse
 import json
 import os
@@ -259,6 +262,30 @@ def cpu_baseline(num_classes, threads, timed_steps=3):
                        f'equivalents per step), mean {mean:.1f} s/step, torch-CPU fp32 oracle on {threads} threads')
 
 
+def dump_outputs(path, model, out, per_tensor=2048):
+    """What a caller of the timed train_step receives from its last step: the log values (log_vars.<key>.npy, float64) and the weights the
+    step left behind, the student's after AdamW and the EMA teacher's (model.npy / ema_model.npy, float32: every floating-point tensor of the
+    state_dict in order, at most `per_tensor` elements of each at positions drawn from a fixed seed; about 2.4 MB for the workload)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out['log_vars'].items():
+        np.save(os.path.join(path, f'log_vars.{k}.npy'), np.array([v], dtype=np.float64))
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(0)
+    parts = {'model': [], 'ema_model': []}
+    for k, t in model.state_dict().items():
+        part = k.split('.', 1)[0]
+        if part not in parts or not torch.is_tensor(t) or not t.is_floating_point():
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > per_tensor:
+            idx = np.sort(rng.choice(flat.numel(), per_tensor, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts[part].append(flat.float().cpu())
+    for part, pieces in parts.items():
+        np.save(os.path.join(path, f'{part}.npy'), torch.cat(pieces).numpy())
+
+
 def launch_ranks(args, argv):
     """`bench.py --gpus N` without a torch.distributed.run environment: start N ranks (one process per GPU, RCCL over xGMI) the way
     the reference's launcher does (tools/dist_train.sh:8-17: `python -m torch.distributed.launch --nproc_per_node=$GPUS
@@ -291,16 +318,21 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default: the config\'s 8)')
     ap.add_argument('--size', type=int, default=None, help='tile size (default 1024)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--per-layer', action='store_true', help='debug: per-layer conv timing table on stderr')
-    ap.add_argument('--no-alt-math', action='store_true', help='skip the informational passes: the other two arithmetics (N=1 only)')
+    ap.add_argument('--full', action='store_true', help='after `value`, also the informational legs: the single-stream region with the '
+                    'roofline and kernel tables, the other two arithmetics (N=1 only) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: skip the single-stream region and the kernel tables')
+    ap.add_argument('--per-layer', action='store_true', help='debug, with --full: per-layer conv timing table on stderr')
+    ap.add_argument('--no-alt-math', action='store_true', help='with --full: skip the other two arithmetics (N=1 only)')
     ap.add_argument('--math', choices=['f32', 'bf16x6', 'f16x3'], default=None, help='arithmetic of the dense convolutions for `value` '
                     '(default: the product default, pfst_amd.layers.CONV_MATH / PFST_CONV_MATH)')
     ap.add_argument('--master-port', type=int, default=None, help='rendezvous port when bench.py starts the ranks itself')
     ap.add_argument('--rendezvous-only', action='store_true', help='launch-path check: join the process group, one all-reduce, no kernels')
     ap.add_argument('--dry-run', action='store_true', help='with --gpus N > 1 and no WORLD_SIZE: print the child command and exit')
     args = ap.parse_args()
+    if args.per_layer and not args.full:
+        ap.error('--per-layer is a table of the --full kernel pass: add --full')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -351,6 +383,12 @@ def main():
     from pfst_amd.registry import UDA
     from pfst_amd.synthetic import fill_state_dict, synth_batch
 
+    import random
+    import numpy as np
+    # the step draws its class mix, colour-jitter / blur decisions and dropout masks from these: seeded, a run's inputs are the same every time
+    random.seed(1234 + rank)
+    np.random.seed(1234 + rank)
+    torch.manual_seed(1234 + rank)
     cfg, w = workload_cfg(WORKLOAD)
     b = args.batch or w['per_gpu_batch']
     S = args.size or w['size']
@@ -487,11 +525,12 @@ def main():
         out['kernel_time_total_ms_per_step'] = tot_ms / args.steps
         return out
 
-    def measure(math, tables=True):
+    def measure(math, tables=True, dump=None):
         """one arithmetic: warm-up; the timed K steps of the PRODUCT configuration (`value`: teacher pass forked, weight gradients on the
-        side stream -- layers.FORK_TEACHER / WGRAD_STREAM, nothing bracketed); then the same K steps on ONE stream with the dominant
-        kernel's launches bracketed by HIP events (a per-kernel duration is only defined while nothing co-runs on the CUs: `roofline`,
-        and the single-stream step as `alt_single_stream`); then the table pass (every launch bracketed)."""
+        side stream -- layers.FORK_TEACHER / WGRAD_STREAM, nothing bracketed), whose last step is written to `dump` if given; with --full
+        then the same K steps on ONE stream with the dominant kernel's launches bracketed by HIP events (a per-kernel duration is only
+        defined while nothing co-runs on the CUs: `roofline`, and the single-stream step as `alt_single_stream`); then the table pass
+        (every launch bracketed)."""
         model, opt = build(math)
         dominant = DOMINANT_KERNEL[math]
         product = (layers.WGRAD_STREAM, layers.FORK_TEACHER)
@@ -502,6 +541,8 @@ def main():
         step_s = []
         elapsed, out = timed_steps(model, opt, args.steps, step_s)
         stats, pdist.STEP_STATS = pdist.STEP_STATS, None
+        if dump:
+            dump_outputs(dump, model, out)
         mine = dict(rank=rank, step_ms=dict(min=round(1e3 * min(step_s), 2), mean=round(1e3 * sum(step_s) / len(step_s), 2), max=round(1e3 * max(step_s), 2)),
                     **pdist.summarize_step_stats(stats))
         if world > 1:
@@ -520,7 +561,7 @@ def main():
             rec['rank_spread'] = dict(step_ms_mean_min=min(means), step_ms_mean_max=max(means),
                                       slowest_rank=int(max(range(world), key=lambda i: means[i])),
                                       exposed_allreduce_ms_mean_max=max((r['exposed_allreduce_ms'] or {}).get('mean', 0.0) for r in per_rank))
-        timing = not args.no_kernel_timing
+        timing = args.full and not args.no_kernel_timing
         if timing:
             # Single-stream region: the same K steps, only the dominant kernel's launches bracketed with events (2700 event pairs per step
             # would cost the step 1.5-2 %, these 272 cost 1 ms).  Its roofline figure is an average over launches that own the device.
@@ -547,7 +588,7 @@ def main():
         torch.cuda.empty_cache()
         return rec
 
-    main = measure(main_math)
+    main = measure(main_math, dump=args.dump_outputs if rank == 0 else None)
     res = None
     if rank == 0:
         global_batch = b * world
@@ -571,7 +612,7 @@ def main():
                 res[k] = main[k]
         if 'single_stream' in main:
             res['alt_single_stream'] = main['single_stream']
-    if world == 1 and not args.no_alt_math:
+    if world == 1 and args.full and not args.no_alt_math:
         # the other arithmetic on the same step, same line: fp32-input MFMA (v_mfma_f32_32x32x2_f32) when `value` runs the
         # fp32-faithful bf16x6 split, and vice versa -- with its own roofline leg
         alt = measure(other_math)
@@ -591,9 +632,9 @@ def main():
         torch.cuda.empty_cache()
     layers.CONV_MATH = main_math
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res['cpu_baseline'] = cpu_baseline(w['num_classes'], usable_cpus())
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             res['cpu_baseline'] = None   # measured at N=1 only
         print(json.dumps(res), flush=True)
     if world > 1:

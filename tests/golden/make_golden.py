@@ -757,10 +757,37 @@ def gen_train_step_variants(ref, only=None):
         print(f'train_step_{name}.npz', lv)
 
 
+CONFIG_NAMES = ['pfst_pots_irrg2vaih_irrg', 'pfst_vaih_irrg2pots_irrg', 'pfst_inria_da', 'pfst_season_net_sp2fa']
+
+
+def gen_reference_configs():
+    """The values of configs/pfst/<name>_deeplabv3plus_r50-d8.py after `_base_` merging, one dict per config, as JSON (a tuple is
+    stored as {"__tuple__": [...]}): the data the drop-in test builds the registered types from where the config files are absent."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from pfst_amd.config import Config
+
+    def enc(v):
+        if isinstance(v, dict):
+            return {k: enc(x) for k, x in v.items()}
+        if isinstance(v, tuple):
+            return {'__tuple__': [enc(x) for x in v]}
+        if isinstance(v, list):
+            return [enc(x) for x in v]
+        return v
+    out = {n: enc(Config.fromfile(os.path.join(REF, 'configs', 'pfst', f'{n}_deeplabv3plus_r50-d8.py')).to_dict()) for n in CONFIG_NAMES}
+    with open(os.path.join(OUT, 'reference_configs.json'), 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('reference_configs.json', list(out))
+
+
 if __name__ == '__main__':
     torch.set_num_threads(8)
+    which = sys.argv[1:] or ['small', 'options', 'options2', 'dataset', 'dataset2', 'pipeline', 'seg', 'step', 'variants', 'step512', 'configs']
+    if 'configs' in which:
+        gen_reference_configs()
     ref = load_reference()
-    which = sys.argv[1:] or ['small', 'options', 'options2', 'dataset', 'dataset2', 'pipeline', 'seg', 'step', 'variants', 'step512']
     if 'options2' in which:
         gen_pfgst_options2(ref)
     if 'small' in which:

@@ -1,5 +1,7 @@
-"""Drop-in boundary on the CPU: the reference's own config files load unchanged and build the registered types with
-the reference's checkpoint layout.  (The config files exist only in the build container; skipped on the GPU box.)"""
+"""Drop-in boundary on the CPU: the reference's own configs build the registered types with the reference's checkpoint layout.
+The configs' values after `_base_` merging are pinned in tests/golden/reference_configs.json (make_golden.py); where the reference's
+config files are present, loading them with Config.fromfile must give exactly those values."""
+import json
 import os
 
 import numpy as np
@@ -9,13 +11,31 @@ REF_CFG = '/root/reference/configs/pfst'
 NAMES = ['pfst_pots_irrg2vaih_irrg', 'pfst_vaih_irrg2pots_irrg', 'pfst_inria_da', 'pfst_season_net_sp2fa']
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference configs not present')
+def _dec(v):
+    if isinstance(v, dict):
+        return tuple(_dec(x) for x in v['__tuple__']) if set(v) == {'__tuple__'} else {k: _dec(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_dec(x) for x in v]
+    return v
+
+
+def reference_config(name, golden_dir):
+    """Config of configs/pfst/<name>_deeplabv3plus_r50-d8.py: the pinned values, checked against the file where it exists"""
+    from pfst_amd.config import Config
+    with open(os.path.join(golden_dir, 'reference_configs.json')) as f:
+        pinned = _dec(json.load(f)[name])
+    path = os.path.join(REF_CFG, f'{name}_deeplabv3plus_r50-d8.py')
+    if os.path.exists(path):
+        assert Config.fromfile(path).to_dict() == pinned
+    return Config(pinned, filename=path)
+
+
 @pytest.mark.parametrize('name', NAMES)
 def test_reference_configs_load_and_build(name, golden_dir):
     import pfst_amd  # noqa: F401
-    from pfst_amd.config import Config, parse_cfg_options
+    from pfst_amd.config import parse_cfg_options
     from pfst_amd.registry import build_train_model
-    cfg = Config.fromfile(os.path.join(REF_CFG, f'{name}_deeplabv3plus_r50-d8.py'))
+    cfg = reference_config(name, golden_dir)
     cfg.merge_from_dict(parse_cfg_options(['model.pretrained=None', 'runner.max_iters=123']))
     assert cfg.uda.type == 'PFGST' and cfg.uda.aux_losses[0]['type'] == 'PFGSTLoss'
     model = build_train_model(cfg)
@@ -28,18 +48,39 @@ def test_reference_configs_load_and_build(name, golden_dir):
     assert not any(p.requires_grad for p in model.ema_model.parameters())
 
 
-def test_presets_match_reference_configs_when_available():
+def test_presets_match_reference_configs_when_available(golden_dir):
     from pfst_amd.presets import WORKLOADS, workload_cfg
     for name, w in WORKLOADS.items():
         cfg, _ = workload_cfg(name)
         assert cfg['model']['decode_head']['num_classes'] == w['num_classes']
-        path = os.path.join(REF_CFG, name + '.py')
-        if os.path.exists(path):
-            from pfst_amd.config import Config
-            ref = Config.fromfile(path)
-            assert ref.uda.pseudo_threshold == cfg['pseudo_threshold'] and ref.uda.alpha == cfg['alpha']
-            assert ref.uda.aux_losses[0]['downscale'] == w['downscale']
-            assert ref.model.decode_head.num_classes == w['num_classes']
+        ref = reference_config(name[:-len('_deeplabv3plus_r50-d8')], golden_dir)
+        assert ref.uda.pseudo_threshold == cfg['pseudo_threshold'] and ref.uda.alpha == cfg['alpha']
+        assert ref.uda.aux_losses[0]['downscale'] == w['downscale']
+        assert ref.model.decode_head.num_classes == w['num_classes']
+
+
+def test_fromfile_merges_base_files(tmp_path):
+    """`_base_` inheritance as the reference's config files use it: a list of relative paths merged in order, nested dicts merged key
+    by key, `_delete_=True` replacing a dict, the file's own values last"""
+    from pfst_amd.config import Config
+    (tmp_path / '_base_').mkdir()
+    (tmp_path / 'pfst').mkdir()
+    (tmp_path / '_base_' / 'model.py').write_text("norm_cfg = dict(type='BN', requires_grad=True)\n"
+                                                  "model = dict(type='EncoderDecoder', decode_head=dict(num_classes=19, dilations=(1, 12, 24, 36)),\n"
+                                                  "             auxiliary_head=dict(num_classes=19, norm_cfg=norm_cfg))\n")
+    (tmp_path / '_base_' / 'schedule.py').write_text("optimizer = dict(type='AdamW', lr=6e-05, paramwise_cfg=dict(custom_keys=dict(head=dict(lr_mult=10.0))))\n"
+                                                     "runner = dict(type='IterBasedRunner', max_iters=40000)\n")
+    (tmp_path / 'pfst' / 'cfg.py').write_text("_base_ = ['../_base_/model.py', '../_base_/schedule.py']\nseed = 0\n"
+                                              "model = dict(decode_head=dict(num_classes=6), auxiliary_head=dict(num_classes=6))\n"
+                                              "optimizer = dict(lr=1e-04, paramwise_cfg=dict(_delete_=True, decay_mult=0.0))\n")
+    cfg = Config.fromfile(str(tmp_path / 'pfst' / 'cfg.py'))
+    assert cfg.to_dict() == dict(
+        norm_cfg=dict(type='BN', requires_grad=True), seed=0,
+        model=dict(type='EncoderDecoder', decode_head=dict(num_classes=6, dilations=(1, 12, 24, 36)),
+                   auxiliary_head=dict(num_classes=6, norm_cfg=dict(type='BN', requires_grad=True))),
+        optimizer=dict(type='AdamW', lr=1e-04, paramwise_cfg=dict(decay_mult=0.0)),
+        runner=dict(type='IterBasedRunner', max_iters=40000))
+    assert cfg.model.decode_head.num_classes == 6 and cfg.runner.max_iters == 40000
 
 
 def test_unknown_options_fail_loudly():

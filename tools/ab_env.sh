@@ -6,7 +6,7 @@
 OFF="$1"
 for L in off on off on; do
   if [ $L = off ]; then PRE="env $OFF"; else PRE=""; fi
-  $PRE python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-alt-math 2>/dev/null | python -c "
+  $PRE python bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-alt-math 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']; h=d['hbm_kernels']
 print('$L', round(d['value'],3), round(d['ms_per_step'],2), {n:h[n]['ms_per_step'] for n in ('pfst_bn_apply','pfst_bn_backward')}, {n:v for n,v in k.items() if 'wgrad' in n})"
