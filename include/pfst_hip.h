@@ -438,6 +438,37 @@ int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, int C, int H,
 /* out[0] = w_pos*acc[0]/((top_k+1)*count), out[1] = w_neg*acc[1]/(top_k*count); top_k = 0: both /(9*count)  (zeros when count <= 1) */
 int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int top_k, float w_pos, float w_neg, float* out, pfst_stream_t stream);
 
+/* ---- PFGSTLoss, kernel K x K for ksize K in {3, 5, 7}: the entries above with `int ksize` before `dil`, the same semantics otherwise.
+ * Tap order (nn.Unfold's): k = (dy+r)*ksize + (dx+r), r = ksize/2, neighbour offset (dy*dil, dx*dil), dy, dx in [-r, r]; maps with
+ * taps are [N][ksize*ksize][H][W].  The similarity map and its adjoint stage (16 + 2*r*dil)^2 halo tiles in LDS: r*dil <= 37. */
+int pfst_sim_map_k(const float* feat, int N, int C, int H, int W, int ksize, int dil, int sim_type, float sigma, float* sim, float* norm,
+                   pfst_stream_t stream);
+/* coef_ws (required, both sim types): (ksize*ksize + 1)*N*H*W floats of scratch (per-pixel stencil coefficients) */
+int pfst_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int ksize,
+                       int dil, int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream);
+/* source pairs: centre label != 255; a neighbour in the zero-padding band has label 0 and similarity against a zero vector */
+int pfst_src_sim_stats_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, int loss_type,
+                         float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream);
+int pfst_src_sim_grad_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, int loss_type,
+                        float margin_pos, float margin_neg, const double* stats,
+                        float w_pos, float w_neg, float w_pos_std, float w_neg_std, float* gsim, float* losses, const void* select, pfst_stream_t stream);
+int pfst_src_sim_select_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, double src_perc,
+                          void* select, pfst_stream_t stream);
+/* valid = (gt != 255) && all ksize*ksize dilated neighbours inside the map and un-mixed; all_in = the second condition alone */
+int pfst_trg_valid_mask_k(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                          unsigned char* valid, unsigned char* all_in, unsigned long long* count, pfst_stream_t stream);
+/* 0 <= top_k <= ksize*ksize - 1 (0: all pairs).  Ranks: stable descending similarity, the lower tap index first on ties; the
+ * top-(top_k+1) and bottom-top_k sets may overlap (2*top_k + 1 > ksize*ksize): a pair in both counts in both losses */
+int pfst_sim_topk_loss_k(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
+                         int N, int C, int H, int W, int ksize, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
+                         float* g_sim, pfst_stream_t stream);
+/* unfold_grad: coefficient gP[k][r] + gP[ksize*ksize-1-k][r+D_k] */
+int pfst_cross_prob_bwd_k(const float* prob, const float* gP, int N, int C, int H, int W, int ksize, int dil, int ds, int unfold_grad,
+                          float* dlogits, int h, int w, pfst_stream_t stream);
+/* top_k = 0: both sums / (ksize*ksize*count) */
+int pfst_sim_loss_finalize_k(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg, float* out,
+                             pfst_stream_t stream);
+
 /* ---- EMA teacher + AdamW on flat parameter arenas (pfgst.py:105-127, torch.optim.AdamW) ------ */
 int pfst_ema_update(float* teacher, const float* student, long long n, float alpha, pfst_stream_t stream);
 int pfst_adamw_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,

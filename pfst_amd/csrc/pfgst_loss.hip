@@ -5,6 +5,7 @@
 // the same configs: sim_type 'gaussian' (:199-201), src_loss_type 'margin' / 'margin2' (:116-131), detach_unfold=False
 // (:151-152), top_k=None (:229-231), downscale None / 1.
 // Neighbour index k = ty*3+tx, offset ((ty-1)*d, (tx-1)*d) -- the order nn.Unfold produces.
+// kernel_size 5 / 7 and top_k > 4: the templated K x K kernels and the `_k` entries at the end of the file.
 #include "common.h"
 #include <stdlib.h>
 #include "../../include/pfst_hip.h"
@@ -911,6 +912,630 @@ extern "C" int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, in
 extern "C" int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int top_k, float w_pos, float w_neg, float* out, pfst_stream_t stream) {
   PFST_CHECK_ARG(acc && count && out && top_k >= 0);
   hipLaunchKernelGGL(sim_loss_finalize_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, acc, count, top_k, w_pos, w_neg, out);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+// ===========================================================================================================================
+// Kernel sizes 3, 5 and 7 (the `_k` entries): nn.Unfold(K, dilation d, padding (K//2) d), tap k = (dy+r) K + (dx+r), r = K//2,
+// offset (dy d, dx d), dy, dx in [-r, r].  The 3x3 entries above stay the production path of the shipped configs (kernel_size 3,
+// top_k <= 4); hip_ops sends everything else here.
+// ===========================================================================================================================
+namespace {
+
+constexpr int KT = 16;                  // pixel tile of the K x K stencil kernels: 16 x 16 pixels, one per thread
+constexpr int KT_LDS_FLOATS = 16384;    // 64 KB of LDS per workgroup: a channel chunk of halo tiles (+ the squared-norm tile)
+constexpr int KT_MAX_CC = 8;            // channels per chunk
+
+// halo tile edge for tap reach `hal` = (K//2) d, and the channels per LDS chunk (0: the tile does not fit)
+inline int kt_edge(int hal) { return KT + 2 * hal; }
+inline int kt_chunk(int hal, bool with_norm) {
+  const i64 la = (i64)kt_edge(hal) * kt_edge(hal);
+  const i64 cc = KT_LDS_FLOATS / la - (with_norm ? 1 : 0);
+  return (int)(cc < 1 ? 0 : (cc > KT_MAX_CC ? KT_MAX_CC : cc));
+}
+
+// Cooperative load of channels [c0, c0 + nc) of the halo tile around pixel tile (x0, y0) into lds[c][la]; positions outside the
+// map are nn.Unfold's zero padding.  nsq != NULL: each tile position also accumulates its squared norm (one owner per position).
+__device__ __forceinline__ void kt_load(const float* __restrict__ fp, int HW, int H, int W, int x0, int y0, int hal, int lw, int la,
+                                        int nc, float* __restrict__ lds, float* __restrict__ nsq) {
+  for (int t = threadIdx.x; t < la; t += blockDim.x) {
+    const int ly = t / lw, lx = t - ly * lw;
+    const int gy = y0 - hal + ly, gx = x0 - hal + lx;
+    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
+    const float* src = fp + (in ? (i64)gy * W + gx : 0);
+    float acc = 0.f;
+    for (int c = 0; c < nc; ++c) {
+      const float v = in ? src[(i64)c * HW] : 0.f;
+      lds[c * la + t] = v;
+      acc = fmaf(v, v, acc);
+    }
+    if (nsq) nsq[t] += acc;
+  }
+}
+
+// ---- similarity map, K x K taps.  The feature map is read once: each workgroup stages a chunk of channels of its (16 + 2 r d)^2
+// halo tile in LDS and every thread takes its K^2 taps from there (K^2 + 1 LDS reads and K^2 fma per pixel and channel, K^2 dot
+// products in registers).  The cosine denominator's neighbour norms come from the tile's squared-norm accumulator, which covers
+// the halo.  D > 0: dilation fixed at compile time (constant LDS offsets); D = 0: any dilation.
+// grid: (ceil(W / 16), ceil(H / 16), N), 256 threads, (cc + 1) * la floats of dynamic LDS
+template <int K, int D, bool GAUSS>
+__global__ __launch_bounds__(256) void sim_map_k_kernel(const float* __restrict__ feat, int C, int H, int W, int dil_rt, int cc,
+                                                        float inv_sigma2, float* __restrict__ sim, float* __restrict__ norm) {
+  constexpr int R = K / 2, KK = K * K;
+  extern __shared__ float lds[];
+  const int dil = D > 0 ? D : dil_rt;
+  const int hal = R * dil, lw = KT + 2 * hal, la = lw * lw;
+  float* nsq = lds + cc * la;
+  const int n = blockIdx.z, HW = H * W;
+  const int x0 = blockIdx.x * KT, y0 = blockIdx.y * KT;
+  const int tx = threadIdx.x % KT, ty = threadIdx.x / KT;
+  const float* fp = feat + (i64)n * C * HW;
+  for (int t = threadIdx.x; t < la; t += blockDim.x) nsq[t] = 0.f;
+  const int ctr = (ty + hal) * lw + tx + hal;
+  float dot[KK];
+#pragma unroll
+  for (int k = 0; k < KK; ++k) dot[k] = 0.f;
+  for (int c0 = 0; c0 < C; c0 += cc) {
+    const int nc = C - c0 < cc ? C - c0 : cc;
+    __syncthreads();                                    // the previous chunk has been read (and nsq zeroed)
+    kt_load(fp + (i64)c0 * HW, HW, H, W, x0, y0, hal, lw, la, nc, lds, GAUSS ? nullptr : nsq);
+    __syncthreads();
+    for (int c = 0; c < nc; ++c) {
+      const float* tl = lds + c * la + ctr;
+      const float a = tl[0];
+#pragma unroll
+      for (int k = 0; k < KK; ++k) {
+        const float b = tl[(k / K - R) * dil * lw + (k % K - R) * dil];
+        if (GAUSS) {
+          const float d = b - a;
+          dot[k] = fmaf(d, d, dot[k]);
+        } else {
+          dot[k] = fmaf(a, b, dot[k]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= W || y >= H) return;
+  const int p = y * W + x;
+  float* sp = sim + (i64)n * KK * HW + p;
+  if (GAUSS) {
+#pragma unroll
+    for (int k = 0; k < KK; ++k) sp[(i64)k * HW] = expf(-dot[k] * inv_sigma2);
+    if (norm) norm[(i64)n * HW + p] = 0.f;
+    return;
+  }
+  const float na = fmaxf(sqrtf(nsq[ctr]), COS_EPS);
+#pragma unroll
+  for (int k = 0; k < KK; ++k) {
+    const float nb = fmaxf(sqrtf(nsq[ctr + (k / K - R) * dil * lw + (k % K - R) * dil]), COS_EPS);   // 0 in the padding -> COS_EPS
+    sp[(i64)k * HW] = dot[k] / (na * nb);
+  }
+  norm[(i64)n * HW + p] = sqrtf(nsq[ctr]);
+}
+
+// ---- adjoint coefficients, both similarity types: coef[n][K^2 + 1][HW] = (A_0 .. A_{K^2-1} with A_centre = 0, B), so that
+// dF(r) = B(r) F(r) + sum_k A_k(r) F(r + D_k).  Pixel r is the mirror tap K^2-1-k of its k-neighbour r + D_k (see sim_map_bwd_kernel).
+template <int K, bool GAUSS>
+__global__ __launch_bounds__(256) void sim_bwd_coef_k_kernel(const float* __restrict__ sim, const float* __restrict__ norm,
+                                                             const float* __restrict__ gsim, int H, int W, int dil, float inv_sigma2,
+                                                             float* __restrict__ coef) {
+  constexpr int R = K / 2, KK = K * K;
+  const int n = blockIdx.y, HW = H * W;
+  const float* sp = sim + (i64)n * KK * HW;
+  const float* gp = gsim + (i64)n * KK * HW;
+  const float* np_ = norm + (i64)n * HW;
+  float* cp = coef + (i64)n * (KK + 1) * HW;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    const float nr = GAUSS ? 1.f : fmaxf(np_[p], COS_EPS);
+    float b = 0.f;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+      const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
+      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
+      float a = 0.f;
+      if (in && k != KK / 2) {
+        const int q = sy * W + sx, m = KK - 1 - k;
+        const float g1 = gp[(i64)k * HW + p], g2 = gp[(i64)m * HW + q];
+        if (GAUSS) {
+          const float c = -2.f * inv_sigma2 * (g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)m * HW + q]);
+          a = -c;
+          b += c;
+        } else {
+          a = (g1 + g2) / (nr * fmaxf(np_[q], COS_EPS));
+          b -= g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)m * HW + q];
+        }
+      } else if (GAUSS && !in) {
+        b += -2.f * inv_sigma2 * gp[(i64)k * HW + p] * sp[(i64)k * HW + p];    // neighbour is the constant 0: centre side only
+      }
+      cp[(i64)k * HW + p] = a;
+    }
+    cp[(i64)KK * HW + p] = GAUSS ? b : b / (nr * nr);
+  }
+}
+
+// ---- the adjoint's stencil: same tiling as sim_map_k_kernel, K^2 + 1 coefficients per thread in registers.
+// grid: (ceil(W / 16), ceil(H / 16), N), 256 threads, cc * la floats of dynamic LDS
+template <int K, int D>
+__global__ __launch_bounds__(256) void sim_map_bwd_k_kernel(const float* __restrict__ feat, const float* __restrict__ coef, int C, int H,
+                                                            int W, int dil_rt, int cc, float* __restrict__ dfeat, int accumulate) {
+  constexpr int R = K / 2, KK = K * K;
+  extern __shared__ float lds[];
+  const int dil = D > 0 ? D : dil_rt;
+  const int hal = R * dil, lw = KT + 2 * hal, la = lw * lw;
+  const int n = blockIdx.z, HW = H * W;
+  const int x0 = blockIdx.x * KT, y0 = blockIdx.y * KT;
+  const int tx = threadIdx.x % KT, ty = threadIdx.x / KT;
+  const int x = x0 + tx, y = y0 + ty;
+  const bool own = x < W && y < H;
+  const int p = own ? y * W + x : 0;
+  const int ctr = (ty + hal) * lw + tx + hal;
+  float A[KK], B = 0.f;
+  const float* cp = coef + (i64)n * (KK + 1) * HW + p;
+#pragma unroll
+  for (int k = 0; k < KK; ++k) A[k] = own ? cp[(i64)k * HW] : 0.f;
+  if (own) B = cp[(i64)KK * HW];
+  const float* fp = feat + (i64)n * C * HW;
+  float* dp = dfeat + (i64)n * C * HW + p;
+  for (int c0 = 0; c0 < C; c0 += cc) {
+    const int nc = C - c0 < cc ? C - c0 : cc;
+    __syncthreads();
+    kt_load(fp + (i64)c0 * HW, HW, H, W, x0, y0, hal, lw, la, nc, lds, nullptr);
+    __syncthreads();
+    if (!own) continue;
+    for (int c = 0; c < nc; ++c) {
+      const float* tl = lds + c * la + ctr;
+      float v = B * tl[0];
+#pragma unroll
+      for (int k = 0; k < KK; ++k) v = fmaf(A[k], tl[(k / K - R) * dil * lw + (k % K - R) * dil], v);
+      const i64 o = (i64)(c0 + c) * HW;
+      dp[o] = accumulate ? dp[o] + v : v;
+    }
+  }
+}
+
+// ---- source pairs, K x K: 0 = skip, 1 = positive pair, 2 = negative pair (nn.Unfold's zero padding has label 0, a real class)
+template <int K>
+__device__ __forceinline__ int src_pair_class_k(const unsigned char* __restrict__ gt, int Hg, int Wg, float sgy, float sgx, int H, int W,
+                                                int y, int x, int k, int dil, int ctr) {
+  constexpr int R = K / 2;
+  const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
+  int nb = 0;
+  if (sy >= 0 && sy < H && sx >= 0 && sx < W) nb = gt[(i64)nearest_src(sy, sgy, Hg) * Wg + nearest_src(sx, sgx, Wg)];
+  return nb == ctr ? 1 : 2;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void src_sel_hist_k_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
+                                                             int Hg, int Wg, int dil, const SrcSel* __restrict__ sel,
+                                                             unsigned int* __restrict__ hist) {
+  constexpr int KK = K * K;
+  __shared__ unsigned int sh[2 * 256];
+  sh[threadIdx.x] = 0; sh[256 + threadIdx.x] = 0;
+  __syncthreads();
+  const int n = blockIdx.y, HW = H * W;
+  const unsigned char* g = gt + (i64)n * Hg * Wg;
+  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
+  const unsigned int shift0 = sel[0].shift, shift1 = sel[1].shift;
+  const unsigned int hi0 = shift0 >= 24 ? 0u : (0xFFFFFFFFu << (shift0 + 8)), hi1 = shift1 >= 24 ? 0u : (0xFFFFFFFFu << (shift1 + 8));
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+    if (ctr == 255) continue;
+    for (int k = 0; k < KK; ++k) {
+      const int cls = src_pair_class_k<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+      const float v = sim[((i64)n * KK + k) * HW + p];
+      if (cls == 1) {
+        const unsigned int key = order_key(v, false);
+        if (((key ^ sel[0].prefix) & hi0) == 0) atomicAdd(&sh[(key >> shift0) & 255u], 1u);
+      } else {
+        const unsigned int key = order_key(v, true);
+        if (((key ^ sel[1].prefix) & hi1) == 0) atomicAdd(&sh[256 + ((key >> shift1) & 255u)], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  if (sh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], sh[threadIdx.x]);
+  if (sh[256 + threadIdx.x]) atomicAdd(&hist[256 + threadIdx.x], sh[256 + threadIdx.x]);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void src_stats_k_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
+                                                          int Hg, int Wg, int dil, int loss_type, float m0, float m1,
+                                                          double* __restrict__ stats, const SrcSel* __restrict__ sel,
+                                                          double* __restrict__ det_part) {
+  // det_part != NULL (deterministic mode): the block's six sums go to its slot of det_part[slots][6] (see src_stats_kernel)
+  constexpr int KK = K * K;
+  __shared__ double sm[16];
+  const int n = blockIdx.y, HW = H * W;
+  const unsigned char* g = gt + (i64)n * Hg * Wg;
+  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
+  double a[6] = {0, 0, 0, 0, 0, 0};
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+    if (ctr == 255) continue;
+    for (int k = 0; k < KK; ++k) {
+      const int cls = src_pair_class_k<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+      const float sv = sim[((i64)n * KK + k) * HW + p];
+      const double s = (double)sv;
+      const double wt = (double)sel_weight(sel, cls == 1 ? 0 : 1, sv);
+      const int o = cls == 1 ? 0 : 3;
+      if (loss_type == 0) {
+        a[o] += wt; a[o + 1] += wt * s; a[o + 2] += wt * s * s;
+      } else {
+        const double h = cls == 1 ? fmax((double)m0 - s, 0.0) : fmax(s - (double)m1, 0.0);
+        a[o] += wt; a[o + 1] += wt * (loss_type == 1 ? h : h * h);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double r = block_sum_d(a[i], sm);
+    if (threadIdx.x == 0) {
+      if (det_part) det_part[((i64)blockIdx.y * gridDim.x + blockIdx.x) * 6 + i] = r;
+      else if (r != 0.0) atomicAdd(&stats[i], r);
+    }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void src_grad_k_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
+                                                         int Hg, int Wg, int dil, int loss_type, float m0, float m1,
+                                                         const double* __restrict__ stats, float w_pos, float w_neg, float w_pos_std,
+                                                         float w_neg_std, float* __restrict__ gsim, float* __restrict__ losses,
+                                                         const SrcSel* __restrict__ sel) {
+  constexpr int KK = K * K;
+  const int n = blockIdx.y, HW = H * W;
+  const unsigned char* g = gt + (i64)n * Hg * Wg;
+  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
+  const bool hinge = loss_type != 0;
+  const SrcMoments mp = moments(stats), mn = moments(stats + 3);
+  const double np = stats[0], nn = stats[3];
+  if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
+    if (hinge) {
+      losses[0] = np > 0 ? (float)((double)w_pos * stats[1] / np) : 0.f;     // (an empty set gives NaN in the reference)
+      losses[1] = nn > 0 ? (float)((double)w_neg * stats[4] / nn) : 0.f;
+      losses[2] = 0.f;
+      losses[3] = 0.f;
+    } else {
+      losses[0] = (float)(-mp.mean * w_pos);
+      losses[1] = (float)(mn.mean * w_neg);
+      losses[2] = (float)(mp.std * w_pos_std);
+      losses[3] = (float)(mn.std * w_neg_std);
+    }
+  }
+  // hinge: d/ds = -/+ e relu(.)^(e-1) w / n;  mean_std: d(-w mean)/ds = -w/n, d(w std)/ds = w (s-mean)/((n-1) std)
+  const double cp = np > 0 ? (double)w_pos / np : 0.0, cn = nn > 0 ? (double)w_neg / nn : 0.0;
+  const double pa = mp.n > 0 ? -(double)w_pos / mp.n : 0.0;
+  const double pb = (mp.n > 1 && mp.std > 0) ? (double)w_pos_std / ((mp.n - 1.0) * mp.std) : 0.0;
+  const double na = mn.n > 0 ? (double)w_neg / mn.n : 0.0;
+  const double nb = (mn.n > 1 && mn.std > 0) ? (double)w_neg_std / ((mn.n - 1.0) * mn.std) : 0.0;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+    for (int k = 0; k < KK; ++k) {
+      const i64 o = ((i64)n * KK + k) * HW + p;
+      float gr = 0.f;
+      if (ctr != 255) {
+        const int cls = src_pair_class_k<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+        const double s = (double)sim[o];
+        const float wt = sel_weight(sel, cls == 1 ? 0 : 1, sim[o]);
+        if (hinge) {
+          const double h = cls == 1 ? (double)m0 - s : s - (double)m1;
+          if (h > 0.0) gr = (float)((cls == 1 ? -cp : cn) * (loss_type == 1 ? 1.0 : 2.0 * h)) * wt;
+        } else {
+          gr = (cls == 1 ? (float)(pa + pb * (s - mp.mean)) : (float)(na + nb * (s - mn.mean))) * wt;
+        }
+      }
+      gsim[o] = gr;
+    }
+  }
+}
+
+// ---- target validity: centre label != 255 and all K^2 dilated neighbours inside the map and un-mixed
+template <int K>
+__global__ __launch_bounds__(256) void trg_valid_k_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ mix,
+                                                          int H, int W, int Hg, int Wg, int dil, unsigned char* __restrict__ valid,
+                                                          unsigned char* __restrict__ all_in, unsigned long long* __restrict__ count) {
+  constexpr int R = K / 2, KK = K * K;
+  __shared__ double sm[16];
+  const int n = blockIdx.y, HW = H * W;
+  const unsigned char* g = gt + (i64)n * Hg * Wg;
+  const unsigned char* m = mix + (i64)n * Hg * Wg;
+  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
+  double cnt = 0.0;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    bool all = true;
+    for (int k = 0; k < KK && all; ++k) {
+      const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
+      all = sy >= 0 && sy < H && sx >= 0 && sx < W && m[(i64)nearest_src(sy, sgy, Hg) * Wg + nearest_src(sx, sgx, Wg)] == 0;
+    }
+    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+    const bool v = all && ctr != 255;
+    valid[(i64)n * HW + p] = v;
+    if (all_in) all_in[(i64)n * HW + p] = all;
+    cnt += v ? 1.0 : 0.0;
+  }
+  cnt = block_sum_d(cnt, sm);
+  if (threadIdx.x == 0 && cnt > 0.0) atomicAdd(count, (unsigned long long)cnt);
+}
+
+// ---- top-k target losses, K x K.  Rank-count selection instead of a sort (no dynamic indexing of the per-thread arrays):
+// rank_j = #{i : s_i > s_j or (s_i == s_j and i < j)} -- stable descending order, lower index first on ties, as the 3x3 kernel's
+// insertion sort.  The top-(top_k+1) set is ranks 0..top_k, the bottom-top_k set ranks K^2-top_k..K^2-1; for 2 top_k + 1 > K^2 the
+// sets overlap and a pair in both contributes to both losses and both gradient terms (torch.topk + gather in the reference).
+template <int K>
+__global__ __launch_bounds__(256) void topk_loss_k_kernel(const float* __restrict__ ema_sim, const float* __restrict__ prob,
+                                                          const unsigned char* __restrict__ valid, const unsigned long long* __restrict__ count,
+                                                          int C, int H, int W, int dil, int top_k, float w_pos, float w_neg,
+                                                          float* __restrict__ gP, double* __restrict__ acc, float* __restrict__ gS) {
+  constexpr int R = K / 2, KK = K * K;
+  __shared__ double sm[16];
+  const int n = blockIdx.y, HW = H * W;
+  const double cnt = (double)count[0];
+  const bool all_pairs = top_k == 0;          // top_k=None: every one of the K^2 pairs, both losses
+  const float cpos = cnt > 1.0 ? (float)((double)w_pos / (cnt * (all_pairs ? KK : top_k + 1))) : 0.f;
+  const float cneg = cnt > 1.0 ? (float)((double)w_neg / (cnt * (all_pairs ? KK : top_k))) : 0.f;
+  const float* pp = prob + (i64)n * C * HW;
+  double spos = 0.0, sneg = 0.0;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const i64 base = (i64)n * KK * HW + p;
+    if (!valid[(i64)n * HW + p]) {
+      for (int k = 0; k < KK; ++k) {
+        gP[base + (i64)k * HW] = 0.f;
+        if (gS) gS[base + (i64)k * HW] = 0.f;
+      }
+      continue;
+    }
+    const int y = p / W, x = p - y * W;
+    float s[KK];                 // the only per-pixel array: indexed by compile-time constants alone
+#pragma unroll
+    for (int k = 0; k < KK; ++k) s[k] = ema_sim[base + (i64)k * HW];
+    for (int j = 0; j < KK; ++j) {
+      const float sj = ema_sim[base + (i64)j * HW];        // (an L1 hit) instead of s[j] with a run-time j
+      bool pos = true, neg = true;
+      if (!all_pairs) {
+        int rank = 0;
+#pragma unroll
+        for (int i = 0; i < KK; ++i) rank += (s[i] > sj || (s[i] == sj && i < j)) ? 1 : 0;
+        pos = rank <= top_k;
+        neg = rank >= KK - top_k;
+      }
+      float gj = 0.f, gsj = 0.f;
+      if (pos || neg) {
+        const int q = (y + (j / K - R) * dil) * W + x + (j % K - R) * dil;     // always inside for valid pixels
+        float P = 0.f;
+        for (int c = 0; c < C; ++c) P = fmaf(pp[(i64)c * HW + p], pp[(i64)c * HW + q], P);
+        if (pos) {                 // loc_pos = -sim * P
+          spos += (double)(-sj * P);
+          gj = -sj * cpos;
+          gsj = -P * cpos;
+        }
+        if (neg) {                 // loc_neg = -(1-sim) * (1-P)
+          sneg += (double)(-(1.f - sj) * (1.f - P));
+          gj += (1.f - sj) * cneg;
+          gsj += (1.f - P) * cneg;
+        }
+      }
+      gP[base + (i64)j * HW] = gj;
+      if (gS) gS[base + (i64)j * HW] = gsj;
+    }
+  }
+  spos = block_sum_d(spos, sm);
+  sneg = block_sum_d(sneg, sm);
+  if (threadIdx.x == 0) {
+    if (spos != 0.0) atomicAdd(&acc[0], spos);
+    if (sneg != 0.0) atomicAdd(&acc[1], sneg);
+  }
+}
+
+// ---- gradient of the cross-probabilities into the student logits, K x K (cross_prob_bwd_kernel; mirror tap K^2-1-k)
+template <int K>
+__global__ __launch_bounds__(256) void cross_prob_bwd_k_kernel(const float* __restrict__ prob, const float* __restrict__ gP, int C, int H,
+                                                               int W, int dil, int ds, int unfold_grad, float* __restrict__ dlogits, int h, int w) {
+  constexpr int R = K / 2, KK = K * K;
+  const int n = blockIdx.y, HW = H * W;
+  const float* pp = prob + (i64)n * C * HW;
+  float* dl = dlogits + (i64)n * C * h * w;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    float g[KK];
+    int off[KK];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+      g[k] = gP[((i64)n * KK + k) * HW + p];
+      const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
+      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
+      off[k] = in ? sy * W + sx : -1;
+      if (unfold_grad && in) g[k] += gP[((i64)n * KK + (KK - 1 - k)) * HW + off[k]];
+      any = any || g[k] != 0.f;
+    }
+    if (!any) continue;
+    float dot = 0.f;  // sum_j p_j * dprob_j
+    for (int c = 0; c < C; ++c) {
+      float d = 0.f;
+#pragma unroll
+      for (int k = 0; k < KK; ++k) if (off[k] >= 0) d = fmaf(g[k], pp[(i64)c * HW + off[k]], d);
+      dot = fmaf(pp[(i64)c * HW + p], d, dot);
+    }
+    const int so = (y * ds) * w + x * ds;
+    for (int c = 0; c < C; ++c) {
+      float d = 0.f;
+#pragma unroll
+      for (int k = 0; k < KK; ++k) if (off[k] >= 0) d = fmaf(g[k], pp[(i64)c * HW + off[k]], d);
+      dl[(i64)c * h * w + so] += pp[(i64)c * HW + p] * (d - dot);
+    }
+  }
+}
+
+__global__ void sim_loss_finalize_k_kernel(const double* __restrict__ acc, const unsigned long long* __restrict__ count, int kk, int top_k,
+                                           float w_pos, float w_neg, float* __restrict__ out) {
+  const double cnt = (double)count[0];
+  out[0] = cnt > 1.0 ? (float)((double)w_pos * acc[0] / (cnt * (top_k == 0 ? kk : top_k + 1))) : 0.f;
+  out[1] = cnt > 1.0 ? (float)((double)w_neg * acc[1] / (cnt * (top_k == 0 ? kk : top_k))) : 0.f;
+}
+
+inline bool ksize_ok(int ksize) { return ksize == 3 || ksize == 5 || ksize == 7; }
+
+// one launch of a kernel template instantiated for K = 3, 5, 7
+#define PFST_KSIZE_SWITCH(ksize, LAUNCH)   \
+  switch (ksize) {                         \
+    case 3: { constexpr int K_ = 3; LAUNCH; break; } \
+    case 5: { constexpr int K_ = 5; LAUNCH; break; } \
+    default: { constexpr int K_ = 7; LAUNCH; break; } \
+  }
+
+template <int K, bool GAUSS>
+void launch_sim_map_k(const float* feat, int N, int C, int H, int W, int dil, int cc, float inv_sigma2, float* sim, float* norm, hipStream_t s) {
+  const int hal = (K / 2) * dil, la = kt_edge(hal) * kt_edge(hal);
+  const dim3 grid(cdiv(W, KT), cdiv(H, KT), N);
+  const size_t lds = (size_t)(cc + 1) * la * sizeof(float);
+  if (dil == 1) hipLaunchKernelGGL((sim_map_k_kernel<K, 1, GAUSS>), grid, dim3(KT * KT), lds, s, feat, C, H, W, dil, cc, inv_sigma2, sim, norm);
+  else if (dil == 2) hipLaunchKernelGGL((sim_map_k_kernel<K, 2, GAUSS>), grid, dim3(KT * KT), lds, s, feat, C, H, W, dil, cc, inv_sigma2, sim, norm);
+  else hipLaunchKernelGGL((sim_map_k_kernel<K, 0, GAUSS>), grid, dim3(KT * KT), lds, s, feat, C, H, W, dil, cc, inv_sigma2, sim, norm);
+}
+
+template <int K>
+void launch_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int dil,
+                          int gauss, float inv_sigma2, int cc, float* dfeat, int accumulate, float* coef, hipStream_t s) {
+  const dim3 gp(px_blocks((i64)H * W), N);
+  if (gauss) hipLaunchKernelGGL((sim_bwd_coef_k_kernel<K, true>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, inv_sigma2, coef);
+  else hipLaunchKernelGGL((sim_bwd_coef_k_kernel<K, false>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, 0.f, coef);
+  const int hal = (K / 2) * dil, la = kt_edge(hal) * kt_edge(hal);
+  const dim3 grid(cdiv(W, KT), cdiv(H, KT), N);
+  const size_t lds = (size_t)cc * la * sizeof(float);
+  if (dil == 1) hipLaunchKernelGGL((sim_map_bwd_k_kernel<K, 1>), grid, dim3(KT * KT), lds, s, feat, coef, C, H, W, dil, cc, dfeat, accumulate);
+  else if (dil == 2) hipLaunchKernelGGL((sim_map_bwd_k_kernel<K, 2>), grid, dim3(KT * KT), lds, s, feat, coef, C, H, W, dil, cc, dfeat, accumulate);
+  else hipLaunchKernelGGL((sim_map_bwd_k_kernel<K, 0>), grid, dim3(KT * KT), lds, s, feat, coef, C, H, W, dil, cc, dfeat, accumulate);
+}
+
+}  // namespace
+
+extern "C" int pfst_sim_map_k(const float* feat, int N, int C, int H, int W, int ksize, int dil, int sim_type, float sigma, float* sim,
+                              float* norm, pfst_stream_t stream) {
+  PFST_CHECK_ARG(feat && sim && norm && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 && ksize_ok(ksize));
+  PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
+  const int cc = kt_chunk((ksize / 2) * dil, true);
+  PFST_CHECK_ARG(cc > 0);                 // (ksize/2) * dil <= 37: the halo tile fits the workgroup's LDS
+  hipStream_t s = (hipStream_t)stream;
+  if (sim_type == 1) {
+    PFST_KSIZE_SWITCH(ksize, (launch_sim_map_k<K_, true>(feat, N, C, H, W, dil, cc, 1.f / (sigma * sigma), sim, norm, s)));
+  } else {
+    PFST_KSIZE_SWITCH(ksize, (launch_sim_map_k<K_, false>(feat, N, C, H, W, dil, cc, 0.f, sim, norm, s)));
+  }
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W,
+                                  int ksize, int dil, int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws,
+                                  pfst_stream_t stream) {
+  PFST_CHECK_ARG(feat && sim && norm && gsim && dfeat && coef_ws && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 &&
+                 ksize_ok(ksize));
+  PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
+  const int cc = kt_chunk((ksize / 2) * dil, false);
+  PFST_CHECK_ARG(cc > 0);
+  const float inv_s2 = sim_type == 1 ? 1.f / (sigma * sigma) : 0.f;
+  PFST_KSIZE_SWITCH(ksize, (launch_sim_map_bwd_k<K_>(feat, sim, norm, gsim, N, C, H, W, dil, sim_type, inv_s2, cc, dfeat, accumulate,
+                                                     coef_ws, (hipStream_t)stream)));
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_src_sim_stats_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                                    int loss_type, float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream) {
+  PFST_CHECK_ARG(sim && gt && stats && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
+  PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(stats, 0, 6 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
+  const int gxs = px_blocks((i64)H * W);
+  double* det = nullptr;
+  if (pfst_deterministic()) {
+    det = static_cast<double*>(pfst_det_scratch((size_t)gxs * N * 6 * sizeof(double), s));
+    PFST_CHECK_ARG(det != nullptr);
+  }
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_stats_k_kernel<K_>, dim3(gxs, N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, loss_type,
+                                              margin_pos, margin_neg, stats, reinterpret_cast<const SrcSel*>(select), det));
+  if (det) hipLaunchKernelGGL(src_stats_det_sum_kernel, dim3(1), dim3(64), 0, s, det, gxs * N, stats);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_src_sim_grad_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                                   int loss_type, float margin_pos, float margin_neg, const double* stats, float w_pos, float w_neg,
+                                   float w_pos_std, float w_neg_std, float* gsim, float* losses, const void* select, pfst_stream_t stream) {
+  PFST_CHECK_ARG(sim && gt && stats && gsim && losses && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 &&
+                 ksize_ok(ksize));
+  PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_grad_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, sim,
+                                              gt, H, W, Hg, Wg, dil, loss_type, margin_pos, margin_neg, stats, w_pos, w_neg, w_pos_std,
+                                              w_neg_std, gsim, losses, reinterpret_cast<const SrcSel*>(select)));
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_src_sim_select_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                                     double src_perc, void* select, pfst_stream_t stream) {
+  PFST_CHECK_ARG(sim && gt && select && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
+  PFST_CHECK_ARG(src_perc >= 0.0 && src_perc <= 1.0 && (reinterpret_cast<uintptr_t>(select) & 7) == 0);
+  hipStream_t s = (hipStream_t)stream;
+  SrcSel* st = reinterpret_cast<SrcSel*>(select);
+  unsigned int* hist = reinterpret_cast<unsigned int*>(st + 2);
+  for (int pass = 0; pass < 4; ++pass) {
+    if (pass == 0) hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, 2);
+    PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_sel_hist_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, sim, gt, H, W,
+                                                Hg, Wg, dil, st, hist));
+    hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, pass == 0 ? 1 : 0);
+  }
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_trg_valid_mask_k(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int ksize,
+                                     int dil, unsigned char* valid, unsigned char* all_in, unsigned long long* count, pfst_stream_t stream) {
+  PFST_CHECK_ARG(gt && mix_mask && valid && count && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), s) != hipSuccess) return PFST_ERR_LAUNCH;
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(trg_valid_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, gt, mix_mask, H, W,
+                                              Hg, Wg, dil, valid, all_in, count));
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_sim_topk_loss_k(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
+                                    int N, int C, int H, int W, int ksize, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
+                                    float* g_sim, pfst_stream_t stream) {
+  PFST_CHECK_ARG(ema_sim && prob && valid && count && gP && acc && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 &&
+                 ksize_ok(ksize));
+  PFST_CHECK_ARG(top_k >= 0 && top_k <= ksize * ksize - 1);     // 0 = all K^2 pairs (top_k=None)
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(acc, 0, 2 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(topk_loss_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, ema_sim, prob, valid,
+                                              count, C, H, W, dil, top_k, w_pos, w_neg, gP, acc, g_sim));
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_cross_prob_bwd_k(const float* prob, const float* gP, int N, int C, int H, int W, int ksize, int dil, int ds,
+                                     int unfold_grad, float* dlogits, int h, int w, pfst_stream_t stream) {
+  PFST_CHECK_ARG(prob && gP && dlogits && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 && ds >= 1 && ksize_ok(ksize));
+  PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(cross_prob_bwd_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream,
+                                              prob, gP, C, H, W, dil, ds, unfold_grad, dlogits, h, w));
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_sim_loss_finalize_k(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg,
+                                        float* out, pfst_stream_t stream) {
+  PFST_CHECK_ARG(acc && count && out && ksize_ok(ksize) && top_k >= 0 && top_k <= ksize * ksize - 1);
+  hipLaunchKernelGGL(sim_loss_finalize_k_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, acc, count, ksize * ksize, top_k, w_pos, w_neg, out);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }

@@ -33,20 +33,22 @@ class PFGSTLoss(nn.Module):
         super().__init__()
         # Implemented: the shipped options plus the variants reachable from the same configs: sim_type
         # 'cosine' | 'gaussian' (sigma), src_loss_type 'mean_std' | 'margin' | 'margin2' (margin), detach_unfold True | False,
-        # top_k 1..4 | None, downscale 0.5 | 1 | None, feat_level None | 0..3 (a backbone feature map instead of the decoded
-        # features, with PFGST(use_decoded_feats=False)), src_perc (the hardest fraction of the source pairs), proj_net_cfg (a
-        # trainable 1x1 projection of both feature maps).  Everything else (cross_prob_type='ema', kernel_size != 3) fails loudly.
-        bad = dict(kernel_size=kernel_size != 3, sim_type=sim_type not in ('cosine', 'gaussian'),
+        # kernel_size 3 | 5 | 7 (odd: the reference's view(-1, k*k, H, W) fails for even sizes), top_k 1..kernel_size^2-1 | None,
+        # downscale 0.5 | 1 | None, feat_level None | 0..3 (a backbone feature map instead of the decoded features, with
+        # PFGST(use_decoded_feats=False)), src_perc (the hardest fraction of the source pairs), proj_net_cfg (a trainable 1x1
+        # projection of both feature maps).  Everything else (cross_prob_type='ema', other kernel sizes) fails loudly.
+        kk = kernel_size * kernel_size if kernel_size in (3, 5, 7) else 0
+        bad = dict(kernel_size=kk == 0, sim_type=sim_type not in ('cosine', 'gaussian'),
                    feat_level=feat_level is not None and feat_level not in (0, 1, 2, 3),
                    src_perc=src_perc is not None and not 0.0 <= src_perc <= 1.0,
                    proj_net=proj_net_cfg is not None and not {'in_channels', 'out_channels'} <= set(proj_net_cfg),
                    src_loss_type=src_loss_type not in ('mean_std', 'margin', 'margin2'), cross_prob_type=cross_prob_type != 'trg',
-                   downscale=downscale not in (None, 0.5, 1, 1.0), top_k=top_k is not None and not (1 <= top_k <= 4),
+                   downscale=downscale not in (None, 0.5, 1, 1.0), top_k=top_k is not None and not (1 <= top_k <= kk - 1),
                    weights=not isinstance(weights, dict), sigma=not sigma > 0)
         bad = [k for k, v in bad.items() if v]
         if bad:
             raise NotImplementedError(f'PFGSTLoss options outside the implemented set: {bad}')
-        self.top_k, self.dilation, self.weights = top_k, dilation, dict(weights)
+        self.top_k, self.dilation, self.kernel_size, self.weights = top_k, dilation, kernel_size, dict(weights)
         self.sim_type, self.sigma = sim_type, float(sigma)
         self.src_loss_type, self.margin = src_loss_type, tuple(margin)
         self.unfold_grad = not detach_unfold
@@ -70,13 +72,13 @@ class PFGSTLoss(nn.Module):
         if isinstance(x_src, (tuple, list)) or isinstance(x_ema, (tuple, list)):
             raise TypeError('PFGSTLoss: x_src / x_ema are feature tuples (use_decoded_feats=False) but feat_level is None')
         gt8, mm8 = tensors['gt_src'], tensors['mix_masks']
-        d, w = self.dilation, self.weights
+        d, w, ks = self.dilation, self.weights, self.kernel_size
         n, c, h, wd = lt.data.shape
         H, W = h // self.ds, wd // self.ds
         # F.interpolate(x, size=(H, W)) nearest (pfgst_loss.py:57-58): identity for downscale 0.5; for downscale 1 the
         # 1/8 features are replicated u x u onto the 1/4 grid, where a dilation-d neighbourhood is EXACTLY the
         # dilation-d/u neighbourhood of the source grid -- so the similarity is computed at the source resolution
-        # and only the tiny 9-channel map is replicated (its adjoint is a u x u sum).
+        # and only the tiny k^2-channel map is replicated (its adjoint is a u x u sum).
         hf, wf = x_src.data.shape[-2:]
         if x_ema.data.shape[-2:] != (hf, wf) or H % hf != 0 or H // hf != W // wf:
             raise NotImplementedError(f'PFGSTLoss: feature grid {hf}x{wf} does not divide the logit grid {H}x{W}')
@@ -94,18 +96,18 @@ class PFGSTLoss(nn.Module):
             from .engine import Var
             x_src = Var(proj.fprop(raw_src.data, bias=proj.bias.data), True)
             x_ema = Var(proj.fprop(raw_ema.data, bias=proj.bias.data), False)
-        ema_sim, ema_norm = ops.sim_map(x_ema.data, fd, self.sim_type, self.sigma)
-        src_sim_f, src_norm = ops.sim_map(x_src.data, fd, self.sim_type, self.sigma)
+        ema_sim, ema_norm = ops.sim_map(x_ema.data, fd, self.sim_type, self.sigma, ksize=ks)
+        src_sim_f, src_norm = ops.sim_map(x_src.data, fd, self.sim_type, self.sigma, ksize=ks)
         src_sim = src_sim_f
         ema_sim_lowres = ema_sim
         if u > 1:
             ema_sim, src_sim = ops.upsample_nearest(ema_sim, u), ops.upsample_nearest(src_sim_f, u)
         l4, gsim = ops.src_sim_losses(src_sim, gt8, d, w['src_pos'], w['src_neg'], w.get('src_pos_std', 0.0), w.get('src_neg_std', 0.0),
-                                      self.src_loss_type, self.margin, src_perc=self.src_perc)
+                                      self.src_loss_type, self.margin, src_perc=self.src_perc, ksize=ks)
         prob = ops.softmax_down(lt.data, self.ds)
-        valid, all9, cnt = ops.trg_valid_mask(gt8, mm8, (H, W), d)
+        valid, all9, cnt = ops.trg_valid_mask(gt8, mm8, (H, W), d, ksize=ks)
         res = ops.sim_topk_loss(ema_sim, prob, valid, cnt, d, self.top_k, w['sim_pos'], w['sim_neg'],
-                                want_sim_grad=proj is not None and tape is not None)
+                                want_sim_grad=proj is not None and tape is not None, ksize=ks)
         l2, gP = res[0], res[1]
         gS = res[2] if len(res) > 2 else None
         ema_sim_f = ema_sim_lowres if u > 1 else ema_sim
@@ -114,19 +116,20 @@ class PFGSTLoss(nn.Module):
                 buf, acc = x_src.grad_target()
                 g_f = gsim if u == 1 else ops.upsample_nearest_bwd(gsim, u)
                 ops.sim_map_bwd(x_src.data, src_sim_f, src_norm, g_f, fd, out=buf, accumulate=acc, sim_type=self.sim_type,
-                                sigma=self.sigma)
+                                sigma=self.sigma, ksize=ks)
                 if proj is not None:
                     # the projection's weights collect gradient from BOTH branches: the teacher-side similarity is a function of
                     # them too (the reference's x_ema carries no graph, proj_net(x_ema) does)
                     gs_f = gS if u == 1 else ops.upsample_nearest_bwd(gS, u)
-                    g_ema = ops.sim_map_bwd(x_ema.data, ema_sim_f, ema_norm, gs_f, fd, sim_type=self.sim_type, sigma=self.sigma)
+                    g_ema = ops.sim_map_bwd(x_ema.data, ema_sim_f, ema_norm, gs_f, fd, sim_type=self.sim_type, sigma=self.sigma,
+                                            ksize=ks)
                     ops.conv_wgrad_(proj.weight.grad, raw_ema.data, g_ema, 1)
                     ops.bias_grad_(proj.bias.grad, g_ema)
                     layers.conv_backward(raw_src, proj, x_src.grad)
                 buf, acc = lt.grad_target()
                 if not acc:
                     ops.fill_(buf, 0.0)
-                ops.cross_prob_bwd_(buf, prob, gP, d, self.ds, self.unfold_grad)
+                ops.cross_prob_bwd_(buf, prob, gP, d, self.ds, self.unfold_grad, ksize=ks)
             # tagged like every closure of the network, so a Tape observer (the per-link backward test) sees the link as wired:
             # it writes dL/dx_src (first writer of that buffer in the sweep) and dL/dlogits_trg, into which the mixed pass's CE
             # backward accumulates afterwards
@@ -138,7 +141,7 @@ class PFGSTLoss(nn.Module):
             out = OrderedDict(loss_src_pos=l4[0:1], loss_src_neg=l4[1:2])
         out.update(loss_sim_pos=l2[0:1], loss_sim_neg=l2[1:2])
         if tensors.get('want_vis'):
-            # pfgst_loss.py:134-137: (img_trg, 1 - mean_k sim_ema, the all-nine-neighbours-unmixed mask) -- visualisation only, built
+            # pfgst_loss.py:134-137: (img_trg, 1 - mean_k sim_ema, the all-k^2-neighbours-unmixed mask) -- visualisation only, built
             # with torch ops because it is off the hot path (PFGST.return_vis_states)
             out['vis|density_sim_feat'] = (tensors.get('img_trg'), 1 - ema_sim.mean(dim=1, keepdim=True), all9.bool())
         return out
