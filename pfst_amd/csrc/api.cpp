@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
+#include <mutex>
 #include "../../include/pfst_hip.h"
 
 static char g_err[512] = "no error";
@@ -24,29 +25,66 @@ extern "C" int pfst_set_deterministic(int on) {
 extern "C" int pfst_get_deterministic(void) { return g_deterministic; }
 
 // Scratch of the deterministic mode's partial sums (the only memory the library allocates itself; nothing outside that mode touches it): one
-// grow-only buffer per stream -- a launcher fills it, a second kernel of the same launcher reduces it, both queued on that stream.
+// grow-only buffer per (device, stream) -- a launcher fills it, a second kernel of the same launcher reduces it, both queued on that stream.
+// The table has a fixed number of slots; a launch on a stream beyond them takes the least recently used slot over.  On failure the message
+// names this scratch (pfst_last_error) and the launcher returns PFST_ERR_LAUNCH without a message of its own (PFST_CHECK_DET).
+static void* det_scratch_fail(int line, const char* what, size_t bytes, hipError_t e) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "deterministic-mode scratch of %zu bytes: %s failed (%s)", bytes, what, hipGetErrorString(e));
+  pfst_set_error(__FILE__, line, msg);
+  return nullptr;
+}
+
 void* pfst_det_scratch(size_t bytes, void* stream) {
-  static struct { void* stream; void* buf; size_t cap; } slots[8];
+  constexpr int kSlots = 8;
+  struct Slot { int dev; void* stream; void* buf; size_t cap; unsigned long long used; };
+  static Slot slots[kSlots];
+  static unsigned long long clock = 0;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  // The key holds the device as well as the stream: the default stream's handle (NULL) is the same number on every device.  (A one-GPU test
+  // box cannot tell the two halves of the key apart; tests/test_deterministic_kernels_gpu.py covers the stream half.)
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return det_scratch_fail(__LINE__, "hipGetDevice", bytes, e);
   int at = -1;
-  for (int i = 0; i < 8; ++i)
-    if (slots[i].buf && slots[i].stream == stream) at = i;
-  if (at < 0)
-    for (int i = 0; i < 8 && at < 0; ++i)
-      if (!slots[i].buf) at = i;
-  if (at < 0) return nullptr;
-  if (slots[at].cap < bytes) {
-    if (slots[at].buf) {
-      if (hipDeviceSynchronize() != hipSuccess) return nullptr;       // earlier launches may still read the old buffer
-      (void)hipFree(slots[at].buf);
-      slots[at].buf = nullptr;
-      slots[at].cap = 0;
+  for (int i = 0; i < kSlots && at < 0; ++i)
+    if (slots[i].buf && slots[i].dev == dev && slots[i].stream == stream) at = i;
+  for (int i = 0; i < kSlots && at < 0; ++i)
+    if (!slots[i].buf) at = i;
+  if (at < 0) {
+    // every slot is held: evict the least recently used one.  Its stream may have been destroyed since, so wait for all work of its device
+    // (which may still read the buffer) rather than for that stream.
+    at = 0;
+    for (int i = 1; i < kSlots; ++i)
+      if (slots[i].used < slots[at].used) at = i;
+    if (slots[at].dev != dev && (e = hipSetDevice(slots[at].dev)) != hipSuccess) return det_scratch_fail(__LINE__, "hipSetDevice", bytes, e);
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipFree(slots[at].buf);
+    const hipError_t e_back = slots[at].dev != dev ? hipSetDevice(dev) : hipSuccess;
+    if (e != hipSuccess) return det_scratch_fail(__LINE__, "eviction (hipDeviceSynchronize / hipFree)", bytes, e);
+    if (e_back != hipSuccess) return det_scratch_fail(__LINE__, "hipSetDevice", bytes, e_back);
+    slots[at] = Slot{};
+  }
+  Slot& sl = slots[at];
+  if (sl.cap < bytes) {
+    if (sl.buf) {
+      if ((e = hipDeviceSynchronize()) != hipSuccess)                 // earlier launches may still read the old buffer
+        return det_scratch_fail(__LINE__, "hipDeviceSynchronize before regrowth", bytes, e);
+      (void)hipFree(sl.buf);
+      sl = Slot{};
     }
     const size_t cap = bytes < (size_t(8) << 20) ? (size_t(8) << 20) : bytes + bytes / 2;
-    if (hipMalloc(&slots[at].buf, cap) != hipSuccess) return nullptr;
-    slots[at].cap = cap;
-    slots[at].stream = stream;
+    if ((e = hipMalloc(&sl.buf, cap)) != hipSuccess) {
+      sl = Slot{};
+      return det_scratch_fail(__LINE__, "hipMalloc", bytes, e);
+    }
+    sl.cap = cap;
   }
-  return slots[at].buf;
+  sl.dev = dev;
+  sl.stream = stream;
+  sl.used = ++clock;
+  return sl.buf;
 }
 
 extern "C" const char* pfst_last_error(void) { return g_err; }

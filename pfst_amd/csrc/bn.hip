@@ -712,7 +712,7 @@ extern "C" int pfst_bn_stats(const float* x, long long x_bs, int N, int C, int H
   split_for(HW, C, N, splits, chunk);
   bool det_ok;
   double* const det = bn_det_part(C, N, splits, s, det_ok);
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   hipLaunchKernelGGL(bn_stats_kernel, dim3(splits, C, N), dim3(256), 0, s, x, x_bs, HW, chunk, ws, det);
   if (det) hipLaunchKernelGGL(bn_det_sum_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, det, N * splits, C, ws);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, ws, C, (double)N * HW, mean, invstd, running_mean,
@@ -781,7 +781,7 @@ extern "C" int pfst_bn_backward(const float* dy, long long dy_bs, const float* y
   split_for(HW, C, N, splits, chunk);
   bool det_ok = true;
   double* const det = fused ? nullptr : bn_det_part(C, N, splits, s, det_ok);      // deterministic mode: slots + ordered sum instead of atomics
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   const bool vec = (HW & 3) == 0 && ((dy_bs | x_bs | dx_bs | (y ? y_bs : 0) | (dres ? dres_bs : 0)) & 3) == 0 &&
                    (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)y | (uintptr_t)dres) & 15) == 0;
   int gx = cdiv(HW, 256 * 4 * (vec ? PFST_BN_BWD_APPLY_U : 1));
@@ -864,7 +864,7 @@ extern "C" int pfst_bn_backward_sums(const float* dy, long long dy_bs, const flo
     const unsigned long long* nomask = nullptr;
     bool det_ok;
     double* const det = bn_det_part(C, N, splits, s, det_ok);
-    PFST_CHECK_ARG(det_ok);
+    PFST_CHECK_DET(det_ok);
     if (vec)
       hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(splits, C, N), dim3(256), 0, s, dy, (i64)dy_bs, none, (i64)0, x, (i64)x_bs, mean, invstd, gamma,
                          beta, HW, chunk, 1, nomask, ws, (pfst_bn_order() >> 1) & 1, none, det);

@@ -25,6 +25,12 @@
     }                                                          \
   } while (0)
 
+// the deterministic-mode scratch could not be had: pfst_det_scratch (or det.h, for its clearing) has set the message already
+#define PFST_CHECK_DET(ok)                                     \
+  do {                                                         \
+    if (!(ok)) return PFST_ERR_LAUNCH;                         \
+  } while (0)
+
 void pfst_set_error(const char* file, int line, const char* msg);
 int pfst_deterministic(void);            // api.cpp: pfst_set_deterministic -- fixed-order sums instead of atomics between workgroups
 void* pfst_det_scratch(size_t bytes, void* stream);   // api.cpp: that mode's partial-sum scratch of `stream` (NULL: allocation failed)

@@ -1167,7 +1167,7 @@ int pfst_wgrad_f16x3_launch(const float* x, i64 x_bs, const float* dy, i64 dy_bs
   const i64 elems = (i64)M * J;
   bool det_ok;
   float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   float* const dwk = ws ? ws : dw;
   const i64 gsk = ws ? -elems : dw_gs;
 #define PFST_LAUNCH_WGRAD(KERNEL_, THREADS_)                                                                                               \

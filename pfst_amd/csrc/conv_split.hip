@@ -1191,7 +1191,7 @@ int launch_wgrad_split_q(const float* x, i64 x_bs, const float* dy, i64 dy_bs, f
   const i64 elems = (i64)M * J;
   bool det_ok;
   float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   float* const dwk = ws ? ws : dw;
   const i64 gsk = ws ? -elems : dw_gs;
   if (BM == 128)
@@ -1218,7 +1218,7 @@ int launch_wgrad_split(const float* x, i64 x_bs, const float* dy, i64 dy_bs, flo
   const i64 elems = (i64)M * J;
   bool det_ok;
   float* const ws = wgrad_det_scratch(elems, (i64)N * chunks, s, det_ok);          // deterministic mode (det.h)
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   hipLaunchKernelGGL((conv_wgrad_split_kernel<BM, T>), grid, dim3(256), 0, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho, Wo, stride,
                      dil, pad, chunks, chunk_len, ws ? elems : (i64)0);
   if (ws) wgrad_det_reduce(ws, dw, elems, 1, N * chunks, 0, s);

@@ -509,7 +509,7 @@ int launch_q(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, in
   const i64 elems = (i64)M * J;
   bool det_ok;
   float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   hipLaunchKernelGGL((conv_wgrad_q_kernel<BM, T, WBK>), grid, dim3(256), g_wgrad_lds_pad, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho, Wo,
                      dil, pad, chunks, chunk_len, N, x_gs, dy_gs, ws ? -elems : dw_gs, gx, gy, gz, xcd_env);
   if (ws) wgrad_det_reduce(ws, dw, elems, groups, N * chunks, dw_gs, s);
@@ -546,7 +546,7 @@ int launch_q16(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, 
   const i64 elems = (i64)M * J;
   bool det_ok;
   float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_ARG(det_ok);
+  PFST_CHECK_DET(det_ok);
   hipLaunchKernelGGL((conv_wgrad_q16_kernel<BM, T>), dim3(gx * gy * gz), dim3(256), g_wgrad_lds_pad, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho,
                      Wo, dil, pad, chunks, chunk_len, N, (i64)0, (i64)0, ws ? -elems : (i64)0, gx, gy, gz, xcd_env, x_amax, dy_amax);
   if (ws) wgrad_det_reduce(ws, dw, elems, 1, N * chunks, 0, s);

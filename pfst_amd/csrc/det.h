@@ -23,8 +23,12 @@ inline float* wgrad_det_scratch(i64 elems, i64 slices, hipStream_t s, bool& ok) 
   ok = true;
   if (!pfst_deterministic()) return nullptr;
   const size_t bytes = sizeof(float) * (size_t)elems * (size_t)slices;
-  float* ws = static_cast<float*>(pfst_det_scratch(bytes, s));
-  ok = ws != nullptr && hipMemsetAsync(ws, 0, bytes, s) == hipSuccess;
+  float* ws = static_cast<float*>(pfst_det_scratch(bytes, s));          // (sets the message when it fails)
+  ok = ws != nullptr;
+  if (ok && hipMemsetAsync(ws, 0, bytes, s) != hipSuccess) {
+    pfst_set_error(__FILE__, __LINE__, "deterministic-mode scratch: hipMemsetAsync failed");
+    ok = false;
+  }
   return ok ? ws : nullptr;
 }
 

@@ -806,7 +806,7 @@ extern "C" int pfst_dwconv3x3_bwd(const float* dy, long long dy_bs, const float*
   if (det_T) {
     const size_t bytes = (size_t)C * det_T * 9 * sizeof(float);
     dwk = static_cast<float*>(pfst_det_scratch(bytes, st));
-    PFST_CHECK_ARG(dwk != nullptr);
+    PFST_CHECK_DET(dwk != nullptr);
     if (hipMemsetAsync(dwk, 0, bytes, st) != hipSuccess) return PFST_ERR_LAUNCH;
   }
   if (plane) {
@@ -932,7 +932,7 @@ extern "C" int pfst_dwconv3x3_multi_bwd(const float* x, long long x_bs, int ns, 
   if (det_T) {
     const size_t per = (size_t)C * det_T * 9, bytes = per * ns * sizeof(float);
     float* part = static_cast<float*>(pfst_det_scratch(bytes, st));
-    PFST_CHECK_ARG(part != nullptr);
+    PFST_CHECK_DET(part != nullptr);
     if (hipMemsetAsync(part, 0, bytes, st) != hipSuccess) return PFST_ERR_LAUNCH;
     for (int i = 0; i < 3; ++i) S.dw[i] = part + (size_t)(i < ns ? i : 0) * per;
   }
@@ -974,7 +974,7 @@ extern "C" int pfst_dwconv3x3_wgrad(const float* x, long long x_bs, const float*
   if (det_T) {
     const size_t bytes = (size_t)C * det_T * 9 * sizeof(float);
     dwk = static_cast<float*>(pfst_det_scratch(bytes, st));
-    PFST_CHECK_ARG(dwk != nullptr);
+    PFST_CHECK_DET(dwk != nullptr);
     if (hipMemsetAsync(dwk, 0, bytes, st) != hipSuccess) return PFST_ERR_LAUNCH;
   }
   if (vec && dil % 4 == 0)

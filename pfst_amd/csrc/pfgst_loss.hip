@@ -828,7 +828,7 @@ extern "C" int pfst_src_sim_stats(const float* sim, const unsigned char* gt, int
   double* det = nullptr;
   if (pfst_deterministic()) {
     det = static_cast<double*>(pfst_det_scratch((size_t)gxs * N * 6 * sizeof(double), s));
-    PFST_CHECK_ARG(det != nullptr);
+    PFST_CHECK_DET(det != nullptr);
   }
   hipLaunchKernelGGL(src_stats_kernel, dim3(gxs, N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, loss_type, margin_pos,
                      margin_neg, stats, reinterpret_cast<const SrcSel*>(select), det);
@@ -1458,7 +1458,7 @@ extern "C" int pfst_src_sim_stats_k(const float* sim, const unsigned char* gt, i
   double* det = nullptr;
   if (pfst_deterministic()) {
     det = static_cast<double*>(pfst_det_scratch((size_t)gxs * N * 6 * sizeof(double), s));
-    PFST_CHECK_ARG(det != nullptr);
+    PFST_CHECK_DET(det != nullptr);
   }
   PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_stats_k_kernel<K_>, dim3(gxs, N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, loss_type,
                                               margin_pos, margin_neg, stats, reinterpret_cast<const SrcSel*>(select), det));

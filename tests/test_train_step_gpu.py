@@ -214,35 +214,58 @@ class count_fused_dgrad_launches:
             setattr(self.ops, fn, f)
 
 
-def test_train_step_at_512_matches_oracle():
+@pytest.fixture(scope='module')
+def oracle_512():
+    """the CPU oracle's fp32 step and its fp64 twin at b = 2 x 512^2, computed once for both legs of test_train_step_at_512_matches_oracle
+    -> (batch, fp32 log values, fp32 extras, fp64 extras)"""
+    from oracle import pfst_oracle as O
+    from pfst_amd.hostinfo import usable_cpus
+    from pfst_amd.synthetic import synth_batch
+    _, student, teacher = seeded_pfgst_state(O, 9)
+    oracle = O.OraclePFGST(student, pseudo_threshold=0.30, teacher_sd=teacher)
+    torch.set_num_threads(usable_cpus())
+    batch = synth_batch(2, 512, 6, seed=4242)
+    random.seed(101); np.random.seed(101)
+    olog, ex = oracle.train_step(batch, return_extras=True)
+    dd = lambda sd: {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    o64 = O.OraclePFGST(dd(student), pseudo_threshold=0.30, teacher_sd=dd(teacher))
+    b64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in batch.items()}
+    random.seed(101); np.random.seed(101)
+    _, ex64 = o64.train_step(b64, masks=ex['masks'], return_extras=True, pseudo_override=(ex['pseudo_label'], ex['n_conf']))
+    return batch, olog, ex, ex64
+
+
+@pytest.mark.parametrize('det', [False, True], ids=['default', 'deterministic'])
+def test_train_step_at_512_matches_oracle(oracle_512, det):
     """One whole step at b = 2 x 512^2 (BASELINE config #1's tile size) under the DEFAULT arithmetic against the oracle.
     At S = 128 a 1/8-grid GEMM has two pixel tiles per image; here it has 32, so the f16x3 machinery of round 3 sits inside an
     end-to-end comparison: workgroups walk tile CHAINS (1024 tiles of layer4.conv3 on 512 resident slots), grids run several rounds,
     the 3x3 kernels use the band tile order per XCD, the whole-line weight gradients split K over pixel chunks, the Winograd-domain
     GEMMs run image-after-image per filter set, and the K >= 512 data gradients carry the fused BatchNorm-backward sums.
-    Same checks as the S = 128 test: 14 log values, mixed-label map exact, logits element-wise, gradients against fp64."""
-    from oracle import pfst_oracle as O
+    Same checks as the S = 128 test: 14 log values, mixed-label map exact, logits element-wise, gradients against fp64.
+    det: the same step in deterministic mode (pfst_set_deterministic) -- at this size the split-K weight gradients run several pixel chunks
+    and the BatchNorm reductions several splits per plane, so every fixed-order reduction is live; every assertion of the default leg holds.
+    Only bn_backward_dual changes the wiring in that mode (the layers run one by one), so the fused data-gradient launches count the same."""
     from pfst_amd import hip_ops, layers
     from pfst_amd._lib import lib
-    from pfst_amd.hostinfo import usable_cpus
-    from pfst_amd.synthetic import synth_batch
     assert layers.CONV_MATH == os.environ.get('PFST_CONV_MATH', 'f16x3')
     b, S = 2, 512
     # the machinery engages at this size: more tiles than workgroups for the large 1x1 GEMMs -> chains
     tiles = (S // 8) * (S // 8) // 128 * (2048 // 128) * b            # layer4.conv3 in 128 x 128 tiles (the unit pfst_f16x3_chain_grid counts slots in)
     if layers.CONV_MATH == 'f16x3':
         assert lib().pfst_f16x3_chain_grid(tiles, 1) < tiles, 'layer4.conv3 would run one tile per workgroup: no chain in this test'
-    model, opt, student, teacher = _build(0.30)
-    oracle = O.OraclePFGST(student, pseudo_threshold=0.30, teacher_sd=teacher)
-    torch.set_num_threads(usable_cpus())
-    batch = synth_batch(b, S, 6, seed=4242)
-    random.seed(101); np.random.seed(101)
-    olog, ex = oracle.train_step(batch, return_extras=True)
+    batch, olog, ex, ex64 = oracle_512
+    model, opt, _, _ = _build(0.30)
     random.seed(101); np.random.seed(101)
     model.debug = {}
     model.injected_pseudo = (ex['pseudo_label'].to(torch.uint8).cuda(), torch.tensor([ex['n_conf']], dtype=torch.int64).cuda())
-    with count_fused_dgrad_launches() as launches:
-        out = model.train_step(to_dev(batch, 'cuda'), opt)
+    hip_ops.set_deterministic(det)
+    try:
+        with count_fused_dgrad_launches() as launches:
+            out = model.train_step(to_dev(batch, 'cuda'), opt)
+        torch.cuda.synchronize()
+    finally:
+        hip_ops.set_deterministic(False)
     dbg, lv = model.debug, out['log_vars']
     print(f'data-gradient launches {launches}')
     if layers.FUSE_BN_BWD and layers.CONV_MATH == 'f16x3' and layers.FUSE_BN_BWD_MIN_K_SPLIT <= 512:
@@ -267,12 +290,10 @@ def test_train_step_at_512_matches_oracle():
     assert_live_target_side(lv)
     # gradients: as close to fp64 as the oracle's own fp32 path (x5), 1e-3 next to the loss -- the criterion of the S = 128 test
     arena = model.student_arena
-    dd = lambda sd: {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
-    o64 = O.OraclePFGST(dd(student), pseudo_threshold=0.30, teacher_sd=dd(teacher))
-    b64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in batch.items()}
-    random.seed(101); np.random.seed(101)
-    _, ex64 = o64.train_step(b64, masks=ex['masks'], return_extras=True, pseudo_override=(ex['pseudo_label'], ex['n_conf']))
     rows = [(name, rel(arena.view(arena.grad, name), g64), rel(ex['grads'][name], g64)) for name, g64 in ex64['grads'].items()]
+    worst = max(rows, key=lambda t: t[1] / max(t[2], 1e-12))
+    print(f'{"deterministic" if det else "default"} leg: worst per-tensor gradient ratio HIP / oracle-fp32 vs fp64 '
+          f'{worst[1] / max(worst[2], 1e-12):.2f} ({worst[0]}: {worst[1]:.2e} / {worst[2]:.2e}); worst HIP rel err {max(r[1] for r in rows):.2e}')
     print('grad rel err vs fp64:  HIP / oracle-fp32 (worst ten by ratio)')
     for name, a, r in sorted(rows, key=lambda t: -t[1] / max(t[2], 1e-12))[:10]:
         print(f'   {a:.2e} {r:.2e} {name}')
