@@ -346,6 +346,15 @@ int pfst_argmax_nchw(const float* x, long long x_bs, unsigned char* label_u8, in
 /* output.flip(dims=(3,)) / (2,) (:316-325) on `planes` H x W maps, out of place */
 int pfst_flip_planes(const float* x, float* y, int planes, int H, int W, int horizontal, int vertical, pfst_stream_t stream);
 int pfst_div_scalar(float* x, long long n, float divisor, pfst_stream_t stream);                              /* seg_logit /= len(imgs) (:367) */
+/* aug_test (:355-372), one view in one pass, bit-identical to the chain resize_bilinear (src Hs x Ws -> input grid Hm x Wm; skipped when
+ * equal) -> resize_bilinear (-> ori_shape Ho x Wo; skipped when equal) -> softmax_nchw -> flip_planes -> acc = (accumulate ? acc : 0) + probs.
+ * src: [N][C][Hs][Ws] with batch stride src_bs (the 1/4 logits, or slide mode's input-size map with Hs x Ws = Hm x Wm); acc: dense
+ * [N][C][Ho][Wo].  C <= PFST_TTA_MAX_C (larger C: -1, the caller runs the chain). */
+#define PFST_TTA_MAX_C 32
+int pfst_tta_accumulate(const float* src, long long src_bs, int N, int C, int Hs, int Ws, int Hm, int Wm, int Ho, int Wo, int hflip, int vflip,
+                        float* acc, int accumulate, pfst_stream_t stream);
+/* seg_logit /= views, then seg_logit.argmax(dim=1) (:367-368) in one pass: labels equal to pfst_div_scalar + pfst_argmax_nchw's */
+int pfst_tta_finalize(const float* acc, int N, int C, int HW, int views, unsigned char* label_u8, pfst_stream_t stream);
 
 /* ---- fused bilinear-upsample + softmax cross-entropy + accuracy (decode_head.py:249-283,
  * cross_entropy_loss.py:45-65, accuracy.py:6-61).  logits are [N][C][h][w]; labels/weights [N][H][W].

@@ -423,6 +423,142 @@ __global__ void div_scalar_kernel(float* __restrict__ x, i64 n, float d) {      
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) x[i] = __fdiv_rn(x[i], d);
 }
 
+// ---- one view of aug_test (:355-372) in one pass: the view's probabilities at ori_shape, un-flipped, written or added into the sum.
+// The chain it replaces: resize_bilinear (1/4 logits -> input grid Hm x Wm), resize_bilinear (-> ori_shape Ho x Wo; skipped when equal),
+// softmax_nchw, flip_planes, axpy_.  Every value is formed with the same operations in the same order: the two resizes with bilin_src /
+// bilin_blend at the host's scales (the intermediate value of a tap is the fp32 value the first resize would have stored), the softmax with
+// softmax_nchw_kernel's max / sequential sum of expf / __fdiv_rn, the sum with axpy_kernel's fmaf(1, p, acc) -- bit-identical results.
+// A resize whose sizes are equal is skipped, as the host skips it.  src is small (1.5 MB at 1024^2, C = 6, L2-resident); the HBM traffic
+// is the read-modify-write of acc, PX = 4 pixels per thread with 16-byte accesses when HW % 4 == 0 (C <= 8; up to PFST_TTA_MAX_C classes
+// one pixel per thread, so that the CM values stay in registers).  grid: (cdiv(HW, PX * 256), N)
+struct TtaTap {          // one bilinear axis tap pair: source indices and weights
+  int i0, i1;
+  float l0, l1;
+};
+template <int CM, int PX>
+__global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __restrict__ src, i64 src_bs, int C, int Hs, int Ws, int Hm,
+                                                             int Wm, int Ho, int Wo, float sh1, float sw1, float sh2, float sw2, int skip1,
+                                                             int skip2, int hflip, int vflip, float* __restrict__ acc, int accumulate) {
+  const int n = blockIdx.y, HW = Ho * Wo;
+  const int p0 = (blockIdx.x * blockDim.x + threadIdx.x) * PX;
+  if (p0 >= HW) return;
+  const float* sp = src + (i64)n * src_bs;
+  const i64 plane_s = (i64)Hs * Ws;
+  float* ap = acc + (i64)n * C * HW;
+  float prob[PX][CM];
+#pragma unroll
+  for (int k = 0; k < PX; ++k) {
+    const int p = p0 + k;
+    if (p >= HW) break;
+    const int ay = p / Wo, ax = p - ay * Wo;
+    const int vy = vflip ? Ho - 1 - ay : ay, vx = hflip ? Wo - 1 - ax : ax;      // the view's pixel that lands on acc's (ay, ax)
+    // rows / columns of the intermediate grid the second resize reads (one each when it is skipped), and the source taps of each
+    TtaTap ry, rx, sy[2], sx[2];
+    if (skip2) {
+      ry = {vy, vy, 1.f, 0.f};
+      rx = {vx, vx, 1.f, 0.f};
+    } else {
+      bilin_src(vy, sh2, Hm, ry.i0, ry.i1, ry.l0, ry.l1);
+      bilin_src(vx, sw2, Wm, rx.i0, rx.i1, rx.l0, rx.l1);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int my = t ? ry.i1 : ry.i0, mx = t ? rx.i1 : rx.i0;
+      if (skip1) {
+        sy[t] = {my, my, 1.f, 0.f};
+        sx[t] = {mx, mx, 1.f, 0.f};
+      } else {
+        bilin_src(my, sh1, Hs, sy[t].i0, sy[t].i1, sy[t].l0, sy[t].l1);
+        bilin_src(mx, sw1, Ws, sx[t].i0, sx[t].i1, sx[t].l0, sx[t].l1);
+      }
+    }
+    auto mid = [&](const float* cp, int a, int b) {      // intermediate value at (row tap a, column tap b): the first resize's output
+      const TtaTap& y = sy[a];
+      const TtaTap& x = sx[b];
+      if (skip1) return cp[(i64)y.i0 * Ws + x.i0];
+      return bilin_blend(cp[(i64)y.i0 * Ws + x.i0], cp[(i64)y.i0 * Ws + x.i1], cp[(i64)y.i1 * Ws + x.i0], cp[(i64)y.i1 * Ws + x.i1], x.l0, x.l1,
+                         y.l0, y.l1);
+    };
+    float mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+      if (c < C) {
+        const float* cp = sp + (i64)c * plane_s;
+        const float v = skip2 ? mid(cp, 0, 0) : bilin_blend(mid(cp, 0, 0), mid(cp, 0, 1), mid(cp, 1, 0), mid(cp, 1, 1), rx.l0, rx.l1, ry.l0, ry.l1);
+        prob[k][c] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+      if (c < C) {
+        prob[k][c] = expf(prob[k][c] - mx);
+        se += prob[k][c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < C) prob[k][c] = __fdiv_rn(prob[k][c], se);
+  }
+  const bool vec = PX == 4 && (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(acc) & 15) == 0;   // p0 + 3 < HW and 16-byte aligned
+#pragma unroll
+  for (int c = 0; c < CM; ++c) {
+    if (c >= C) break;
+    float* cp = ap + (i64)c * HW + p0;
+    if constexpr (PX == 4) {
+      if (vec) {
+        float4 a;
+        if (accumulate) {
+          a = *reinterpret_cast<const float4*>(cp);
+          a.x = fmaf(1.f, prob[0][c], a.x); a.y = fmaf(1.f, prob[1][c], a.y); a.z = fmaf(1.f, prob[2][c], a.z); a.w = fmaf(1.f, prob[3][c], a.w);
+        } else {
+          a = make_float4(prob[0][c], prob[1][c], prob[2][c], prob[3][c]);
+        }
+        *reinterpret_cast<float4*>(cp) = a;
+        continue;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PX; ++k)
+      if (p0 + k < HW) cp[k] = accumulate ? fmaf(1.f, prob[k][c], cp[k]) : prob[k][c];
+  }
+}
+// seg_logit /= views (div_scalar_kernel's __fdiv_rn, BEFORE the comparison: ties made by the rounding resolve as in div + argmax), then the
+// first maximal class (argmax_nchw_kernel).  Only the labels are written.  Four pixels per thread, 16-byte loads when HW % 4 == 0.
+__global__ __launch_bounds__(256) void tta_finalize_kernel(const float* __restrict__ acc, int C, int HW, float views,
+                                                           unsigned char* __restrict__ lab) {
+  const int n = blockIdx.y;
+  const int p0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (p0 >= HW) return;
+  const float* ap = acc + (i64)n * C * HW + p0;
+  unsigned char* lp = lab + (i64)n * HW + p0;
+  if ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(acc) & 15) == 0 && (reinterpret_cast<uintptr_t>(lab) & 3) == 0) {
+    float4 best = *reinterpret_cast<const float4*>(ap);
+    best.x = __fdiv_rn(best.x, views); best.y = __fdiv_rn(best.y, views); best.z = __fdiv_rn(best.z, views); best.w = __fdiv_rn(best.w, views);
+    uchar4 arg = make_uchar4(0, 0, 0, 0);
+    for (int c = 1; c < C; ++c) {
+      const float4 v = *reinterpret_cast<const float4*>(ap + (i64)c * HW);
+      const float x = __fdiv_rn(v.x, views), y = __fdiv_rn(v.y, views), z = __fdiv_rn(v.z, views), w = __fdiv_rn(v.w, views);
+      if (x > best.x) { best.x = x; arg.x = (unsigned char)c; }
+      if (y > best.y) { best.y = y; arg.y = (unsigned char)c; }
+      if (z > best.z) { best.z = z; arg.z = (unsigned char)c; }
+      if (w > best.w) { best.w = w; arg.w = (unsigned char)c; }
+    }
+    *reinterpret_cast<uchar4*>(lp) = arg;
+    return;
+  }
+  for (int k = 0; k < 4 && p0 + k < HW; ++k) {
+    float best = __fdiv_rn(ap[k], views);
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = __fdiv_rn(ap[(i64)c * HW + k], views);
+      if (v > best) { best = v; arg = c; }
+    }
+    lp[k] = (unsigned char)arg;
+  }
+}
+
 // ---- integer-factor nearest up-sampling of small maps and its adjoint (F.interpolate(mode='nearest'),
 // pfgst_loss.py:57-58 when downscale == 1: features at 1/8 are resized to the 1/4 logits grid)
 __global__ void upsample_nearest_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w, int u) {
@@ -603,6 +739,29 @@ extern "C" int pfst_flip_planes(const float* x, float* y, int planes, int H, int
 extern "C" int pfst_div_scalar(float* x, long long n, float divisor, pfst_stream_t stream) {
   PFST_CHECK_ARG(x && n > 0 && divisor != 0.f);
   hipLaunchKernelGGL(div_scalar_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, (i64)n, divisor);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_tta_accumulate(const float* src, long long src_bs, int N, int C, int Hs, int Ws, int Hm, int Wm, int Ho, int Wo, int hflip,
+                                   int vflip, float* acc, int accumulate, pfst_stream_t stream) {
+  PFST_CHECK_ARG(src && acc && N > 0 && N <= 65535 && C > 0 && C <= PFST_TTA_MAX_C && Hs > 0 && Ws > 0 && Hm > 0 && Wm > 0 && Ho > 0 && Wo > 0);
+  PFST_CHECK_ARG(src_bs >= (i64)C * Hs * Ws && (i64)Ho * Wo <= 0x7ffffff0LL);
+  const int HW = Ho * Wo;
+  const bool skip1 = Hs == Hm && Ws == Wm, skip2 = Hm == Ho && Wm == Wo;
+  const float sh1 = (float)Hs / (float)Hm, sw1 = (float)Ws / (float)Wm, sh2 = (float)Hm / (float)Ho, sw2 = (float)Wm / (float)Wo;   // = resize_bilinear's
+  if (C <= 8)
+    hipLaunchKernelGGL((tta_accumulate_kernel<8, 4>), dim3(cdiv(cdiv(HW, 4), 256), N), dim3(256), 0, (hipStream_t)stream, src, (i64)src_bs, C, Hs, Ws, Hm, Wm, Ho, Wo, sh1, sw1,
+                       sh2, sw2, (int)skip1, (int)skip2, hflip ? 1 : 0, vflip ? 1 : 0, acc, accumulate ? 1 : 0);
+  else
+    hipLaunchKernelGGL((tta_accumulate_kernel<PFST_TTA_MAX_C, 1>), dim3(cdiv(HW, 256), N), dim3(256), 0, (hipStream_t)stream, src, (i64)src_bs, C, Hs, Ws, Hm, Wm, Ho, Wo,
+                       sh1, sw1, sh2, sw2, (int)skip1, (int)skip2, hflip ? 1 : 0, vflip ? 1 : 0, acc, accumulate ? 1 : 0);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+extern "C" int pfst_tta_finalize(const float* acc, int N, int C, int HW, int views, unsigned char* label_u8, pfst_stream_t stream) {
+  PFST_CHECK_ARG(acc && label_u8 && N > 0 && N <= 65535 && C > 0 && C <= 255 && HW > 0 && HW <= 0x7ffffff0 && views > 0);
+  hipLaunchKernelGGL(tta_finalize_kernel, dim3(cdiv(cdiv(HW, 4), 256), N), dim3(256), 0, (hipStream_t)stream, acc, C, HW, (float)views, label_u8);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }

@@ -85,6 +85,14 @@ class TileFolder:
         if not self.test_mode and self.ann_dir is not None:
             seg = _read_label(os.path.join(self.ann_dir, info['ann']['seg_map']))
         out = self.pipeline(img, seg)
+        if self.pipeline.tta is not None:
+            # a multi-view (MultiScaleFlipAug) item: a list of view tensors and a list of metas, in view order
+            item = {k: [torch.from_numpy(a) for a in v] for k, v in out.items() if isinstance(v[0], np.ndarray)}
+            item['img_metas'] = [dict(filename=info['filename'], ori_shape=img.shape, img_shape=tuple(out['img'][i].shape[1:]) + (3,),
+                                      img_norm_cfg=out['img_norm_cfg'][i], scale=out['scale'][i], flip=out['flip'][i],
+                                      flip_direction=out['flip_direction'][i], scale_index=out['scale_index'][i],
+                                      flip_permutes=out['flip_permutes'][i]) for i in range(len(out['img']))]
+            return item
         item = {k: torch.from_numpy(v) for k, v in out.items() if isinstance(v, np.ndarray)}
         item['img_metas'] = dict(filename=info['filename'], ori_shape=img.shape, img_shape=tuple(out['img'].shape[1:]) + (3,),
                                  img_norm_cfg=out['img_norm_cfg'])

@@ -77,11 +77,33 @@ def revise_checkpoint_keys(state_dict, revise_keys=((r'^module\.', ''), ('model.
     return out
 
 
+AUG_TEST_RATIOS = [0.5, 0.75, 1.0, 1.25, 1.5, 1.75]        # tools/test.py:156-161 of the reference (`--aug-test`)
+
+
+def enable_aug_test(pipeline, img_ratios=AUG_TEST_RATIOS, flip=True):
+    """`--aug-test` on a dataset pipeline list, in place: the MultiScaleFlipAug step (found by type, not at a fixed index) gets the ratios
+    and `flip`.  Its transforms get a RandomFlip right after the Resize when they have none -- the shipped configs carry it commented out, and
+    without it a `flip=True` view is the plain image whose prediction is then flipped back (mirrored) by `inference`.  -> the step"""
+    steps = [s for s in pipeline if s.get('type') == 'MultiScaleFlipAug']
+    if len(steps) != 1:
+        raise ValueError(f'--aug-test needs exactly one MultiScaleFlipAug step in the test pipeline, found {len(steps)}')
+    step = steps[0]
+    step['img_ratios'] = list(img_ratios)
+    step['flip'] = flip
+    tr = step['transforms'] = [dict(t) for t in step['transforms']]
+    if flip and not any(t.get('type') == 'RandomFlip' for t in tr):
+        at = next((i + 1 for i, t in enumerate(tr) if t.get('type') == 'Resize'), 0)
+        tr.insert(at, dict(type='RandomFlip'))
+    return step
+
+
 def build_eval_fn(val_cfg, num_classes, device, metric='mIoU', max_images=None):
     """The validation pass the reference's EvalHook / DistEvalHook run every `evaluation.interval` iterations
     (rsiseg/apis/train.py:152-168, core/evaluation/eval_hooks.py:12-58, apis/test.py single_gpu_test with pre_eval): whole-tile
     inference of the student with samples_per_gpu = 1, per-class area statistics summed over the images (ranks take every
-    world-th image and the statistics are all-reduced), then the metric table.  -> fn(model) -> {'aAcc', 'mIoU', 'mAcc', 'IoU.<c>'}"""
+    world-th image and the statistics are all-reduced), then the metric table.  A pipeline whose MultiScaleFlipAug makes several views
+    (test-time augmentation) is scored on the average of the views (EncoderDecoder.aug_test_labels).
+    -> fn(model) -> {'aAcc', 'mIoU', 'mAcc', 'IoU.<c>'}"""
     import torch.distributed as dist
     from .data import TileFolder
     dataset = TileFolder(val_cfg, test_mode=True)
@@ -101,7 +123,10 @@ def build_eval_fn(val_cfg, num_classes, device, metric='mIoU', max_images=None):
         n = len(dataset) if max_images is None else min(len(dataset), max_images)
         for i in range(rank, n, world):
             item = dataset[i]
-            pred8, _ = seg.inference(item['img'][None].to(device), [item['img_metas']], rescale=True)
+            if isinstance(item['img'], list):       # a MultiScaleFlipAug item: the views averaged (aug_test), batch 1 like the reference
+                pred8 = seg.aug_test_labels([v[None].to(device) for v in item['img']], [[m] for m in item['img_metas']], rescale=True)
+            else:
+                pred8, _ = seg.inference(item['img'][None].to(device), [item['img_metas']], rescale=True)
             gt = torch.from_numpy(dataset.gt_seg_map(i)).to(device)
             acc.update(pred8.reshape(gt.shape), gt)
         if hasattr(seg, '_last_states'):

@@ -976,6 +976,31 @@ def div_scalar_(x, d):
     return x
 
 
+TTA_MAX_C = 32          # PFST_TTA_MAX_C: classes held in registers by pfst_tta_accumulate
+
+
+def tta_accumulate_(acc, src, mid_hw, hflip=False, vflip=False, accumulate=True):
+    """acc (dense [N, C, Ho, Wo]) = (acc if accumulate else 0) + flip(softmax(resize(resize(src, mid_hw), (Ho, Wo)))), bit for bit what
+    resize_bilinear -> resize_bilinear -> softmax_nchw -> flip_planes -> axpy_ computes; a resize between equal sizes is skipped.
+    src: [N, C, Hs, Ws] (dense planes); C <= TTA_MAX_C"""
+    _dense(acc)
+    n, c, hs, ws = src.shape
+    assert acc.shape[:2] == (n, c), (tuple(acc.shape), tuple(src.shape))
+    ho, wo = acc.shape[2:]
+    call('pfst_tta_accumulate', src.data_ptr(), _bs(src), n, c, hs, ws, int(mid_hw[0]), int(mid_hw[1]), ho, wo, int(bool(hflip)),
+         int(bool(vflip)), acc.data_ptr(), int(bool(accumulate)), _stream())
+    return acc
+
+
+def tta_finalize(acc, views):
+    """(acc / views).argmax(dim=1) as uint8 [N, H, W]: labels equal to div_scalar_ + argmax_nchw's; acc is left as it is"""
+    _dense(acc)
+    n, c, h, w = acc.shape
+    lab = torch.empty(n, h, w, dtype=U8, device=acc.device)
+    call('pfst_tta_finalize', acc.data_ptr(), n, c, h * w, int(views), lab.data_ptr(), _stream())
+    return lab
+
+
 # ---------------------------------------------------------------- losses
 def ce_upsample_fwd(logits, label_u8, pix_weight=None, class_weight=None, ignore_index=255):
     """-> (lse [N,H,W], acc float64[4] = (weighted nll sum, #correct, #valid, #labels outside [0,C) that are not ignore_index))"""

@@ -588,16 +588,104 @@ class EncoderDecoder(nn.Module):
         self._last_states = None
         return list(lab8.cpu().numpy()), states
 
+    # ------------------------------------------------------------------ test-time augmentation (encoder_decoder.py:355-372)
+    @staticmethod
+    def _flip_axes(direction):
+        """(horizontal, vertical) un-flips of a view: `direction` None (not flipped) or its flip_direction (a name or a list of names,
+        each applied once per mention, as `inference` does)"""
+        if direction is None:
+            return False, False
+        d = direction if isinstance(direction, list) else [direction]
+        assert all(x in ('horizontal', 'vertical') for x in d), d
+        return d.count('horizontal') % 2 == 1, d.count('vertical') % 2 == 1
+
+    def _tta_forward(self, img):
+        """the forward of a batch of views -> (src, mid_hw): in whole mode the 1/4-resolution logits and the input size they are resized to
+        first (encode_decode); in slide mode the window average at the input size, whose one resize goes to ori_shape"""
+        mode = (self.test_cfg or {}).get('mode', 'whole')
+        assert mode in ('slide', 'whole')
+        hw = tuple(img.shape[2:])
+        if mode == 'slide':
+            return self.slide_inference(img, None, False), hw
+        with bn_eval():
+            x = self.extract_feat(img.contiguous(), None)
+            logits = self.decode_head(x, return_features=False, tape=None, training=False)
+        return logits.data, hw
+
+    @staticmethod
+    def _tta_add(acc, src, mid_hw, ori_hw, direction):
+        """acc (None: a new sum) += the view's probabilities at ori_shape, un-flipped: pfst_tta_accumulate, or for more than
+        ops.TTA_MAX_C classes the chain it fuses (resize, resize, softmax, flip, axpy) -- the same values either way"""
+        hflip, vflip = EncoderDecoder._flip_axes(direction)
+        n, c = src.shape[:2]
+        if c <= ops.TTA_MAX_C:
+            first = acc is None
+            if first:
+                acc = torch.empty(n, c, ori_hw[0], ori_hw[1], device=src.device)
+            return ops.tta_accumulate_(acc, src, mid_hw, hflip, vflip, accumulate=not first)
+        p = src if tuple(src.shape[2:]) == tuple(mid_hw) else ops.resize_bilinear(src, mid_hw)
+        if tuple(mid_hw) != tuple(ori_hw):
+            p = ops.resize_bilinear(p, ori_hw)
+        p = ops.softmax_nchw(p)
+        if hflip or vflip:
+            p = ops.flip_planes(p, horizontal=hflip, vertical=vflip)
+        if acc is None:
+            return p
+        ops.axpy_(acc, p)
+        return acc
+
+    def aug_test_scale_(self, img, img_meta, flips, acc=None):
+        """One scale of a test-time augmentation, the data path's entry (shared by aug_test).  `img` [1, 3, H, W] is the scale's plain view,
+        `flips` lists the scale's views in view order, each None (the plain view) or its flip_direction.  ONE forward at batch 1 + D: the view
+        and its D distinct flips, made on the device with flip_planes -- exact when the pipeline flips after Resize and the steps after the flip
+        are per pixel (Normalize), which the pipeline records as `flip_permutes` --, then each view's probabilities are added to `acc` in view
+        order (a duplicated view adds twice).  The f16x3 convolutions scale by the maximum over the batch, so the sum is within the tolerance
+        of per-view forwards, not bit-identical to them.  -> acc (None: a new sum) [1, C, *ori_shape]"""
+        assert img.shape[0] == 1, 'the paired-flip forward takes one image'
+        ori_hw = tuple(img_meta[0]['ori_shape'][:2])
+        keys = [self._flip_axes(d) for d in flips]
+        distinct = []
+        for k in keys:
+            if k != (False, False) and k not in distinct:
+                distinct.append(k)
+        batch = torch.cat([img] + [ops.flip_planes(img.contiguous(), horizontal=h, vertical=v) for h, v in distinct], 0) if distinct else img
+        src, mid_hw = self._tta_forward(batch)
+        for d, k in zip(flips, keys):
+            b = 0 if k == (False, False) else 1 + distinct.index(k)
+            acc = self._tta_add(acc, src[b:b + 1], mid_hw, ori_hw, d)
+        return acc
+
+    def aug_test_labels(self, imgs, img_metas, rescale=True):
+        """aug_test's prediction as a device tensor uint8 [N, *ori_shape].  The views are summed in the reference's order; a run of views of
+        one scale whose metas say `flip_permutes` (the pipeline flips after Resize) goes through aug_test_scale_, every other view through
+        its own forward.  The sum over views / len(imgs) and the arg-max are one pass (pfst_tta_finalize)."""
+        assert rescale
+        assert len(imgs) == len(img_metas) and len(imgs) > 0
+        ori = tuple(img_metas[0][0]['ori_shape'][:2])
+        assert all(tuple(m['ori_shape'][:2]) == ori for ms in img_metas for m in ms)
+        self.repack_weights(need_dgrad=False)
+        direction = lambda m: m['flip_direction'] if m.get('flip') else None
+        acc, i = None, 0
+        while i < len(imgs):
+            m = img_metas[i][0]
+            if imgs[i].shape[0] == 1 and m.get('flip_permutes') and not m.get('flip') and m.get('scale_index') is not None:
+                j = i + 1
+                while j < len(imgs) and img_metas[j][0].get('scale_index') == m['scale_index']:
+                    j += 1
+                acc = self.aug_test_scale_(imgs[i], img_metas[i], [direction(img_metas[v][0]) for v in range(i, j)], acc)
+                i = j
+                continue
+            src, mid_hw = self._tta_forward(imgs[i])
+            acc = self._tta_add(acc, src, mid_hw, ori, direction(m))
+            i += 1
+        return ops.tta_finalize(acc, len(imgs))
+
     def aug_test(self, imgs, img_metas, rescale=True):
         """Test with augmentations (encoder_decoder.py:355-372): the class probabilities of every augmented view, each mapped back to
-        `ori_shape` and un-flipped, are averaged; the arg-max of the average is the prediction.  Only rescale=True, like the reference."""
-        assert rescale
-        seg_logit, _ = self.inference_probs(imgs[0], img_metas[0], rescale)
-        for i in range(1, len(imgs)):
-            cur, _ = self.inference_probs(imgs[i], img_metas[i], rescale)
-            ops.axpy_(seg_logit, cur)
-        ops.div_scalar_(seg_logit, len(imgs))
-        return list(ops.argmax_nchw(seg_logit).cpu().numpy()), {}
+        `ori_shape` and un-flipped, are averaged; the arg-max of the average is the prediction.  Only rescale=True, like the reference.
+        Each view's resizes, softmax, un-flip and sum are one kernel (pfst_tta_accumulate, bit-identical to the separate passes); see
+        aug_test_labels for the paired-flip forward of pipeline items."""
+        return list(self.aug_test_labels(imgs, img_metas, rescale).cpu().numpy()), {}
 
     def forward_test(self, imgs, img_metas=None, **kwargs):
         """base.py:74-99: one view -> simple_test, several -> aug_test"""

@@ -6,7 +6,7 @@ Reference (all under rsiseg/datasets/pipelines): loading.py:100-163 (LoadAnnotat
 transforms.py:11-260 (Resize: ratio sampled with np.random.random_sample, keep-ratio rescale), :262-329 (RandomFlip),
 :331-402 (Pad), :404-451 (Normalize), :644-736 (RandomCrop + cat_max_ratio retries), :942-1059 (PhotoMetricDistortion),
 :1061-1160 (StrongAugmentation = the same distortion written to `img_strong_aug`), rsi_aug.py:29-108 (RandomRotate90),
-formating.py:189-217 (DefaultFormatBundle), test_time_aug.py (MultiScaleFlipAug with one scale, no flip).
+formating.py:189-217 (DefaultFormatBundle), test_time_aug.py (MultiScaleFlipAug: scales, ratios, flips).
 
 The random decisions use the global NumPy RNG with the reference's calls in the reference's order (np.random.random_sample for
 the scale ratio, np.random.randint for crop offsets, np.random.rand / np.random.choice for rotation and flips,
@@ -17,6 +17,8 @@ implements the same geometry (half-pixel centres, keep-ratio rounding of mmcv.re
 formulas in float arithmetic.
 
 Images travel as HxWx3 uint8 in BGR order like mmcv.imread, `Normalize(to_rgb=True)` swaps them; labels as HxW uint8."""
+import warnings
+
 import numpy as np
 
 IGNORE = 255
@@ -286,32 +288,48 @@ _KNOWN = {'LoadImageFromFile', 'LoadAnnotations', 'LoadAnnotationsPseudoLabelsV2
           'ImageToTensor', 'MultiScaleFlipAug', 'ClipNormalize', 'Uint82Float'}
 
 
+# steps of a MultiScaleFlipAug view after its RandomFlip that map every pixel on its own: the flipped view is then the plain view flipped
+_PER_PIXEL = {'Normalize', 'ClipNormalize', 'Uint82Float', 'ImageToTensor', 'Collect', 'DefaultFormatBundle'}
+
+
 class Pipeline:
     """steps: the reference's list of dict(type=..., **kw).  __call__(img_bgr_u8, seg_u8 | None) -> dict with float32 CHW arrays
-    `img` (+ `img_strong_aug`), uint8 `gt_semantic_seg` [1,H,W] and `img_norm_cfg`."""
+    `img` (+ `img_strong_aug`), uint8 `gt_semantic_seg` [1,H,W] and `img_norm_cfg`.
+
+    A MultiScaleFlipAug with ratios, several scales, flips or several flip directions (`self.tta`) makes several views: __call__ then
+    returns the reference's dict of lists (test_time_aug.py:118-126), one entry per view, with the keys above and `scale`, `flip`,
+    `flip_direction`, `scale_index` and `flip_permutes` (the flipped views of the scale are the plain view flipped, exactly)."""
 
     lazy_resize = True          # Resize followed by RandomCrop computes the crop window only (LazyResize); False: the eager order
 
     def __init__(self, steps):
         flat = []
+        self.tta = None
         for s in steps:
             s = dict(s)
             t = s.pop('type')
             if t not in _KNOWN:
                 raise NotImplementedError(f'pipeline step {t} is outside the PFST dataset configs')
-            if t == 'MultiScaleFlipAug':           # one scale, no flip (the shipped test pipelines): inline its transforms
-                if s.get('flip') or s.get('img_ratios') is not None:
-                    raise NotImplementedError('multi-scale / flip test-time augmentation is outside the PFST configs')
-                scale = s['img_scale']
-                for q in s['transforms']:
-                    q = dict(q)
-                    qt = q.pop('type')
-                    if qt == 'Resize':
-                        q.setdefault('img_scale', scale)
-                    flat.append((qt, q))
+            if self.tta is not None:
+                raise NotImplementedError(f'pipeline step {t} after a multi-view MultiScaleFlipAug')
+            if t == 'MultiScaleFlipAug':
+                tta = self._multi_scale_flip_aug(**s)
+                if tta is None:                    # one scale, no flip (the shipped test pipelines): inline its transforms
+                    scale = s['img_scale']
+                    for q in s['transforms']:
+                        q = dict(q)
+                        qt = q.pop('type')
+                        if qt == 'Resize':
+                            q.setdefault('img_scale', scale)
+                        flat.append((qt, q))
+                    continue
+                self.tta = tta
+                flat.append(('MultiScaleFlipAug', {}))
                 continue
             flat.append((t, s))
         self.steps = flat
+        if self.tta is not None:
+            flat = flat + self.tta['transforms']
         self.reduce_zero_label = any(k.get('reduce_zero_label') for t, k in flat if t.startswith('LoadAnnotations'))
         # LoadAnnotationsPseudoLabelsV2(pseudo_labels_dir=None) (loading.py:463-468, the shipped target pipelines): the target's label map is
         # all `ignore`.  It is never forwarded (uda_dataset.py:127-133) but RandomCrop(cat_max_ratio < 1) walks its ten retries on it, so the
@@ -333,14 +351,24 @@ class Pipeline:
         # LoadImageFromFile's default (loading.py:80-84): what the metas carry when the pipeline has no Normalize step (season_net)
         nch = 1 if img.ndim < 3 else img.shape[2]
         norm_cfg = dict(mean=[0.0] * nch, std=[1.0] * nch, to_rgb=False)
-        for t, k in self.steps:
+        if self.tta is None:
+            out, seg, norm_cfg = self._apply(self.steps, out, seg, blank, norm_cfg)
+            return self._finish(out, seg, norm_cfg)
+        return self._views(out, seg, blank, norm_cfg)
+
+    def _apply(self, steps, out, seg, blank, norm_cfg, view=None):
+        """run `steps` on out['img'] / seg; view: dict(scale, flip, flip_direction) of a MultiScaleFlipAug view"""
+        for t, k in steps:
             if isinstance(out['img'], LazyResize) and t not in ('RandomCrop', 'Resize', 'LoadImageFromFile', 'LoadAnnotations',
                                                                 'LoadAnnotationsPseudoLabelsV2'):
                 out['img'] = out['img'].materialize()          # a step other than the crop needs the pixels
             if t == 'Resize':
-                scale = k.get('img_scale')
-                scale = tuple(scale[0]) if isinstance(scale, (list, tuple)) and isinstance(scale[0], (list, tuple)) else tuple(scale)
-                if k.get('ratio_range') is not None:
+                if view is not None:                 # a MultiScaleFlipAug view: results['scale'] is used as it is (mmseg Resize)
+                    scale = tuple(view['scale'])
+                else:
+                    scale = k.get('img_scale')
+                    scale = tuple(scale[0]) if isinstance(scale, (list, tuple)) and isinstance(scale[0], (list, tuple)) else tuple(scale)
+                if view is None and k.get('ratio_range') is not None:
                     lo, hi = k['ratio_range']
                     ratio = np.random.random_sample() * (hi - lo) + lo
                     scale = (int(scale[0] * ratio), int(scale[1] * ratio))
@@ -381,6 +409,12 @@ class Pipeline:
                     out['img'] = np.rot90(out['img'], k=rot, axes=(0, 1)).copy()
                     if seg is not None:
                         seg = np.rot90(seg, k=rot, axes=(0, 1)).copy()
+            elif t == 'RandomFlip' and view is not None:      # a MultiScaleFlipAug view: results['flip'] / ['flip_direction'] decide, no draw
+                if view['flip']:
+                    ax = 1 if view['flip_direction'] == 'horizontal' else 0
+                    out['img'] = np.flip(out['img'], ax)
+                    if seg is not None:
+                        seg = np.flip(seg, ax).copy()
             elif t == 'RandomFlip':
                 p = k.get('prob', k.get('flip_ratio'))
                 if np.random.rand() < p:
@@ -419,10 +453,72 @@ class Pipeline:
                         out[key] = pad_to(out[key], k['size'], k.get('pad_val', 0))
                 if seg is not None:
                     seg = pad_to(seg, out['img'].shape[:2], k.get('seg_pad_val', IGNORE))
+        return out, seg, norm_cfg
+
+    def _finish(self, out, seg, norm_cfg):
         if isinstance(out['img'], LazyResize):
             out['img'] = out['img'].materialize()
         res = {key: np.ascontiguousarray(out[key].transpose(2, 0, 1), dtype=np.float32) for key in ('img', 'img_strong_aug') if key in out}
         if seg is not None:
             res['gt_semantic_seg'] = np.ascontiguousarray(seg, dtype=np.uint8)[None]
         res['img_norm_cfg'] = norm_cfg
+        return res
+
+    @staticmethod
+    def _multi_scale_flip_aug(transforms, img_scale, img_ratios=None, flip=False, flip_direction='horizontal'):
+        """test_time_aug.py:54-96 -> None for one scale without flips (its transforms are inlined), else the view plan"""
+        if img_ratios is not None:
+            img_ratios = img_ratios if isinstance(img_ratios, list) else [img_ratios]
+            if not all(isinstance(r, float) for r in img_ratios):
+                raise ValueError(f'MultiScaleFlipAug img_ratios must be floats, got {img_ratios}')
+        if isinstance(img_scale, list) and len(img_scale) == 2 and all(isinstance(v, (int, float)) for v in img_scale):
+            img_scale = tuple(img_scale)                   # a tuple that went through a list-only format
+        if img_scale is None:
+            if img_ratios is None:
+                raise ValueError('MultiScaleFlipAug with img_scale=None needs img_ratios')
+            scales = None                                  # mode 1: the image size times each ratio, per image (:104-107)
+        elif isinstance(img_scale, tuple) and img_ratios is not None:
+            scales = [(int(img_scale[0] * r), int(img_scale[1] * r)) for r in img_ratios]        # mode 2
+        else:
+            scales = [tuple(v) for v in img_scale] if isinstance(img_scale, list) else [tuple(img_scale)]     # mode 3
+        directions = flip_direction if isinstance(flip_direction, list) else [flip_direction]
+        steps = [(q['type'], {k: v for k, v in q.items() if k != 'type'}) for q in transforms]
+        types = [t for t, _ in steps]
+        for t in types:
+            if t not in _KNOWN:
+                raise NotImplementedError(f'pipeline step {t} is outside the PFST dataset configs')
+        if not flip and directions != ['horizontal']:
+            warnings.warn('flip_direction has no effect when flip is set to False')
+        if flip and 'RandomFlip' not in types:
+            warnings.warn('flip has no effect when RandomFlip is not in transforms')
+        if img_ratios is None and not flip and len(directions) == 1 and scales is not None and len(scales) == 1:
+            return None
+        # the flipped views are pure permutations of the plain view when the flip comes after the resize and only per-pixel steps follow it
+        permutes = False
+        if types.count('RandomFlip') == 1:
+            f = types.index('RandomFlip')
+            permutes = all(t != 'Resize' for t in types[f + 1:]) and all(t in _PER_PIXEL for t in types[f + 1:])
+        return dict(transforms=steps, scales=scales, ratios=img_ratios, flip_aug=[False, True] if flip else [False], directions=directions,
+                    flip_permutes=permutes)
+
+    def _views(self, out, seg, blank, norm_cfg):
+        """MultiScaleFlipAug.__call__ (test_time_aug.py:98-126): scale-major, then flip, then each flip direction -- with the reference's
+        multiplicity (flip=False and two directions: the plain view twice) -- each view through the transforms; a dict of lists"""
+        T = self.tta
+        out, seg, norm_cfg = self._apply(self.steps[:-1], out, seg, blank, norm_cfg)
+        if isinstance(out['img'], LazyResize):
+            out['img'] = out['img'].materialize()
+        scales = T['scales']
+        if scales is None:
+            h, w = out['img'].shape[:2]
+            scales = [(int(w * r), int(h * r)) for r in T['ratios']]
+        res = {}
+        for si, scale in enumerate(scales):
+            for flip in T['flip_aug']:
+                for d in T['directions']:
+                    view = dict(scale=scale, flip=flip, flip_direction=d)
+                    r = self._finish(*self._apply(T['transforms'], dict(out), seg, blank, norm_cfg, view))
+                    r.update(view, scale_index=si, flip_permutes=T['flip_permutes'])
+                    for key, v in r.items():
+                        res.setdefault(key, []).append(v)
         return res

@@ -5,7 +5,11 @@ PFST workflow uses: whole-tile inference of the SEGMENTOR (the student of a PFGS
   python tools/test.py CONFIG CHECKPOINT --eval mIoU --revise-checkpoint-key
 
 `--revise-checkpoint-key` strips the DDP `module.` prefix and the UDA wrapper's `model.` prefix exactly as the reference's
-`load_checkpoint(revise_keys=[(r'^module\\.', ''), ('model.', '')])` (tools/test.py:237-242)."""
+`load_checkpoint(revise_keys=[(r'^module\\.', ''), ('model.', '')])` (tools/test.py:237-242).
+
+`--aug-test` (tools/test.py:35,156-161) evaluates with multi-scale + flip test-time augmentation: the pipeline's MultiScaleFlipAug gets the
+ratios [0.5, 0.75, 1.0, 1.25, 1.5, 1.75] and flip=True (plus a RandomFlip after its Resize when the config has it commented out, see
+pfst_amd.evaluation.enable_aug_test), the prediction is the arg-max of the views' mean probabilities; --work-dir gets eval_multi_scale.json."""
 import argparse
 import json
 import os
@@ -19,6 +23,7 @@ def parse_args(argv=None):
     p.add_argument('config')
     p.add_argument('checkpoint')
     p.add_argument('--work-dir')
+    p.add_argument('--aug-test', action='store_true', help='multi-scale + flip test-time augmentation (the reference\'s six ratios)')
     p.add_argument('--eval', type=str, nargs='+', default=['mIoU'], help='mIoU / mDice / mFscore')
     p.add_argument('--split', default='test', choices=['test', 'val'])
     p.add_argument('--revise-checkpoint-key', action='store_true')
@@ -28,16 +33,25 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+def load_config(args):
+    """the config with --cfg-options merged and, with --aug-test, the test-time augmentation set on cfg.data[split]'s pipeline"""
+    from pfst_amd.config import Config, parse_cfg_options
+    from pfst_amd.evaluation import enable_aug_test
+    cfg = Config.fromfile(args.config)
+    if args.cfg_options:
+        cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
+    if args.aug_test:
+        enable_aug_test(cfg.data[args.split]['pipeline'])
+    return cfg
+
+
 def main(argv=None):
     args = parse_args(argv)
     import torch
     import pfst_amd  # noqa: F401
-    from pfst_amd.config import Config, parse_cfg_options
     from pfst_amd.evaluation import build_eval_fn, revise_checkpoint_keys
     from pfst_amd.registry import build_segmentor
-    cfg = Config.fromfile(args.config)
-    if args.cfg_options:
-        cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
+    cfg = load_config(args)
     torch.cuda.set_device(args.gpu_id)
     dev = torch.device('cuda', args.gpu_id)
     cfg.model['pretrained'] = None
@@ -59,8 +73,16 @@ def main(argv=None):
     print(json.dumps(res, indent=1))
     if args.work_dir:
         os.makedirs(args.work_dir, exist_ok=True)
-        with open(os.path.join(args.work_dir, 'eval.json'), 'w') as f:
-            json.dump(dict(config=args.config, checkpoint=args.checkpoint, metric=res), f, indent=1)
+        if args.aug_test:
+            from pfst_amd.pipeline import Pipeline
+            tta = Pipeline(cfg.data[args.split]['pipeline']).tta
+            views = len(tta['ratios']) * len(tta['flip_aug']) * len(tta['directions'])
+            with open(os.path.join(args.work_dir, 'eval_multi_scale.json'), 'w') as f:
+                json.dump(dict(config=args.config, checkpoint=args.checkpoint, img_ratios=tta['ratios'], flip=len(tta['flip_aug']) == 2,
+                               flip_direction=tta['directions'], views=views, metric=res), f, indent=1)
+        else:
+            with open(os.path.join(args.work_dir, 'eval.json'), 'w') as f:
+                json.dump(dict(config=args.config, checkpoint=args.checkpoint, metric=res), f, indent=1)
     return res
 
 
