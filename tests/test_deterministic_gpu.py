@@ -91,3 +91,62 @@ def test_log_values_read_before_the_backward_sweep_are_the_steps_log_values():
         assert list(la) == list(lb) and len(la) >= 14
         for k in la:
             assert abs(la[k] - lb[k]) <= 1e-12 * max(1.0, abs(la[k])), (k, la[k], lb[k])
+
+
+def _bench_shape_steps(overlap):
+    """deterministic mode at the bench shape (the flagship workload, b = 8 x 1024^2): two train steps from the same state -> per step the
+    log values, the gradient arena and the updated weights (host copies), and the arena layout"""
+    import pfst_amd  # noqa: F401
+    from pfst_amd import hip_ops, layers
+    from pfst_amd.optim import build_optimizer
+    from pfst_amd.presets import OPTIMIZER, workload_cfg
+    from pfst_amd.registry import UDA
+    from pfst_amd.synthetic import fill_state_dict, synth_batch
+    cfg, w = workload_cfg('pfst_pots_irrg2vaih_irrg_deeplabv3plus_r50-d8')
+    batch = synth_batch(w['per_gpu_batch'], w['size'], w['num_classes'], w['in_channels'], seed=1234, device='cuda')
+    layers.set_overlap(*overlap)
+    hip_ops.set_deterministic(True)
+    model = UDA.build(cfg)
+    fill_state_dict(model.state_dict(), 0)
+    model.cuda()
+    opt = build_optimizer(model, OPTIMIZER)
+    random.seed(0); np.random.seed(0); torch.manual_seed(0); torch.cuda.manual_seed_all(0)
+    steps = []
+    for _ in range(2):
+        lv = model.train_step(batch, opt)['log_vars']
+        torch.cuda.synchronize()
+        a = model.student_arena
+        steps.append((lv, a.grad.cpu(), a.data.cpu()))
+    layout = [(n, a.offsets[n], int(np.prod(a.shapes[n]))) for n in a.names]
+    del model, opt, batch, a
+    torch.cuda.empty_cache()
+    return steps, layout
+
+
+def test_stream_schedule_does_not_change_the_step_at_the_bench_shape():
+    """tests above at the bench shape (tools/det_repro_fullsize.py --runs 3 --last-single-stream as a test): in deterministic mode, two
+    train steps of b = 8 x 1024^2 give the SAME gradient arenas and updated weights, bit for bit, with the product's stream overlap on
+    (twice) and on one stream -- co-running kernels at the product's grid sizes must not change a single element"""
+    from pfst_amd import hip_ops, layers
+    prev_overlap = (layers.WGRAD_STREAM, layers.FORK_TEACHER)
+    assert not hip_ops.is_deterministic()
+    runs = []
+    try:
+        for overlap in ((True, True), (True, True), (False, False)):
+            runs.append(_bench_shape_steps(overlap))
+    finally:
+        hip_ops.set_deterministic(False)
+        layers.set_overlap(*prev_overlap)
+    (ref, layout), others = runs[0], runs[1:]
+    for r, (steps, _) in enumerate(others, 1):
+        for s in range(2):
+            (la, ga, wa), (lb, gb, wb) = ref[s], steps[s]
+            diff = [(n, int((ga[o:o + k] != gb[o:o + k]).sum()), float((ga[o:o + k] - gb[o:o + k]).norm() / ga[o:o + k].norm()))
+                    for n, o, k in layout if not torch.equal(ga[o:o + k], gb[o:o + k])]
+            assert not diff, f'run {r} ({"one stream" if r == 2 else "overlap"}) step {s}: {len(diff)} of {len(layout)} gradient tensors differ: {diff[:12]}'
+            wdiff = [n for n, o, k in layout if not torch.equal(wa[o:o + k], wb[o:o + k])]
+            assert not wdiff, f'run {r} step {s}: updated weights differ: {wdiff[:12]}'
+            assert list(la) == list(lb)
+            for k in la:
+                assert abs(la[k] - lb[k]) <= 1e-12 * max(1.0, abs(la[k])), (r, s, k, la[k], lb[k])
+    print(f'   3 runs x 2 steps at b = 8 x 1024^2: 0 of {len(layout)} gradient tensors differ')

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Deterministic mode at the bench shape (b = 8 x 1024^2, stream overlap on): the same first train step from the same state twice -- the gradient
-arenas must be bit-identical; lists the tensors that are not.  python tools/det_repro_fullsize.py [--runs 3]"""
+arenas must be bit-identical; lists the tensors that are not.  python tools/det_repro_fullsize.py [--runs 3]
+Backed by tests/test_deterministic_gpu.py::test_stream_schedule_does_not_change_the_step_at_the_bench_shape (--runs 3 --last-single-stream,
+two steps per run); this tool stays for listing the differing tensors of a single step."""
 import argparse
 import os
 import random
