@@ -122,38 +122,48 @@ def conv_out_size(hi, k, stride, dil, pad):
     return (hi + 2 * pad - (k - 1) * dil - 1) // stride + 1
 
 
+def _pack_outs(w, want_fprop, want_dgrad, out_f, out_d, shape_f, shape_d=None, dtype=F32):
+    """the (forward, data-gradient) images of a weight-packing call: None where the direction is not wanted, else the caller's buffer
+    (checked: an image of another size or type must not reach the kernel) or a fresh one"""
+    def image(want, out, shape):
+        if not want:
+            return None
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=w.device)
+        n = 1
+        for s in shape:
+            n *= s
+        assert _dense(out, dtype).numel() == n, (tuple(out.shape), shape)
+        return out
+    return image(want_fprop, out_f, shape_f), image(want_dgrad, out_d, shape_f if shape_d is None else shape_d)
+
+
 def pack_weight(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None):
     """w [Cout][Cin][k][k] -> K-major packings used by the implicit GEMM."""
     _dense(w)
     co, ci, kh, kw = w.shape
     assert kh == kw and kh in (1, 3)
-    wf = (out_f if out_f is not None else torch.empty(kh * kw * ci, co, device=w.device)) if want_fprop else None
-    wd = (out_d if out_d is not None else torch.empty(kh * kw * co, ci, device=w.device)) if want_dgrad else None
+    wf, wd = _pack_outs(w, want_fprop, want_dgrad, out_f, out_d, (kh * kw * ci, co), (kh * kw * co, ci))
     call('pfst_conv_pack_weight', w.data_ptr(), _p(wf), _p(wd), co, ci, kh * kw, _stream())
     return wf, wd
 
 
-_stats_cache = {}
+_scratch_cache = {}
 
 
-def _stats_ws(dev, nfloat):
-    """per-stream scratch for the conv epilogue's BN partials (consumed by bn_finalize_partials on the same stream)"""
-    key = (dev, torch.cuda.current_stream().cuda_stream)
-    t = _stats_cache.get(key)
-    if t is None or t.numel() < nfloat:
-        t = torch.empty(max(nfloat, 1 << 20), dtype=F32, device=dev)
-        _stats_cache[key] = t
+def _scratch(dev, tag, n, floor=0, dtype=F32):
+    """per-(device, stream, tag) scratch of at least n elements, consumed on the same stream: kept while it is large enough, else
+    replaced by one of max(n, floor) elements.  Tags: 'stats' the conv / depthwise / Winograd epilogues' BN partials (read by
+    bn_finalize_partials), ('multi', i) the same per branch of a multi-branch launch (all alive until their statistics are finalised),
+    'V' 'M' 'U' 'Pf' 'Pd' the transform-domain tensors, 'bn' the fp64 sums of the BatchNorm kernels"""
+    key = (dev, torch.cuda.current_stream().cuda_stream, tag)
+    t = _scratch_cache.get(key)
+    if t is None or t.numel() < n:
+        t = _scratch_cache[key] = torch.empty(max(n, floor), dtype=dtype, device=dev)
     return t
 
 
-def _stats_ws_multi(dev, nfloat, i):
-    """as _stats_ws, one scratch per branch of a multi-branch launch (all of them are alive until their statistics are finalised)"""
-    key = (dev, torch.cuda.current_stream().cuda_stream, 'multi', i)
-    t = _stats_cache.get(key)
-    if t is None or t.numel() < nfloat:
-        t = torch.empty(max(nfloat, 1 << 16), dtype=F32, device=dev)
-        _stats_cache[key] = t
-    return t
+_STATS_FLOOR = 1 << 20       # floats of a 'stats' scratch at least: every shape of the network fits, one allocation per stream
 
 
 def conv_stats_slots(n, cout, ho, wo):
@@ -190,27 +200,33 @@ def bnb_tile_rows(m):
     return 128 if m > 64 else (64 if m > 32 else 32)
 
 
-def conv_fprop(x, wk, cout, ksize, stride=1, dil=1, pad=0, bias=None, out=None, want_stats=False):
-    """want_stats: also return (stats_ws, slots), the epilogue's per-channel BN partial sums"""
+def _conv_fprop(entry, wbytes, x, wk, cout, ksize, stride, dil, pad, bias, out, want_stats, amax=(), minmax=None, bnl=None):
+    """the forward launch of the three implicit-GEMM families.  entry / wbytes: the C entry and what its K-major image holds per weight
+    (1 fp32, or 6 / 4 bytes of split pieces).  The f16x3 entry alone takes amax = (w_amax, x_amax) pointers in front of the bias, and,
+    behind the common arguments, the want_minmax flag (minmax: None marks the other entries) and the normalise-on-load rows"""
     n, c, hi, wi = x.shape
     ho, wo = conv_out_size(hi, ksize, stride, dil, pad), conv_out_size(wi, ksize, stride, dil, pad)
-    assert wk.numel() == ksize * ksize * c * cout, (wk.shape, c, cout, ksize)
+    assert wk.numel() == wbytes * ksize * ksize * c * cout, (wk.shape, c, cout, ksize)
     if out is None:
         out = torch.empty(n, cout, ho, wo, device=x.device)
-    assert tuple(out.shape) == (n, cout, ho, wo)
-    slots = conv_stats_slots(n, cout, ho, wo) if want_stats else 0
-    st = _stats_ws(x.device, 2 * cout * slots) if want_stats else None
-    call('pfst_conv_igemm', x.data_ptr(), _bs(x), _dense(wk).data_ptr(), _p(bias), out.data_ptr(), _bs(out),
-         n, c, hi, wi, cout, ho, wo, ksize, stride, dil, pad, 0, 0, _p(st), 0, _stream())
+    assert tuple(out.shape) == (n, cout, ho, wo)          # (the C side sees a pointer and a batch stride)
+    f16 = minmax is not None
+    slots, st = 0, None
+    if want_stats:
+        # f16x3: two pixel-waves per 128-pixel tile at every tile height
+        slots = n * ((ho * wo + 127) // 128) * 2 if f16 else conv_stats_slots(n, cout, ho, wo)
+        st = _scratch(x.device, 'stats', (4 if minmax else 2) * cout * slots, _STATS_FLOOR)
+    tail = (0, 0, 0, int(minmax), _p(None if bnl is None else _dense(bnl))) if f16 else ()
+    call(entry, x.data_ptr(), _bs(x), _dense(wk, F32 if wbytes == 1 else U8).data_ptr(), *amax, _p(bias), out.data_ptr(), _bs(out),
+         n, c, hi, wi, cout, ho, wo, ksize, stride, dil, pad, 0, 0, _p(st), 0, *tail, _stream())
     return (out, st, slots) if want_stats else out
 
 
-def conv_dgrad(dy, wk_d, cin, in_hw, ksize, stride=1, dil=1, pad=0, out=None, accumulate=False, bnb=None):
-    """bnb = (pre, y | None, coef, relu): `out` is the COMPLETE gradient of a conv -> BN layer's output and this launch also emits
-    that layer's BatchNorm-backward sums (pfst_bnb_fuse_t); returns (out, partials, slots) then."""
+def _conv_dgrad(entry, wbytes, dy, wk_d, cin, in_hw, ksize, stride, dil, pad, out, accumulate, bnb, amax=(), tail=()):
+    """the data-gradient launch of the three families (as _conv_fprop; tail: the f16x3 entry's gate and its unused forward arguments)"""
     n, co, ho, wo = dy.shape
     hi, wi = in_hw
-    assert wk_d.numel() == ksize * ksize * co * cin
+    assert wk_d.numel() == wbytes * ksize * ksize * co * cin
     if out is None:
         assert not accumulate
         out = torch.empty(n, cin, hi, wi, device=dy.device)
@@ -219,33 +235,33 @@ def conv_dgrad(dy, wk_d, cin, in_hw, ksize, stride=1, dil=1, pad=0, out=None, ac
     if bnb is not None:
         st, part, slots = _bnb_struct(bnb, n, cin, hi, wi, co, dy.device)
         fuse = ctypes.addressof(st)
-    call('pfst_conv_igemm', dy.data_ptr(), _bs(dy), _dense(wk_d).data_ptr(), 0, out.data_ptr(), _bs(out),
-         n, co, ho, wo, cin, hi, wi, ksize, stride, dil, pad, 1, int(accumulate), 0, fuse, _stream())
+    call(entry, dy.data_ptr(), _bs(dy), _dense(wk_d, F32 if wbytes == 1 else U8).data_ptr(), *amax, 0, out.data_ptr(), _bs(out),
+         n, co, ho, wo, cin, hi, wi, ksize, stride, dil, pad, 1, int(accumulate), 0, fuse, *tail, _stream())
     return (out, part, slots) if bnb is not None else out
+
+
+def conv_fprop(x, wk, cout, ksize, stride=1, dil=1, pad=0, bias=None, out=None, want_stats=False):
+    """want_stats: also return (stats_ws, slots), the epilogue's per-channel BN partial sums"""
+    return _conv_fprop('pfst_conv_igemm', 1, x, wk, cout, ksize, stride, dil, pad, bias, out, want_stats)
+
+
+def conv_dgrad(dy, wk_d, cin, in_hw, ksize, stride=1, dil=1, pad=0, out=None, accumulate=False, bnb=None):
+    """bnb = (pre, y | None, coef, relu): `out` is the COMPLETE gradient of a conv -> BN layer's output and this launch also emits
+    that layer's BatchNorm-backward sums (pfst_bnb_fuse_t); returns (out, partials, slots) then."""
+    return _conv_dgrad('pfst_conv_igemm', 1, dy, wk_d, cin, in_hw, ksize, stride, dil, pad, out, accumulate, bnb)
 
 
 def pack_weight_split(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None):
     """w [Cout][Cin][k][k] -> bf16x3-split K-major images (uint8 buffers of 6 bytes per weight)."""
     _dense(w)
     co, ci, kh, kw = w.shape
-    nbytes = 6 * co * ci * kh * kw
-    wf = (out_f if out_f is not None else torch.empty(nbytes, dtype=U8, device=w.device)) if want_fprop else None
-    wd = (out_d if out_d is not None else torch.empty(nbytes, dtype=U8, device=w.device)) if want_dgrad else None
+    wf, wd = _pack_outs(w, want_fprop, want_dgrad, out_f, out_d, (6 * co * ci * kh * kw,), dtype=U8)
     call('pfst_conv_pack_weight_split', w.data_ptr(), _p(wf), _p(wd), co, ci, kh * kw, _stream())
     return wf, wd
 
 
 def conv_fprop_split(x, wk6, cout, ksize, stride=1, dil=1, pad=0, bias=None, out=None, want_stats=False):
-    n, c, hi, wi = x.shape
-    ho, wo = conv_out_size(hi, ksize, stride, dil, pad), conv_out_size(wi, ksize, stride, dil, pad)
-    assert wk6.numel() == 6 * ksize * ksize * c * cout
-    if out is None:
-        out = torch.empty(n, cout, ho, wo, device=x.device)
-    slots = conv_stats_slots(n, cout, ho, wo) if want_stats else 0
-    st = _stats_ws(x.device, 2 * cout * slots) if want_stats else None
-    call('pfst_conv_igemm_split', x.data_ptr(), _bs(x), wk6.data_ptr(), _p(bias), out.data_ptr(), _bs(out),
-         n, c, hi, wi, cout, ho, wo, ksize, stride, dil, pad, 0, 0, _p(st), 0, _stream())
-    return (out, st, slots) if want_stats else out
+    return _conv_fprop('pfst_conv_igemm_split', 6, x, wk6, cout, ksize, stride, dil, pad, bias, out, want_stats)
 
 
 # ---------------------------------------------------------------- fp32-faithful two-piece fp16 split (csrc/conv_f16x3.hip)
@@ -312,9 +328,7 @@ def pack_weight_f16x2(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=Non
         assert w.dim() == 3 and w.shape[0] == sets
         _, co, ci = w.shape
         t = 1
-    nbytes = 4 * sets * co * ci * t
-    wf = (out_f if out_f is not None else torch.empty(nbytes, dtype=U8, device=w.device)) if want_fprop else None
-    wd = (out_d if out_d is not None else torch.empty(nbytes, dtype=U8, device=w.device)) if want_dgrad else None
+    wf, wd = _pack_outs(w, want_fprop, want_dgrad, out_f, out_d, (4 * sets * co * ci * t,), dtype=U8)
     if amax is None:
         amax = absmax(w, sets)
     call('pfst_conv_pack_weight_f16x2', w.data_ptr(), _p(wf), _p(wd), co, ci, t, sets, amax.data_ptr(), _stream())
@@ -361,19 +375,11 @@ def conv_fprop_f16x3(x, wk4, w_amax, x_amax, cout, ksize, stride=1, dil=1, pad=0
     the sums -- bn_finalize_partials(predict_amax=...) turns them into max |relu(bn(out))|.
     bnl: coef [C, 4] of the conv -> BN -> ReLU layer feeding this one: x is that layer's PRE-normalisation output, normalised between load and
     split (x_amax = the predicted max of the normalised tensor)"""
-    n, c, hi, wi = x.shape
+    c = x.shape[1]
     assert bnl is None or (tuple(bnl.shape) == (c, 4) and bias is None and conv_fprop_bnl_ok(c, cout, ksize, stride, pad))
-    ho, wo = conv_out_size(hi, ksize, stride, dil, pad), conv_out_size(wi, ksize, stride, dil, pad)
-    assert wk4.numel() == 4 * ksize * ksize * c * cout and f16x3_eligible(c, cout, ksize)
-    if out is None:
-        out = torch.empty(n, cout, ho, wo, device=x.device)
-    slots = n * ((ho * wo + 127) // 128) * 2 if want_stats else 0        # two pixel-waves per 128-pixel tile at every tile height
-    want_minmax = bool(want_minmax and want_stats and bias is None)
-    st = _stats_ws(x.device, (4 if want_minmax else 2) * cout * slots) if want_stats else None
-    call('pfst_conv_igemm_f16x3', x.data_ptr(), _bs(x), wk4.data_ptr(), w_amax.data_ptr(), x_amax.data_ptr(), _p(bias), out.data_ptr(), _bs(out),
-         n, c, hi, wi, cout, ho, wo, ksize, stride, dil, pad, 0, 0, _p(st), 0, 0, 0, 0, int(want_minmax), _p(None if bnl is None else _dense(bnl)),
-         _stream())
-    return (out, st, slots) if want_stats else out
+    assert f16x3_eligible(c, cout, ksize)
+    return _conv_fprop('pfst_conv_igemm_f16x3', 4, x, wk4, cout, ksize, stride, dil, pad, bias, out, want_stats,
+                       amax=(w_amax.data_ptr(), x_amax.data_ptr()), minmax=bool(want_minmax and want_stats and bias is None), bnl=bnl)
 
 
 def conv_wgrad_f16x3_(dw, x, dy, x_amax, dy_amax, bnl=None):
@@ -404,17 +410,9 @@ def conv_dgrad_f16x3(dy, wk4_d, w_amax, dy_amax, cin, in_hw, ksize, stride=1, di
         assert not accumulate and dgrad_gate_ok(cin, in_hw) and tuple(g.shape) == (n, cin, hi, wi)
         assert mask.dtype == torch.int64 and mask.numel() == n * cin * hi * wi // 64
         g_ptr, g_bs, m_ptr = g.data_ptr(), _bs(g), mask.data_ptr()
-    assert wk4_d.numel() == 4 * ksize * ksize * co * cin and f16x3_eligible(co, cin, ksize)
-    if out is None:
-        assert not accumulate
-        out = torch.empty(n, cin, hi, wi, device=dy.device)
-    fuse, part, slots, st = 0, None, 0, None
-    if bnb is not None:
-        st, part, slots = _bnb_struct(bnb, n, cin, hi, wi, co, dy.device)
-        fuse = ctypes.addressof(st)
-    call('pfst_conv_igemm_f16x3', dy.data_ptr(), _bs(dy), wk4_d.data_ptr(), w_amax.data_ptr(), dy_amax.data_ptr(), 0, out.data_ptr(), _bs(out),
-         n, co, ho, wo, cin, hi, wi, ksize, stride, dil, pad, 1, int(accumulate), 0, fuse, g_ptr, g_bs, m_ptr, 0, 0, _stream())
-    return (out, part, slots) if bnb is not None else out
+    assert f16x3_eligible(co, cin, ksize)
+    return _conv_dgrad('pfst_conv_igemm_f16x3', 4, dy, wk4_d, cin, in_hw, ksize, stride, dil, pad, out, accumulate, bnb,
+                       amax=(w_amax.data_ptr(), dy_amax.data_ptr()), tail=(g_ptr, g_bs, m_ptr, 0, 0))
 
 
 def _bnb_struct(bnb, n, cin, hi, wi, co, dev):
@@ -432,19 +430,7 @@ def _bnb_struct(bnb, n, cin, hi, wi, co, dev):
 
 def conv_dgrad_split(dy, wk6_d, cin, in_hw, ksize, stride=1, dil=1, pad=0, out=None, accumulate=False, bnb=None):
     """bnb: as conv_dgrad (returns (out, partials, slots) then)"""
-    n, co, ho, wo = dy.shape
-    hi, wi = in_hw
-    assert wk6_d.numel() == 6 * ksize * ksize * co * cin
-    if out is None:
-        assert not accumulate
-        out = torch.empty(n, cin, hi, wi, device=dy.device)
-    fuse, part, slots, st = 0, None, 0, None
-    if bnb is not None:
-        st, part, slots = _bnb_struct(bnb, n, cin, hi, wi, co, dy.device)
-        fuse = ctypes.addressof(st)
-    call('pfst_conv_igemm_split', dy.data_ptr(), _bs(dy), wk6_d.data_ptr(), 0, out.data_ptr(), _bs(out),
-         n, co, ho, wo, cin, hi, wi, ksize, stride, dil, pad, 1, int(accumulate), 0, fuse, _stream())
-    return (out, part, slots) if bnb is not None else out
+    return _conv_dgrad('pfst_conv_igemm_split', 6, dy, wk6_d, cin, in_hw, ksize, stride, dil, pad, out, accumulate, bnb)
 
 
 def conv_wgrad_(dw, x, dy, ksize, stride=1, dil=1, pad=0):
@@ -491,17 +477,7 @@ def bias_grad_(db, dy):
 
 
 # ---------------------------------------------------------------- Winograd F(2x2,3x3) (wide stride-1 3x3 convolutions)
-_wino_cache = {}
-
-
-def _wino_ws(dev, tag, nfloat):
-    """per-stream scratch for the transform-domain tensors (consumed on the same stream)"""
-    key = (dev, torch.cuda.current_stream().cuda_stream, tag)
-    t = _wino_cache.get(key)
-    if t is None or t.numel() < nfloat:
-        t = torch.empty(nfloat, dtype=F32, device=dev)
-        _wino_cache[key] = t
-    return t
+_wino_ws, _wino_cache = _scratch, _scratch_cache        # the transform-domain scratch (tags 'V' 'M' 'U' 'Pf' 'Pd', exact sizes) under its older names
 
 
 # output tile edge m of the Winograd F(m x m, 3x3) transforms: 4 (4x fewer MACs, 36 transform indices) or 2 (2.25x, 16 indices)
@@ -523,32 +499,36 @@ def wino_tiles(h, w, dil, m=None):
     return lib().pfst_wino_tiles(h, w, dil, _wino_m(m)[0])
 
 
-def wino_pack_weight(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None, m=None):
-    """w [Cout][Cin][3][3] -> transform-domain filters U[X][K/4][M][4], X = (m+2)^2, for fprop (K = Cin) and dgrad (K = Cout, flipped)."""
+def _wino_filter_dims(w, m):
     _dense(w)
     m, nx = _wino_m(m)
     co, ci, kh, kw = w.shape
     assert kh == 3 and kw == 3
-    uf = (out_f if out_f is not None else torch.empty(nx * co * ci, device=w.device)) if want_fprop else None
-    ud = (out_d if out_d is not None else torch.empty(nx * co * ci, device=w.device)) if want_dgrad else None
-    assert (uf is None or uf.numel() == nx * co * ci) and (ud is None or ud.numel() == nx * co * ci)
+    return m, nx, co, ci
+
+
+def wino_pack_weight(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None, m=None):
+    """w [Cout][Cin][3][3] -> transform-domain filters U[X][K/4][M][4], X = (m+2)^2, for fprop (K = Cin) and dgrad (K = Cout, flipped)."""
+    m, nx, co, ci = _wino_filter_dims(w, m)
+    uf, ud = _pack_outs(w, want_fprop, want_dgrad, out_f, out_d, (nx * co * ci,))
     call('pfst_wino_pack_weight', w.data_ptr(), _p(uf), _p(ud), co, ci, m, _stream())
     return uf, ud
 
 
+def _wino_filter_plain(w, want_fprop, want_dgrad, m):
+    """the plain fp32 transform-domain filter sets [X][Cout][Cin] (data gradient: [X][Cin][Cout], flipped) in per-stream scratch: what the
+    split packings of both arithmetics start from; -> (m, X, Cout, Cin, sets_f | None, sets_d | None)"""
+    m, nx, co, ci = _wino_filter_dims(w, m)
+    pf = _scratch(w.device, 'Pf', nx * co * ci) if want_fprop else None
+    pd = _scratch(w.device, 'Pd', nx * co * ci) if want_dgrad else None
+    call('pfst_wino_filter_plain', w.data_ptr(), _p(pf), _p(pd), co, ci, m, _stream())
+    return m, nx, co, ci, pf, pd
+
+
 def wino_pack_weight_split(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None, m=None):
     """transform-domain filters for the bf16x6 GEMM: X split-packed sets (uint8 buffers of X * 6 * Cout * Cin bytes)"""
-    _dense(w)
-    m, nx = _wino_m(m)
-    co, ci, kh, kw = w.shape
-    assert kh == 3 and kw == 3
-    n = co * ci
-    pf = _wino_ws(w.device, 'Pf', nx * n) if want_fprop else None
-    pd = _wino_ws(w.device, 'Pd', nx * n) if want_dgrad else None
-    call('pfst_wino_filter_plain', w.data_ptr(), _p(pf), _p(pd), co, ci, m, _stream())
-    uf = (out_f if out_f is not None else torch.empty(nx * 6 * n, dtype=U8, device=w.device)) if want_fprop else None
-    ud = (out_d if out_d is not None else torch.empty(nx * 6 * n, dtype=U8, device=w.device)) if want_dgrad else None
-    assert (uf is None or uf.numel() == nx * 6 * n) and (ud is None or ud.numel() == nx * 6 * n)
+    m, nx, co, ci, pf, pd = _wino_filter_plain(w, want_fprop, want_dgrad, m)
+    uf, ud = _pack_outs(w, want_fprop, want_dgrad, out_f, out_d, (nx * 6 * co * ci,), dtype=U8)
     call('pfst_wino_pack_weight_split', _p(pf), _p(pd), _p(uf), _p(ud), co, ci, m, _stream())
     return uf, ud
 
@@ -556,19 +536,12 @@ def wino_pack_weight_split(w, want_fprop=True, want_dgrad=True, out_f=None, out_
 def wino_pack_weight_f16(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None, m=None):
     """transform-domain filters for the f16x3 GEMM: X two-piece fp16 sets (uint8 buffers of X * 4 * Cout * Cin bytes) + the X slots with
     each set's absolute maximum; -> (uf, ud, amax_f, amax_d)"""
-    _dense(w)
-    m, nx = _wino_m(m)
-    co, ci, kh, kw = w.shape
-    assert kh == 3 and kw == 3
-    n = co * ci
-    pf = _wino_ws(w.device, 'Pf', nx * n) if want_fprop else None
-    pd = _wino_ws(w.device, 'Pd', nx * n) if want_dgrad else None
-    call('pfst_wino_filter_plain', w.data_ptr(), _p(pf), _p(pd), co, ci, m, _stream())
+    m, nx, co, ci, pf, pd = _wino_filter_plain(w, want_fprop, want_dgrad, m)
     uf = ud = af = ad = None
     if want_fprop:
-        uf, _, af = pack_weight_f16x2(pf[:nx * n].view(nx, co, ci), True, False, out_f=out_f, sets=nx)
+        uf, _, af = pack_weight_f16x2(pf[:nx * co * ci].view(nx, co, ci), True, False, out_f=out_f, sets=nx)
     if want_dgrad:
-        _, ud, ad = pack_weight_f16x2(pd[:nx * n].view(nx, co, ci), False, True, out_d=out_d, sets=nx)
+        _, ud, ad = pack_weight_f16x2(pd[:nx * co * ci].view(nx, co, ci), False, True, out_d=out_d, sets=nx)
     return uf, ud, af, ad
 
 
@@ -584,8 +557,8 @@ def wino_conv(x, u, cout, dil, out=None, accumulate=False, keep_v=False, want_st
     m, nx = _wino_m(m)
     t = wino_tiles(h, w, dil, m)
     assert u.numel() == nx * c * cout * ((4 if u_amax is not None else 6) if u.dtype == U8 else 1), 'filter set was packed for another tile size'
-    v = torch.empty(nx * n * c * t, dtype=F32, device=x.device) if keep_v else _wino_ws(x.device, 'V', nx * n * c * t)
-    mb = _wino_ws(x.device, 'M', nx * n * cout * t)
+    v = torch.empty(nx * n * c * t, dtype=F32, device=x.device) if keep_v else _scratch(x.device, 'V', nx * n * c * t)
+    mb = _scratch(x.device, 'M', nx * n * cout * t)
     if out is None:
         assert not accumulate
         out = torch.empty(n, cout, h, w, device=x.device)
@@ -605,7 +578,7 @@ def wino_conv(x, u, cout, dil, out=None, accumulate=False, keep_v=False, want_st
     slots, st = 0, None
     if want_stats:                      # BN partial sums of the output come out of the output transform
         slots = n * lib().pfst_wino_stats_slots(h, w, dil, m)
-        st = _stats_ws(x.device, (4 if want_minmax else 2) * cout * slots)
+        st = _scratch(x.device, 'stats', (4 if want_minmax else 2) * cout * slots, _STATS_FLOOR)
     bx, bx_bs, bcoef, brelu = 0, 0, 0, 0
     if bnb is not None:
         # a data-gradient launch that completes the gradient of a conv -> BN [-> ReLU] layer's output (no residual): bnb = (pre, coef, relu) of
@@ -632,15 +605,15 @@ def wino_wgrad_(dw, x, dy, dil, v=None, m=None, split=False, v_amax=None, x_amax
     m, nx = _wino_m(m)
     assert dy.shape == (n, co, h, w) and dw.numel() == co * ci * 9
     t = wino_tiles(h, w, dil, m)
-    dm = _wino_ws(x.device, 'M', nx * n * co * t)
-    du = _wino_ws(x.device, 'U', nx * co * ci)
+    dm = _scratch(x.device, 'M', nx * n * co * t)
+    du = _scratch(x.device, 'U', nx * co * ci)
     # split: False / 0 fp32-input MFMA, True / 1 bf16x6, 2 f16x3 (falls back to bf16x6 for <= 64 rows).  f16x3: both operands PRE-SPLIT by
     # their transforms (v given: the packed V and its bound group kept from the f16x3 forward pass)
     f16 = split == 2 and co > 64
     assert not (f16 and v is not None and v_amax is None), 'a kept V must come with the slot group of its scale bound'
     assert f16 or v_amax is None, 'a packed V kept from an f16x3 forward pass needs the f16x3 weight gradient'
     if v is None:
-        v = _wino_ws(x.device, 'V', nx * n * ci * t)
+        v = _scratch(x.device, 'V', nx * n * ci * t)
         v_amax = amax_slots(x.device) if f16 else None
         if f16 and x_amax is None:
             x_amax = absmax(x)
@@ -668,7 +641,7 @@ def dwconv(x, w, dil, flip=False, out=None, accumulate=False, want_stats=False, 
     slots, st = 0, None
     if want_stats:
         slots = n * lib().pfst_dwconv_stats_slots(h, wd, dil)
-        st = _stats_ws(x.device, (4 if want_minmax else 2) * c * slots)
+        st = _scratch(x.device, 'stats', (4 if want_minmax else 2) * c * slots, _STATS_FLOOR)
     call('pfst_dwconv3x3', x.data_ptr(), _bs(x), _dense(w).data_ptr(), out.data_ptr(), _bs(out), n, c, h, wd, dil,
          int(flip), int(accumulate), _p(st), int(bool(want_minmax and want_stats)), _p(bnl), _stream())
     return (out, st, slots) if want_stats else out
@@ -703,7 +676,7 @@ def dwconv_multi(x, ws, dils, want_stats=False, want_mean=False, want_minmax=Fal
     k = len(ws)
     ys = [torch.empty(n, c, h, w, device=x.device) for _ in range(k)]
     want_minmax = bool(want_minmax and want_stats)          # the (minimum, maximum) partials behind each branch's sums
-    sts = [(_stats_ws_multi(x.device, (4 if want_minmax else 2) * c * n, i) if want_stats else None) for i in range(k)]
+    sts = [(_scratch(x.device, ('multi', i), (4 if want_minmax else 2) * c * n, 1 << 16) if want_stats else None) for i in range(k)]
     mean = torch.empty(n, c, 1, 1, device=x.device) if want_mean else None
     call('pfst_dwconv3x3_multi_fwd', x.data_ptr(), _bs(x), k, _ptr_array([_dense(t) for t in ws]), _ptr_array(ys),
          (ctypes.c_longlong * k)(*[_bs(y) for y in ys]), _ptr_array(sts), int(want_minmax), (ctypes.c_int * k)(*dils), _p(mean), n, c, h, w,
@@ -741,25 +714,13 @@ def dwconv_bwd_(dw, x, dy, w, dil, dx, accumulate=False, bnl=None, bnb=None):
 
 
 # ---------------------------------------------------------------- batch norm
-_ws_cache = {}
-
-
-def _ws(dev, nbytes=2 * 8 * 4096):
-    key = (dev, torch.cuda.current_stream().cuda_stream)
-    t = _ws_cache.get(key)
-    if t is None or t.numel() * 8 < nbytes:
-        t = torch.empty(max(nbytes // 8, 8192), dtype=F64, device=dev)
-        _ws_cache[key] = t
-    return t
-
-
 def bn_stats(x, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, gamma=None, beta=None):
     n, c, h, w = x.shape
     mean = torch.empty(c, device=x.device)
     invstd = torch.empty(c, device=x.device)
     coef = torch.empty(c, 4, device=x.device) if gamma is not None else None
     call('pfst_bn_stats', x.data_ptr(), _bs(x), n, c, h * w, mean.data_ptr(), invstd.data_ptr(), _p(running_mean),
-         _p(running_var), float(momentum), float(eps), _ws(x.device, 16 * c).data_ptr(), _p(gamma), _p(beta), _p(coef), _stream())
+         _p(running_var), float(momentum), float(eps), _scratch(x.device, 'bn', 2 * c, 8192, F64).data_ptr(), _p(gamma), _p(beta), _p(coef), _stream())
     return (mean, invstd, coef) if gamma is not None else (mean, invstd)
 
 
@@ -795,7 +756,7 @@ def bn_backward(dy, y, x, mean, invstd, gamma, dgamma, dbeta, relu=True, dres=No
     call('pfst_bn_backward', dy.data_ptr(), _bs(dy), _p(y), 0 if y is None else _bs(y), x.data_ptr(), _bs(x),
          mean.data_ptr(), invstd.data_ptr(), _dense(gamma).data_ptr(), _p(beta), dx.data_ptr(), _bs(dx),
          _p(dres), 0 if dres is None else _bs(dres), int(dres_accumulate), _p(dgamma), _p(dbeta),
-         n, c, h * w, int(relu), _p(mask), _ws(x.device, 16 * c).data_ptr(), _p(partials), int(slots), _p(amax), _p(None if post is None else _dense(post)), _stream())
+         n, c, h * w, int(relu), _p(mask), _scratch(x.device, 'bn', 2 * c, 8192, F64).data_ptr(), _p(partials), int(slots), _p(amax), _p(None if post is None else _dense(post)), _stream())
     return dx
 
 

@@ -4,6 +4,7 @@
 Naming mirrors mmcv's ConvModule / DepthwiseSeparableConvModule (`.conv`, `.bn`, `.depthwise_conv`,
 `.pointwise_conv`) because checkpoints key on it (SURVEY.md §8b "Checkpoint layout")."""
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -120,6 +121,22 @@ class bn_eval:
         _BN_EVAL = self.prev
 
 
+class ConvPlan(NamedTuple):
+    """what Conv2dP.plan decides: the kernel family per direction (forward / data gradient) and the weight images to pack for them"""
+    wino: bool = False          # forward and data gradient through the Winograd domain ...
+    wino_f16: bool = False      # ... with the f16x3 transform-domain GEMM (else bf16x6 / fp32 by CONV_MATH)
+    f16_f: bool = False         # direct forward on the f16x3 kernel
+    f16_d: bool = False         # direct data gradient on the f16x3 kernel
+    split_f: bool = False       # ... on the bf16x6 kernel
+    split_d: bool = False
+    fp32_f: bool = False        # ... on the fp32-input MFMA kernel: the plain K-major image is needed
+    fp32_d: bool = False
+
+
+# Conv2dP.wgrad_route answers that scale both operands from slot groups with their absolute maxima (the f16x3 kernels)
+WGRAD_READS_AMAX = ('wino_f16x3', 'line_f16x3', 'quad_f16x3')
+
+
 class Conv2dP(nn.Module):
     """Weights of an nn.Conv2d (+ K-major packings for the implicit GEMM)."""
 
@@ -155,6 +172,17 @@ class Conv2dP(nn.Module):
     def wino_wgrad_ok(self, h, w):
         return self.wino and self.cin * self.cout >= WINO_MIN_CC_WGRAD and ops.wino_tiles(h, w, self.dilation) % 4 == 0
 
+    @property
+    def fprop_reads_amax(self):
+        """this layer's forward pass scales its input from a published maximum (the f16x3 GEMM, direct or in the Winograd domain): the caller
+        hands fprop the slot group (amax_of), and the same two kernels are the ones that can emit (min, max) partials of their output"""
+        return self.f16_f or self.wino_f16
+
+    @property
+    def dgrad_reads_amax(self):
+        """the same for the data gradient and max |dy|"""
+        return self.f16_d or self.wino_f16
+
     def fprop(self, xd, out=None, bias=None, want_stats=False, keep=False, x_amax=None, bnl=None, want_minmax=False):
         """keep: training forward -- the Winograd path keeps its transformed input for the weight gradient (self.saved_v);
         x_amax: the slot with max |xd| when the caller has it (f16x3 layers; computed here otherwise);
@@ -173,15 +201,14 @@ class Conv2dP(nn.Module):
             return res                                     # (y, stats, slots) with want_stats, else y
         assert bnl is None or (self.fprop_bnl_ok() and bias is None and x_amax is not None), \
             'only the Winograd input transform, the 256-row 1x1 f16x3 GEMM (and the depthwise / max-pool kernels) normalise on load'
+        geom = (self.cout, self.k, self.stride, self.dilation, self.padding)
+        kw = dict(bias=bias, out=out, want_stats=want_stats)
         if self.f16_f:
-            return ops.conv_fprop_f16x3(xd, self.w4f, self.w_amax, x_amax if x_amax is not None else ops.absmax(xd), self.cout, self.k,
-                                        self.stride, self.dilation, self.padding, bias=bias, out=out, want_stats=want_stats,
-                                        want_minmax=want_minmax, bnl=bnl)
+            return ops.conv_fprop_f16x3(xd, self.w4f, self.w_amax, x_amax if x_amax is not None else ops.absmax(xd), *geom,
+                                        want_minmax=want_minmax, bnl=bnl, **kw)
         if self.split_f:
-            return ops.conv_fprop_split(xd, self.w6f, self.cout, self.k, self.stride, self.dilation, self.padding, bias=bias, out=out,
-                                        want_stats=want_stats)
-        return ops.conv_fprop(xd, self.wf, self.cout, self.k, self.stride, self.dilation, self.padding, bias=bias, out=out,
-                              want_stats=want_stats)
+            return ops.conv_fprop_split(xd, self.w6f, *geom, **kw)
+        return ops.conv_fprop(xd, self.wf, *geom, **kw)
 
     def fprop_bnl_ok(self):
         """the forward GEMM can normalise its input as it loads it (ops.conv_fprop_f16x3(bnl=...)) and the weight gradient likewise
@@ -213,48 +240,95 @@ class Conv2dP(nn.Module):
         """the data-gradient launch can add a ReLU-gated tensor in its epilogue (ops.conv_dgrad_f16x3(gate=...))"""
         return FUSE_RES_GATE and self.f16_d and not self.wino and not self.depthwise and ops.dgrad_gate_ok(self.cin, in_hw)
 
+    def wgrad_route(self, h, w, xd=None, dy=None, lazy=False):
+        """which kernel computes this layer's weight gradient for an input of h x w -- the ONE statement of that choice: _wgrad launches
+        from it, conv_backward and conv_bn_act learn from it whether the kernel scales x / dy from published maxima (WGRAD_READS_AMAX).
+        xd, dy: the operands where the caller has them (the K-quad f16x3 kernel wants aligned planes: ops.wgrad_q_operands_ok; a caller that
+        asks before dy exists gets the answer for aligned ones); lazy: the input is a pre-normalisation tensor to be normalised on load"""
+        split = _split_mode()
+        f16 = CONV_MATH == 'f16x3' and self.cout > 64
+        line = self.k == 1 and self.stride == 1 and (h * w) % 4 == 0        # the whole-line 1x1 kernels read float4s of a plane
+        if self.wino_wgrad_ok(h, w):
+            # the f16x3 Winograd-domain weight gradient pairs with the f16x3 forward pass: only a `wino_f16` layer keeps a PACKED V with
+            # the slot group of its scale bound.  A Winograd layer outside the f16x3 GEMM's shapes (3x3 64 -> 256, 48 -> 512: Cin not a
+            # multiple of 32, or a data gradient the kernel does not cover) kept a plain fp32 V and takes the bf16x6 product (ADVICE r3)
+            return 'wino_f16x3' if (f16 and self.wino_f16) else ('wino_bf16x6' if split else 'wino_f32')
+        if f16 and line:
+            return 'line_f16x3'
+        if lazy:
+            raise RuntimeError('a normalise-on-load input reached a weight-gradient kernel that reads the tensor as stored')
+        if self.wgrad_f16q_ok(h, w) and (xd is None or ops.wgrad_q_operands_ok(xd, dy)):
+            return 'quad_f16x3'
+        if split and line:
+            return 'quad_bf16x6'
+        return 'generic'
+
     def dgrad(self, dy, in_hw, out, accumulate, bn=None, dy_amax=None, gate=None):
         """bn: BnBackwardCtx of the layer that produced this conv's input, when this launch completes that gradient;
         dy_amax: slot group with max |dy| (f16x3 layers; computed here when the producer did not publish it);
         gate: (g, mask) added where the mask has the bit (Var.pending of a residual block's input; only where dgrad_can_gate)"""
         assert gate is None or (self.f16_d and not self.wino and not accumulate)
+        kw = dict(out=out, accumulate=accumulate)
         if self.wino:
             if bn is not None:           # the output transform emits the BatchNorm-backward sums of the layer that owns `out` (no residual there)
                 assert bn.y is None
-                _, bn.partials, bn.slots = ops.wino_conv(dy, self.ud, self.cin, self.dilation, out=out, accumulate=accumulate,
-                                                         u_amax=self.ud_amax if self.wino_f16 else None,
-                                                         x_amax=dy_amax if self.wino_f16 else None, bnb=(bn.pre, bn.coef, bn.relu))
-                return out
-            return ops.wino_conv(dy, self.ud, self.cin, self.dilation, out=out, accumulate=accumulate,
-                                 u_amax=self.ud_amax if self.wino_f16 else None, x_amax=dy_amax if self.wino_f16 else None)
-        if self.f16_d:
-            amax = dy_amax if dy_amax is not None else ops.absmax(dy)
-            if bn is not None:
-                _, bn.partials, bn.slots = ops.conv_dgrad_f16x3(dy, self.w4d, self.w_amax, amax, self.cin, in_hw, self.k, self.stride,
-                                                                self.dilation, self.padding, out=out, accumulate=accumulate,
-                                                                bnb=(bn.pre, bn.y, bn.coef, bn.relu, bn.mask), gate=gate)
-                return out
-            return ops.conv_dgrad_f16x3(dy, self.w4d, self.w_amax, amax, self.cin, in_hw, self.k, self.stride, self.dilation,
-                                        self.padding, out=out, accumulate=accumulate, gate=gate)
-        if self.split_d:
-            if bn is not None:
-                _, bn.partials, bn.slots = ops.conv_dgrad_split(dy, self.w6d, self.cin, in_hw, self.k, self.stride, self.dilation,
-                                                                self.padding, out=out, accumulate=accumulate,
-                                                                bnb=(bn.pre, bn.y, bn.coef, bn.relu))
-                return out
-            return ops.conv_dgrad_split(dy, self.w6d, self.cin, in_hw, self.k, self.stride, self.dilation, self.padding,
-                                        out=out, accumulate=accumulate)
-        if bn is not None:
-            _, bn.partials, bn.slots = ops.conv_dgrad(dy, self.wd, self.cin, in_hw, self.k, self.stride, self.dilation, self.padding,
-                                                      out=out, accumulate=accumulate, bnb=(bn.pre, bn.y, bn.coef, bn.relu))
-            return out
-        return ops.conv_dgrad(dy, self.wd, self.cin, in_hw, self.k, self.stride, self.dilation, self.padding,
-                              out=out, accumulate=accumulate)
+                kw['bnb'] = (bn.pre, bn.coef, bn.relu)
+            res = ops.wino_conv(dy, self.ud, self.cin, self.dilation, u_amax=self.ud_amax if self.wino_f16 else None,
+                                x_amax=dy_amax if self.wino_f16 else None, **kw)
+        else:
+            if bn is not None:           # (bn_apply's bitmask of y as the gate: a variant of the f16x3 epilogue only)
+                kw['bnb'] = (bn.pre, bn.y, bn.coef, bn.relu, bn.mask if self.f16_d else None)
+            geom = (self.cin, in_hw, self.k, self.stride, self.dilation, self.padding)
+            if self.f16_d:
+                res = ops.conv_dgrad_f16x3(dy, self.w4d, self.w_amax, dy_amax if dy_amax is not None else ops.absmax(dy), *geom, gate=gate, **kw)
+            elif self.split_d:
+                res = ops.conv_dgrad_split(dy, self.w6d, *geom, **kw)
+            else:
+                res = ops.conv_dgrad(dy, self.wd, *geom, **kw)
+        if bn is None:
+            return res
+        _, bn.partials, bn.slots = res
+        return out
+
+    def plan(self, need_dgrad):
+        """the kernel family of each direction of this layer and the weight images they read, from (CONV_MATH, the WINOGRAD / WINO_MIN_CC
+        switches, need_dgrad, the layer's own shape) and nothing else: no allocation, no launch, any device"""
+        if self.depthwise:
+            return ConvPlan()
+        f16, split = CONV_MATH == 'f16x3', _split_mode()
+        wino = self._wino_eligible()
+        # (the transform-domain GEMMs have no 64-row tile: more than 64 rows in both directions)
+        wino_f16 = (wino and f16 and ops.f16x3_eligible(self.cin, self.cout) and self.cout > 64
+                    and (not need_dgrad or (ops.f16x3_eligible(self.cout, self.cin) and self.cin > 64)))
+        if wino and self.bias is None:
+            return ConvPlan(wino=True, wino_f16=wino_f16)        # the direct-convolution packings are not needed
+        f16_f = f16 and ops.f16x3_eligible(self.cin, self.cout, self.k)
+        f16_d = f16 and need_dgrad and ops.f16x3_eligible(self.cout, self.cin, self.k)
+        split_f = split and self.cin % 16 == 0 and not f16_f
+        split_d = split and self.cout % 16 == 0 and need_dgrad and not f16_d
+        # the fp32 K-major images only for the directions that run on the fp32-input MFMA kernels (every layer under 'f32'; the stems
+        # and the classifiers' data gradient otherwise): 106 small launches per step less in the split modes
+        return ConvPlan(wino, wino_f16, f16_f, f16_d, split_f, split_d, fp32_f=not (f16_f or split_f),
+                        fp32_d=need_dgrad and not (f16_d or split_d))
+
+    def set_plan(self, need_dgrad):
+        """adopt plan(need_dgrad): the mode attributes fprop / dgrad / wgrad_route dispatch on (no buffers, no launches: repack does those)"""
+        p = self.plan(need_dgrad)
+        self.wino, self.wino_f16, self.f16_f, self.f16_d, self.split_f, self.split_d = p[:6]
+        return p
+
+    def _buffer(self, name, shape, dtype=torch.float32):
+        """the weight image self.<name>: kept while it has this shape and type on the weights' device, else allocated"""
+        t = getattr(self, name)
+        if t is None or t.device != self.weight.device or t.dtype != dtype or tuple(t.shape) != shape:
+            t = torch.empty(shape, dtype=dtype, device=self.weight.device)
+            setattr(self, name, t)
+        return t
 
     def repack(self, need_dgrad, batch=None, rec=None):
-        """batch: a WeightBatch collecting the f16x3 images of the whole network for its three launches (the other packings, a few
-        small layers, are launched here either way); rec: a list that receives those other launches as (function, args) -- the model replays
-        them on later steps instead of walking its layers again (EncoderDecoder.repack_weights)"""
+        """the weight images plan() asks for.  batch: a WeightBatch collecting the f16x3 images of the whole network for its three launches
+        (the other packings, a few small layers, are launched here either way); rec: a list that receives those other launches as
+        (function, args) -- the model replays them on later steps instead of walking its layers again (EncoderDecoder.repack_weights)"""
         if self.depthwise:
             return
 
@@ -262,65 +336,34 @@ class Conv2dP(nn.Module):
             if rec is not None:
                 rec.append((fn, a))
             return fn(*a)
-        self.wino = self._wino_eligible()
-        f16 = CONV_MATH == 'f16x3'
-        self.wino_f16 = self.f16_f = self.f16_d = False
-        if self.wino:
-            split = _split_mode()                   # transform-domain GEMMs on a split kernel: split-packed filter sets
-            # (the transform-domain GEMMs have no 64-row tile: more than 64 rows in both directions)
-            self.wino_f16 = (f16 and ops.f16x3_eligible(self.cin, self.cout) and self.cout > 64
-                             and (not need_dgrad or (ops.f16x3_eligible(self.cout, self.cin) and self.cin > 64)))
-            n = (ops.WINO_TILE + 2) ** 2 * (self.weight.numel() // 9) * ((4 if self.wino_f16 else 6) if split else 1)
+        p = self.set_plan(need_dgrad)
+        w, split = self.weight.data, _split_mode()
+        if p.wino:
+            # transform-domain GEMMs on a split kernel: split-packed filter sets
+            n = (ops.WINO_TILE + 2) ** 2 * (w.numel() // 9) * ((4 if p.wino_f16 else 6) if split else 1)
             dt = torch.uint8 if split else torch.float32
-            if self.uf is None or self.uf.device != self.weight.device or self.uf.dtype != dt or self.uf.numel() != n:
-                self.uf = torch.empty(n, dtype=dt, device=self.weight.device)
-                self.ud = None
-            if need_dgrad and self.ud is None:
-                self.ud = torch.empty(n, dtype=dt, device=self.weight.device)
-            if self.wino_f16 and batch is not None:
+            uf = self._buffer('uf', (n,), dt)
+            ud = self._buffer('ud', (n,), dt) if need_dgrad else None
+            if p.wino_f16 and batch is not None:
                 batch.add_wino(self, need_dgrad)
-            elif self.wino_f16:
-                _, _, self.uf_amax, self.ud_amax = ops.wino_pack_weight_f16(self.weight.data, True, need_dgrad, self.uf,
-                                                                            self.ud if need_dgrad else None)
+            elif p.wino_f16:
+                _, _, self.uf_amax, self.ud_amax = ops.wino_pack_weight_f16(w, True, need_dgrad, uf, ud)
             else:
-                pack = ops.wino_pack_weight_split if split else ops.wino_pack_weight
-                launch(pack, self.weight.data, True, need_dgrad, self.uf, self.ud if need_dgrad else None)
-            if self.bias is None:
-                return                    # the direct-convolution packings are not needed
-        self.f16_f = f16 and ops.f16x3_eligible(self.cin, self.cout, self.k)
-        self.f16_d = f16 and need_dgrad and ops.f16x3_eligible(self.cout, self.cin, self.k)
-        # the fp32 K-major images only for the directions that run on the fp32-input MFMA kernels (every layer under 'f32'; the stems
-        # and the classifiers' data gradient otherwise): 106 small launches per step less in the split modes
-        fp32_f = not (self.f16_f or (_split_mode() and self.cin % 16 == 0))
-        fp32_d = need_dgrad and not (self.f16_d or (_split_mode() and self.cout % 16 == 0))
-        if fp32_f or fp32_d:
-            if self.wf is None or self.wf.device != self.weight.device:
-                self.wf = torch.empty(self.k * self.k * self.cin, self.cout, device=self.weight.device)
-                self.wd = None
-            if fp32_d and self.wd is None:
-                self.wd = torch.empty(self.k * self.k * self.cout, self.cin, device=self.weight.device)
-            launch(ops.pack_weight, self.weight.data, fp32_f, fp32_d, self.wf if fp32_f else None, self.wd if fp32_d else None)
-        if self.f16_f or self.f16_d:
-            nbytes = 4 * self.weight.numel()
-            if self.f16_f and (self.w4f is None or self.w4f.device != self.weight.device):
-                self.w4f = torch.empty(nbytes, dtype=torch.uint8, device=self.weight.device)
-            if self.f16_d and (self.w4d is None or self.w4d.device != self.weight.device):
-                self.w4d = torch.empty(nbytes, dtype=torch.uint8, device=self.weight.device)
+                launch(ops.wino_pack_weight_split if split else ops.wino_pack_weight, w, True, need_dgrad, uf, ud)
+        taps = self.k * self.k
+        if p.fp32_f or p.fp32_d:
+            launch(ops.pack_weight, w, p.fp32_f, p.fp32_d, self._buffer('wf', (taps * self.cin, self.cout)) if p.fp32_f else None,
+                   self._buffer('wd', (taps * self.cout, self.cin)) if p.fp32_d else None)
+        if p.f16_f or p.f16_d:
+            w4f = self._buffer('w4f', (4 * w.numel(),), torch.uint8) if p.f16_f else None
+            w4d = self._buffer('w4d', (4 * w.numel(),), torch.uint8) if p.f16_d else None
             if batch is not None:
                 batch.add_direct(self)
             else:
-                _, _, self.w_amax = ops.pack_weight_f16x2(self.weight.data, self.f16_f, self.f16_d, self.w4f if self.f16_f else None,
-                                                          self.w4d if self.f16_d else None)
-        self.split_f = _split_mode() and self.cin % 16 == 0 and not self.f16_f
-        self.split_d = _split_mode() and self.cout % 16 == 0 and need_dgrad and not self.f16_d
-        if self.split_f or self.split_d:
-            nbytes = 6 * self.weight.numel()
-            if self.split_f and (self.w6f is None or self.w6f.device != self.weight.device):
-                self.w6f = torch.empty(nbytes, dtype=torch.uint8, device=self.weight.device)
-            if self.split_d and (self.w6d is None or self.w6d.device != self.weight.device):
-                self.w6d = torch.empty(nbytes, dtype=torch.uint8, device=self.weight.device)
-            launch(ops.pack_weight_split, self.weight.data, self.split_f, self.split_d, self.w6f if self.split_f else None,
-                   self.w6d if self.split_d else None)
+                _, _, self.w_amax = ops.pack_weight_f16x2(w, p.f16_f, p.f16_d, w4f, w4d)
+        if p.split_f or p.split_d:
+            launch(ops.pack_weight_split, w, p.split_f, p.split_d, self._buffer('w6f', (6 * w.numel(),), torch.uint8) if p.split_f else None,
+                   self._buffer('w6d', (6 * w.numel(),), torch.uint8) if p.split_d else None)
 
 
 def repack_key(need_dgrad):
@@ -348,11 +391,9 @@ class WeightBatch:
 
     def add_wino(self, conv, need_dgrad):
         n = (ops.WINO_TILE + 2) ** 2 * conv.cout * conv.cin
-        dev = conv.weight.device
-        if conv.pf is None or conv.pf.device != dev or conv.pf.numel() != n:      # plain transform-domain sets, resident per layer
-            conv.pf, conv.pd = torch.empty(n, device=dev), None
-        if need_dgrad and conv.pd is None:
-            conv.pd = torch.empty(n, device=dev)
+        conv._buffer('pf', (n,))                # plain transform-domain sets, resident per layer
+        if need_dgrad:
+            conv._buffer('pd', (n,))
         self.items.append((conv, ops.WINO_TILE, need_dgrad))
 
     def flush(self):
@@ -583,7 +624,7 @@ def conv_forward(x, conv, tape, out=None):
         y = ops.dwconv(xd, conv.weight.data, conv.dilation, out=out)
     else:
         y = conv.fprop(xd, out=out, bias=None if conv.bias is None else conv.bias.data, keep=tape is not None,
-                       x_amax=amax_of(x) if (conv.f16_f or conv.wino_f16) else None)
+                       x_amax=amax_of(x) if conv.fprop_reads_amax else None)
     saved_v = None if conv.depthwise else conv.saved_v
     yv = Var(y, tape is not None)
     if tape is not None:
@@ -659,33 +700,28 @@ def join_side_stream():
             main.wait_stream(side)
 
 
-def _wgrad(conv, xd, dy, saved_v, x_amax=None, dy_amax=None, x_bnl=None):
-    """weight gradient of a dense convolution into conv.weight.grad (fp32 atomics): Winograd-domain, 1x1 / 3x3 K-quad or generic
-    kernel; in the split modes the 1x1 and Winograd-domain products use the fp32-faithful split on the bf16 / fp16 matrix cores.
-    saved_v: (transformed input, its amax slot group) kept from the forward pass; x_amax / dy_amax: slot groups when the caller has
-    them (f16x3)"""
-    split = _split_mode()
-    f16 = split and CONV_MATH == 'f16x3' and conv.cout > 64
-    v, v_amax = saved_v if saved_v is not None else (None, None)
-    if conv.wino_wgrad_ok(xd.shape[2], xd.shape[3]):
-        # the f16x3 Winograd-domain weight gradient pairs with the f16x3 forward pass: only a `wino_f16` layer keeps a PACKED V with
-        # the slot group of its scale bound.  A Winograd layer outside the f16x3 GEMM's shapes (3x3 64 -> 256, 48 -> 512: Cin not a
-        # multiple of 32, or a data gradient the kernel does not cover) kept a plain fp32 V and takes the bf16x6 product (ADVICE r3)
-        f16w = f16 and conv.wino_f16
-        ops.wino_wgrad_(conv.weight.grad, xd, dy, conv.dilation, v=v, split=2 if f16w else split, v_amax=v_amax if f16w else None,
+def _wgrad(conv, xd, dy, saved_v, x_amax=None, dy_amax=None, x_bnl=None, route=None):
+    """weight gradient of a dense convolution into conv.weight.grad (fp32 atomics) on the kernel conv.wgrad_route names: Winograd-domain,
+    1x1 / 3x3 K-quad or generic; in the split modes the 1x1 and Winograd-domain products use the fp32-faithful split on the bf16 / fp16
+    matrix cores.  saved_v: (transformed input, its amax slot group) kept from the forward pass; x_amax / dy_amax: slot groups when the
+    caller has them (f16x3); x_bnl: xd is the pre-normalisation tensor the forward GEMM normalised as it loaded it
+    (conv_bn_act(defer='amax') -> conv3), coef [C, 4] its record; route: conv.wgrad_route's answer where the caller has asked already"""
+    if route is None:
+        route = conv.wgrad_route(xd.shape[2], xd.shape[3], xd, dy, lazy=x_bnl is not None)
+    if route.startswith('wino'):
+        v, v_amax = saved_v if saved_v is not None else (None, None)
+        f16w = route == 'wino_f16x3'
+        ops.wino_wgrad_(conv.weight.grad, xd, dy, conv.dilation, v=v, split=2 if f16w else _split_mode(), v_amax=v_amax if f16w else None,
                         x_amax=x_amax if f16w else None, dy_amax=dy_amax if f16w else None)
-    elif f16 and conv.k == 1 and conv.stride == 1 and (xd.shape[2] * xd.shape[3]) % 4 == 0:
-        # x_bnl: xd is the pre-normalisation tensor the forward GEMM normalised as it loaded it (conv_bn_act(defer='amax') -> conv3)
+    elif route in WGRAD_READS_AMAX:
         assert x_bnl is None or x_amax is not None
-        ops.conv_wgrad_f16x3_(conv.weight.grad, xd, dy, x_amax if x_amax is not None else ops.absmax(xd),
-                              dy_amax if dy_amax is not None else ops.absmax(dy), bnl=x_bnl)
-        return
-    elif x_bnl is not None:
-        raise RuntimeError('a normalise-on-load input reached a weight-gradient kernel that reads the tensor as stored')
-    elif conv.wgrad_f16q_ok(xd.shape[2], xd.shape[3]) and ops.wgrad_q_operands_ok(xd, dy):
-        ops.conv_wgrad_f16q_(conv.weight.grad, xd, dy, x_amax if x_amax is not None else ops.absmax(xd),
-                             dy_amax if dy_amax is not None else ops.absmax(dy), conv.k, conv.dilation)
-    elif split and conv.k == 1 and conv.stride == 1 and (xd.shape[2] * xd.shape[3]) % 4 == 0:
+        x_amax = x_amax if x_amax is not None else ops.absmax(xd)
+        dy_amax = dy_amax if dy_amax is not None else ops.absmax(dy)
+        if route == 'line_f16x3':
+            ops.conv_wgrad_f16x3_(conv.weight.grad, xd, dy, x_amax, dy_amax, bnl=x_bnl)
+        else:
+            ops.conv_wgrad_f16q_(conv.weight.grad, xd, dy, x_amax, dy_amax, conv.k, conv.dilation)
+    elif route == 'quad_bf16x6':
         ops.conv_wgrad_split_(conv.weight.grad, xd, dy, conv.k, conv.stride, conv.dilation, conv.padding)
     else:
         ops.conv_wgrad_(conv.weight.grad, xd, dy, conv.k, conv.stride, conv.dilation, conv.padding)
@@ -708,26 +744,6 @@ def conv_backward(x, conv, dy, saved_v=None, final=False, dy_amax=None, dw_bnb=N
     dy_amax: the slot group the kernel that produced dy published max |dy| to (f16x3)"""
     xd = x.data if x.lazy is None else x.lazy[0]
     x_bnl = None if x.lazy is None else x.lazy[1]          # the depthwise layer's input is normalised on load (conv_bn_act(defer=True))
-    f16w = CONV_MATH == 'f16x3' and not conv.depthwise and conv.cout > 64 and conv.k == 1 and conv.stride == 1
-    wino16 = CONV_MATH == 'f16x3' and not conv.depthwise and conv.wino_f16
-    f16q = not conv.depthwise and x.lazy is None and conv.wgrad_f16q_ok(xd.shape[2], xd.shape[3])
-    x_amax = amax_of(x) if (f16w or f16q or (wino16 and saved_v is None)) else None
-    if (f16w or f16q or wino16) and dy_amax is None:
-        dy_amax = ops.absmax(dy)
-    if WGRAD_STREAM and not conv.depthwise:
-        wg_bnl = x_bnl if not (conv.depthwise or conv.wino) else None       # (the Winograd layers' weight gradient reads the kept transform)
-
-        def wg():
-            _wgrad(conv, xd, dy, saved_v, x_amax, dy_amax, wg_bnl)
-        # (every tensor the side stream reads is recorded on it: the host drops its references when this closure returns, long before the
-        # queued launch runs -- the coefficient rows of a normalise-on-load input included)
-        _on_side_stream(wg, dy, xd, None if saved_v is None else saved_v[0], wg_bnl, x_amax, dy_amax,
-                        None if saved_v is None else saved_v[1])          # (the slot groups are views of an arena block that is replaced every ~10 steps)
-        if conv.bias is not None:
-            ops.bias_grad_(conv.bias.grad, dy)
-        if x.requires_grad:
-            _dgrad_into(x, conv, dy, final, dy_amax)
-        return
     if conv.depthwise:
         if x.requires_grad:
             buf, acc = x.grad_target()         # both gradients from one staging of dy and one read of x (3 N of traffic instead of 4 N)
@@ -735,12 +751,28 @@ def conv_backward(x, conv, dy, saved_v=None, final=False, dy_amax=None, dw_bnb=N
         else:
             assert x_bnl is None and dw_bnb is None          # (a depthwise layer on the network input: weight gradient only)
             ops.dwconv_wgrad_(conv.weight.grad, xd, dy, conv.dilation)
+        return
+    wg_bnl = x_bnl if not conv.wino else None           # (the Winograd layers' weight gradient reads the kept transform)
+    x_amax = None
+    route = conv.wgrad_route(xd.shape[2], xd.shape[3], xd, dy, lazy=wg_bnl is not None)
+    if route in WGRAD_READS_AMAX:
+        # the maxima its kernel scales by, on this stream in front of the launches (a transform kept from the forward pass stands in for x)
+        x_amax = amax_of(x) if saved_v is None else None
+        dy_amax = dy_amax if dy_amax is not None else ops.absmax(dy)
+
+    def wg():
+        _wgrad(conv, xd, dy, saved_v, x_amax, dy_amax, wg_bnl, route)
+    if WGRAD_STREAM:
+        # (every tensor the side stream reads is recorded on it: the host drops its references when this closure returns, long before the
+        # queued launch runs -- the coefficient rows of a normalise-on-load input included)
+        _on_side_stream(wg, dy, xd, None if saved_v is None else saved_v[0], wg_bnl, x_amax, dy_amax,
+                        None if saved_v is None else saved_v[1])          # (the slot groups are views of an arena block that is replaced every ~10 steps)
     else:
-        _wgrad(conv, xd, dy, saved_v, x_amax, dy_amax, x_bnl if not conv.wino else None)
-        if conv.bias is not None:
-            ops.bias_grad_(conv.bias.grad, dy)
-        if x.requires_grad:
-            _dgrad_into(x, conv, dy, final, dy_amax)
+        wg()
+    if conv.bias is not None:
+        ops.bias_grad_(conv.bias.grad, dy)
+    if x.requires_grad:
+        _dgrad_into(x, conv, dy, final, dy_amax)
 
 
 _identity_rows = {}
@@ -813,9 +845,9 @@ def conv_bn_act(x, conv, bn, tape, relu=True, residual=None, out=None, post_scal
             pre = ops.dwconv(xd, conv.weight.data, conv.dilation, bnl=x_bnl)
     elif fused_stats:                              # GEMM epilogue, or the Winograd output transform
         pre, st, slots = conv.fprop(xd, out=pre_out, want_stats=True, keep=tape is not None,
-                                    x_amax=amax_of(x) if (conv.f16_f or conv.wino_f16) else None, bnl=x_bnl, want_minmax=need_pred)
+                                    x_amax=amax_of(x) if conv.fprop_reads_amax else None, bnl=x_bnl, want_minmax=need_pred)
     else:
-        pre = conv.fprop(xd, keep=tape is not None, x_amax=amax_of(x) if (conv.f16_f or conv.wino_f16) else None, bnl=x_bnl)
+        pre = conv.fprop(xd, keep=tape is not None, x_amax=amax_of(x) if conv.fprop_reads_amax else None, bnl=x_bnl)
     saved_v = None if conv.depthwise else conv.saved_v
     if _BN_EVAL:
         assert tape is None, 'eval-mode BN is inference only'
@@ -868,9 +900,8 @@ def conv_bn_act(x, conv, bn, tape, relu=True, residual=None, out=None, post_scal
     in_hw = xd.shape[-2:]
     if final and x.lazy is None and x.requires_grad and conv.dgrad_can_gate(in_hw):
         x.gate_consumer = True            # this layer's data gradient completes dL/dx and can add a gated identity-branch gradient (Var.pending)
-    def need_dpre_amax():                 # f16x3: does a kernel reading dL/dpre of this layer scale it from a published maximum?
-        return CONV_MATH == 'f16x3' and not conv.depthwise and ((conv.f16_d and x.requires_grad) or (conv.cout > 64 and conv.k == 1)
-                                                                or conv.wino_f16 or conv.wgrad_f16q_ok(pre.shape[2], pre.shape[3]))
+    def need_dpre_amax():                 # does a kernel reading dL/dpre of this layer scale it from a published maximum?
+        return not conv.depthwise and ((conv.dgrad_reads_amax and x.requires_grad) or conv.wgrad_route(*in_hw) in WGRAD_READS_AMAX)
 
     if FUSE_RES_GATE and not relu and residual is None and out_var is None and post_scale is None and (not defer or as_residual) and not conv.depthwise \
             and (pre.shape[2] * pre.shape[3]) % 256 == 0:

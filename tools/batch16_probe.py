@@ -76,14 +76,14 @@ def main():
         t = {}
         for n in (8, 16):
             x = torch.relu(torch.randn(n, cin, H, W, device=dev))
-            xa = ops.absmax(x) if (conv.f16_f or conv.wino_f16 or layers.CONV_MATH == 'f16x3') else None
-            y = conv.fprop(x, keep=True, x_amax=xa if (conv.f16_f or conv.wino_f16) else None)
+            xa = ops.absmax(x) if (conv.fprop_reads_amax or layers.CONV_MATH == 'f16x3') else None
+            y = conv.fprop(x, keep=True, x_amax=xa if conv.fprop_reads_amax else None)
             saved_v = conv.saved_v
             dy = torch.randn_like(y) * 1e-3
             da = ops.absmax(dy) if layers.CONV_MATH == 'f16x3' else None
             dx = torch.empty_like(x)
             need_d = cin >= 16                                   # the stem's first convolution has no data gradient
-            tf = timeit(lambda: conv.fprop(x, keep=False, x_amax=xa if (conv.f16_f or conv.wino_f16) else None))
+            tf = timeit(lambda: conv.fprop(x, keep=False, x_amax=xa if conv.fprop_reads_amax else None))
             td = timeit(lambda: conv.dgrad(dy, (H, W), dx, False, dy_amax=da)) if need_d else 0.0
             tw = timeit(lambda: layers._wgrad(conv, x, dy, saved_v, xa, da))
             t[n] = (tf, td, tw)
