@@ -29,7 +29,7 @@ class Var:
         self.bn = None
         self._claimed = self._sealed = False
         # (pre, coef): a conv -> BN -> ReLU output that is never materialised -- data is None, the ONE consumer (a depthwise layer, the stem's
-        # max-pool) normalises the pre-BN tensor `pre` with coef[c] = (mean, invstd, sc, sh) as it loads it (layers.conv_bn_act(defer=True))
+        # max-pool) normalises the pre-BN tensor `pre` with coef[c] = (mean, invstd, sc, sh) as it loads it (layers.norm_plan decides, NormPlan.dest 'lazy')
         self.lazy = None
         self.lazy_norelu = False      # lazy, and the deferred layer has NO ReLU (a downsample conv -> BN: read only as bn_apply's residual operand)
         self.amax = None          # device slot with max |data| (scale of the two-piece fp16 split, layers.CONV_MATH == 'f16x3'), set on first use
@@ -43,7 +43,7 @@ class Var:
         # a downsample layer's output (conv -> BN, no ReLU; read only as the residual of the block's bn3): what bn3's backward needs to run BOTH
         # layers' BatchNorm backward in one reduction + one apply pass (layers.FUSE_BN_BWD_DUAL); 'done' = (dL/dpre, its amax group) once it has
         self.dual = None
-        # a concat buffer whose writers leave their PRE-normalisation outputs in its slices (layers.conv_bn_act(defer='slice')): [C, 4] rows
+        # a concat buffer whose writers leave their PRE-normalisation outputs in its slices (layers.norm_plan, NormPlan.dest 'slice'): [C, 4] rows
         # (mean, invstd, sc, sh) per channel, filled slice by slice; the owner turns the buffer into a lazy Var for its single consumer
         self.coef_table = None
 

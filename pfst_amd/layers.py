@@ -183,6 +183,11 @@ class Conv2dP(nn.Module):
         """the same for the data gradient and max |dy|"""
         return self.f16_d or self.wino_f16
 
+    def emits_minmax(self, into_slice=False):
+        """the kernel producing this layer's output can emit its per-channel (min, max) partials (fprop / ops.dwconv(want_minmax=True)): the f16x3
+        GEMM epilogue and, unless the output goes into a slice of a concat buffer, the Winograd output transform and the depthwise kernels"""
+        return self.bias is None and ((self.f16_f and not self.wino) or ((self.wino or self.depthwise) and not into_slice))
+
     def fprop(self, xd, out=None, bias=None, want_stats=False, keep=False, x_amax=None, bnl=None, want_minmax=False):
         """keep: training forward -- the Winograd path keeps its transformed input for the weight gradient (self.saved_v);
         x_amax: the slot with max |xd| when the caller has it (f16x3 layers; computed here otherwise);
@@ -215,6 +220,11 @@ class Conv2dP(nn.Module):
         (ops.conv_wgrad_f16x3_(bnl=...)): a 1x1 f16x3 layer on the 256-row tile -- every Bottleneck conv3"""
         return (CONV_MATH == 'f16x3' and self.f16_f and not self.wino and not self.depthwise and self.bias is None and self.cout > 64
                 and ops.conv_fprop_bnl_ok(self.cin, self.cout, self.k, self.stride, self.padding))
+
+    def wino_bnl_ok(self, h, w, training):
+        """the Winograd input transform can normalise an h x w input on load (fprop(bnl=...)); in training the weight gradient must then come
+        from the transform kept in forward, the only place the normalised values exist"""
+        return self.wino and self.bias is None and (not training or self.wino_wgrad_ok(h, w))
 
     def can_fuse_bn_backward(self):
         """the data gradient runs on the K-quad implicit-GEMM kernel with whole row tiles (its epilogue can emit the sums)"""
@@ -486,11 +496,9 @@ class DepthwiseSeparableConvModule(nn.Module):
         self.pointwise_conv = ConvModule(cin, cout, 1)
 
     def forward(self, x, tape, out=None, post_scale=None, defer=False):
-        # FOLD_BN_DWSEP: the depthwise stage's conv -> BN -> ReLU output is never written -- the pointwise layer's f16x3 GEMM and weight gradient
-        # normalise the depthwise output as they load it (the depthwise kernel emits the (min, max) partials of the predicted maximum)
         h, w = (x.data if x.lazy is None else x.lazy[0]).shape[-2:]
-        fold = FOLD_BN_DWSEP and self.pointwise_conv.conv.fprop_bnl_ok() and (h * w) % 128 == 0
-        return self.pointwise_conv(self.depthwise_conv(x, tape, defer='amax' if fold else False), tape, out=out, post_scale=post_scale, defer=defer)
+        y = self.depthwise_conv(x, tape, defer=folds_into_pointwise([self.pointwise_conv.conv], h * w))
+        return self.pointwise_conv(y, tape, out=out, post_scale=post_scale, defer=defer)
 
 
 # the atrous depthwise branches of the ASPP head as ONE launch each way (csrc/dwconv.hip, pfst_dwconv3x3_multi_*); False: per branch
@@ -535,6 +543,110 @@ FUSE_BN_BWD_DUAL = True
 # operands (dL/dpre is never written)
 
 
+class NormPlan(NamedTuple):
+    """what norm_plan decides for one conv -> BN [-> ReLU] layer: where the normalised result goes and what the statistics step produces"""
+    # 'written': the normalisation pass (ops.bn_apply) writes y.  Else y is never written and the single consumer normalises the pre-BN tensor
+    # as it loads it: 'lazy' (Var.lazy = (pre, coef, bn)), 'lazy_norelu' (the same without a ReLU: read only as a residual operand),
+    # 'slice' (the convolution writes pre-BN values into the concat slice, the coefficient rows go into the concat's table)
+    dest: str = 'written'
+    fused_stats: bool = True        # the batch statistics come out of the producing kernel (else the stand-alone ops.bn_stats pass) ...
+    tiny: bool = False              # ... which a layer with a handful of values per channel never does (see norm_plan)
+    predict_amax: bool = False      # max |y| of the unwritten tensor is predicted from the producer's (min, max) partials (f16x3 consumers)
+    identity_rows: bool = False     # a concat writer that normalises its slice itself after all: identity rows into the concat's table
+    want_coef: bool = False         # the statistics step also forms the (mean, invstd, sc, sh) rows
+
+
+def _deferral_allowed():            # a normalised tensor may be left unwritten at all: the master switch, and never on running statistics
+    return DEFER_BN_APPLY and not _BN_EVAL
+
+
+# `defer` -- the vocabulary of conv_bn_act, ConvModule.forward, DepthwiseSeparableConvModule.forward and dwsep_branches -- names the layer's
+# ONLY consumer, as the caller guarantees it:
+#   False       anything: the normalised tensor is written;
+#   True        a kernel that normalises on load and needs nothing else (a depthwise layer, the stem's max-pool);
+#   'amax'      an f16x3 GEMM operand producer that normalises on load (the Winograd input transform, which writes V pre-split; a 256-row 1x1
+#               GEMM): under f16x3 it needs max |y| of the tensor that is never written -- the producing kernel emits (min, max) partials
+#               and ops.bn_finalize_partials predicts it exactly;
+#   'slice'     the same through a concat buffer: `out` is a slice of a concat Var whose owner set up a coefficient table (Var.coef_table) and,
+#               under f16x3, a shared slot group for the maximum (Var.amax);
+#   'residual'  (a downsample conv -> BN, no ReLU) the residual operand of the block's bn3 normalisation pass, which applies fma(r, sc, sh)
+#               as it loads r (ops.bn_apply(residual_coef=...)).
+# A layer that cannot honour the request writes its output as usual.
+def norm_plan(conv, in_shape, defer=False, relu=True, residual=False, out=False, post_scale=False, tape=False, table=False, group=False):
+    """The route of one conv -> BN [-> ReLU] layer, stated ONCE: conv_bn_act and dwsep_branches ask and then only execute.  Reads the switches,
+    CONV_MATH, _BN_EVAL, the conv's adopted plan, the (N, C, H, W) it reads and what the call has (truth values; table / group: the concat
+    `out` is a slice of has a coefficient table / a shared slot group); no tensor data, no launch, any device -- like Conv2dP.plan"""
+    n, _, h, w = in_shape
+    plain = _deferral_allowed() and not residual and not post_scale
+    need_pred = defer in ('amax', 'slice') and CONV_MATH == 'f16x3'
+    if defer == 'slice':
+        lazy = bool(table and plain and relu and not conv.depthwise and not conv.wino and (group or not need_pred))
+    elif defer == 'residual':
+        lazy = bool(plain and not relu and not out and not conv.depthwise)
+    else:
+        lazy = bool(defer and plain and relu and not out)
+    # Batch statistics over a handful of values per channel (the ASPP image-pool branch: N x C x 1 x 1, i.e. b values) are a
+    # cancellation: var = E[x^2] - mean^2 from the epilogue's fp32 partial sums of squares loses what torch's two-pass variance keeps
+    # (per-link test: 1.3e-3 on that layer's backward against 6e-5 for torch-fp32).  Those tiny layers take the stand-alone statistics
+    # kernel, whose sums of exact fp64 squares are exact for fp32 inputs.
+    tiny = n * h * w <= 64
+    fused_stats = FUSE_BN_STATS and not _BN_EVAL and not tiny
+    # no producer of (min, max) partials for a maximum that must be predicted, or no finalize kernel to fill the table's rows: written as usual
+    if (need_pred and not (fused_stats and conv.emits_minmax(into_slice=defer == 'slice'))) or (defer == 'slice' and not fused_stats):
+        lazy = False
+    dest = 'written' if not lazy else {'slice': 'slice', 'residual': 'lazy_norelu'}.get(defer, 'lazy')
+    return NormPlan(dest, fused_stats, tiny, need_pred and lazy, identity_rows=bool(defer == 'slice' and table and not lazy),
+                    want_coef=not _BN_EVAL and bool((tape and FUSE_BN_BWD) or lazy))
+
+
+# The consumers' side -- may THIS consumer normalise its input on load?  Each returns the `defer` to hand the producing layer.
+def folds_into_wino(conv2, h, w, training):                 # Bottleneck bn1 into conv2's Winograd input transform
+    return 'amax' if FOLD_BN_WINO and conv2.wino_bnl_ok(h, w, training) else False
+
+
+def folds_into_gemm(conv3, hw):                             # Bottleneck bn2 into conv3's f16x3 GEMM and weight gradient; hw: pixels per plane
+    return 'amax' if FOLD_BN_GEMM and conv3.fprop_bnl_ok() and hw % 128 == 0 else False
+
+
+# a depthwise stage into its pointwise f16x3 GEMM and weight gradient (the depthwise kernels -- strip, whole-plane, three-branch -- emit the
+# (min, max) partials); several pointwise layers: the fused atrous branches, all or none
+def folds_into_pointwise(pointwise_convs, hw):
+    return 'amax' if FOLD_BN_DWSEP and hw % 128 == 0 and all(c.fprop_bnl_ok() for c in pointwise_convs) else False
+
+
+# the ASPP concat's writers into the bottleneck's Winograd input transform; the concat's owner allocates the coefficient table on this answer,
+# hence the deferral switch here too
+def folds_into_concat(bottleneck_conv, h, w, training):
+    return 'slice' if FOLD_BN_CONCAT and _deferral_allowed() and bottleneck_conv.wino_bnl_ok(h, w, training) else False
+
+
+def folds_into_residual():                                  # a downsample branch into the residual operand of its block's bn3 normalisation pass
+    return 'residual' if FOLD_BN_RESIDUAL else False
+
+
+def _batch_stats(pre, bn, plan, tape, relu, stats=None, slice_var=None):
+    """the statistics step of a conv -> BN layer -> (mean, invstd, coef | None, pred_amax | None).  stats: (workspace, slots), the producing
+    kernel's partials (plan.fused_stats); slice_var: the concat slice of plan.dest == 'slice' (rows into its table, the maximum into its group)"""
+    if _BN_EVAL:
+        assert tape is None, 'eval-mode BN is inference only'
+        return bn.running_mean, torch.rsqrt(bn.running_var + BN_EPS), None, None
+    n, c, h, w = pre.shape
+    if n * h * w == 1:
+        # torch.nn.functional.batch_norm's own check: the image-pool BatchNorm of the ASPP head sees N x C x 1 x 1, so a per-GPU batch of
+        # one cannot train (SURVEY K7); same exception type and text as the reference raises
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size(pre.shape)}')
+    into_slice = plan.dest == 'slice'
+    gb = dict(gamma=bn.weight.data, beta=bn.bias.data) if plan.want_coef else {}
+    pred_amax = (slice_var.parent.amax if into_slice else ops.amax_slots(pre.device)) if plan.predict_amax else None
+    if plan.fused_stats:
+        res = ops.bn_finalize_partials(*stats, c, n * h * w, bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS, predict_amax=pred_amax,
+                                       relu=relu, coef_out=slice_var.parent.coef_table[slice_var.c0:slice_var.c1] if into_slice else None, **gb)
+    else:
+        res = ops.bn_stats(pre, bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS, **gb)
+    bn._pending_batches += 1
+    return res[0], res[1], res[2] if plan.want_coef else None, pred_amax
+
+
 def dwsep_branches(x, mods, tape, outs, pool=None, defer=False):
     """DepthwiseSeparableConvModules `mods` applied to the SAME input x (the ASPP head's atrous branches, sep_aspp_head.py:63-77), results
     into the concat slices `outs`.  Where the fused kernels cover the shape the depthwise stages run as one launch -- every plane of x is
@@ -552,15 +664,13 @@ def dwsep_branches(x, mods, tape, outs, pool=None, defer=False):
     if not fused:
         return [m(x, tape, out=o, defer=defer) for m, o in zip(mods, outs)]
     xd = x.data
-    want_stats = FUSE_BN_STATS and not _BN_EVAL
-    # FOLD_BN_DWSEP: the branches' normalised depthwise outputs are never written, the pointwise GEMMs normalise on load (see the flag)
-    n_, c_, h_, w_ = xd.shape
-    fold = (FOLD_BN_DWSEP and DEFER_BN_APPLY and CONV_MATH == 'f16x3' and want_stats and (h_ * w_) % 128 == 0
-            and all(m.pointwise_conv.conv.fprop_bnl_ok() for m in mods))
+    # one route for all branches (same shape, same consumer kind): where the pointwise GEMMs normalise on load the branches' normalised
+    # depthwise outputs are never written
+    plan = norm_plan(convs[0], xd.shape, folds_into_pointwise([m.pointwise_conv.conv for m in mods], xd.shape[2] * xd.shape[3]), tape=tape is not None)
+    fold = plan.dest == 'lazy'
+    res = ops.dwconv_multi(xd, [c.weight.data for c in convs], dils, want_stats=plan.fused_stats, want_mean=pool is not None, want_minmax=fold)
     if pool is not None:
-        res, pool['mean'] = ops.dwconv_multi(xd, [c.weight.data for c in convs], dils, want_stats=want_stats, want_mean=True, want_minmax=fold)
-    else:
-        res = ops.dwconv_multi(xd, [c.weight.data for c in convs], dils, want_stats=want_stats, want_minmax=fold)
+        res, pool['mean'] = res
     dpres, bnbs = [None] * len(mods), [None] * len(mods)
     if tape is not None:
         x.claim_first_use()
@@ -576,22 +686,7 @@ def dwsep_branches(x, mods, tape, outs, pool=None, defer=False):
     for i, m in enumerate(mods):
         bn = m.depthwise_conv.bn
         pre, st, slots = res[i]
-        if _BN_EVAL:
-            assert tape is None, 'eval-mode BN is inference only'
-            mean, invstd, coef = bn.running_mean, torch.rsqrt(bn.running_var + BN_EPS), None
-        else:
-            want_coef = (tape is not None and FUSE_BN_BWD) or fold
-            gb = dict(gamma=bn.weight.data, beta=bn.bias.data) if want_coef else {}
-            n, c, h, w = pre.shape
-            pred_amax = ops.amax_slots(pre.device) if fold else None
-            if want_stats:
-                out3 = ops.bn_finalize_partials(st, slots, c, n * h * w, bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS,
-                                                predict_amax=pred_amax, relu=True, **gb)
-            else:
-                out3 = ops.bn_stats(pre, bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS, **gb)
-            mean, invstd = out3[:2]
-            coef = out3[2] if want_coef else None
-            bn._pending_batches += 1
+        mean, invstd, coef, pred_amax = _batch_stats(pre, bn, plan, tape, True, (st, slots))
         yv = Var(None, tape is not None)
         if fold:
             yv.lazy, yv.amax = (pre, coef, bn), pred_amax          # never written: the pointwise GEMM and its weight gradient normalise on load
@@ -794,81 +889,30 @@ def conv_bn_act(x, conv, bn, tape, relu=True, residual=None, out=None, post_scal
     post_scale: [N, C] factors applied to y after the ReLU -- the Dropout2d mask of the layer feeding conv_seg, folded into the
     normalisation pass and, in backward, into the BatchNorm-backward passes (one tensor round trip less each way)"""
     assert post_scale is None or residual is None
-    # defer: the caller guarantees that the ONLY consumer of the result normalises on load (a depthwise layer or the stem's max-pool): the
-    # normalisation pass is skipped, the returned Var carries (pre, coef) in .lazy and no data.  x.lazy: this layer IS such a consumer.
-    # defer='amax': the consumer is an f16x3 GEMM operand producer (the Winograd input transform, which writes V pre-split) and needs
-    # max |y| of the tensor that is never written: under f16x3 the producing GEMM emits (min, max) partials and the finalize kernel predicts it
+    # defer: what the caller guarantees about the result's ONLY consumer (norm_plan documents the values); where the plan honours it the
+    # normalisation pass is skipped and the returned Var carries (pre, coef, bn) in .lazy and no data.  x.lazy: this layer IS such a consumer.
     xd = x.data if x.lazy is None else x.lazy[0]
     x_bnl = None if x.lazy is None else x.lazy[1]
     assert x.lazy is None or not x.lazy_norelu, 'a deferred downsample output (no ReLU) is only read as a residual'
     assert x_bnl is None or conv.depthwise or (conv.wino and conv.bias is None) or conv.fprop_bnl_ok(), \
         'only a depthwise layer, the Winograd input transform, a 256-row 1x1 f16x3 GEMM (or the max-pool) reads a deferred normalisation'
-    # defer='slice': `out` is a slice of a concat Var with a coefficient table (Var.coef_table): the PRE-normalisation output goes into the slice,
-    # this layer's rows into the table, the predicted maximum into the concat's shared slot group
-    # defer='residual' (a downsample conv -> BN layer, no ReLU): the ONLY consumer is the residual operand of the block's bn3 normalisation
-    # pass, which applies fma(r, sc, sh) as it loads r (ops.bn_apply(residual_coef=...)); the returned Var is marked lazy_norelu
-    as_residual = defer == 'residual'
-    into_slice = slice_requested = defer == 'slice'
-    need_pred = defer in ('amax', 'slice') and CONV_MATH == 'f16x3'
-    if into_slice:
-        defer = bool(isinstance(out, Var) and out.parent is not None and out.parent.coef_table is not None and DEFER_BN_APPLY and not _BN_EVAL and relu
-                     and residual is None and post_scale is None and not conv.depthwise and not conv.wino and (not need_pred or out.parent.amax is not None))
-        into_slice = defer
-    elif as_residual:
-        defer = bool(FOLD_BN_RESIDUAL and DEFER_BN_APPLY and not _BN_EVAL and not relu and residual is None and out is None and post_scale is None
-                     and not conv.depthwise)
-        as_residual = defer
-    else:
-        defer = bool(defer and DEFER_BN_APPLY and not _BN_EVAL and relu and residual is None and out is None and post_scale is None)
-    # Batch statistics over a handful of values per channel (the ASPP image-pool branch: N x C x 1 x 1, i.e. b values) are a
-    # cancellation: var = E[x^2] - mean^2 from the epilogue's fp32 partial sums of squares loses what torch's two-pass variance keeps
-    # (per-link test: 1.3e-3 on that layer's backward against 6e-5 for torch-fp32).  Those tiny layers take the stand-alone statistics
-    # kernel, whose sums of exact fp64 squares are exact for fp32 inputs.
-    tiny = xd.shape[0] * xd.shape[2] * xd.shape[3] <= 64
-    fused_stats = FUSE_BN_STATS and not _BN_EVAL and not tiny
-    # producers of (min, max) partials: the f16x3 GEMM epilogue and (not into a concat slice) the Winograd output transform
-    mm_producer = conv.bias is None and ((conv.f16_f and not conv.wino) or (conv.wino and not into_slice) or (conv.depthwise and not into_slice))
-    if need_pred and not (defer and fused_stats and mm_producer):
-        defer = need_pred = into_slice = False           # no producer of (min, max) partials here: the normalised tensor is written as usual
-    if into_slice and not fused_stats:
-        defer = into_slice = False
-    if slice_requested and not into_slice and isinstance(out, Var) and out.parent is not None and out.parent.coef_table is not None:
+    cat = out.parent if isinstance(out, Var) else None          # the concat buffer `out` is a slice of
+    plan = norm_plan(conv, xd.shape, defer, relu, residual is not None, out is not None, post_scale is not None, tape is not None,
+                     table=cat is not None and cat.coef_table is not None, group=cat is not None and cat.amax is not None)
+    defer, into_slice, need_pred = plan.dest != 'written', plan.dest == 'slice', plan.predict_amax
+    if plan.identity_rows:
         # this writer normalises its slice itself after all: identity rows, max(fma(y, 1, 0), 0) = y for its ReLU'd (non-negative) values
         assert relu
-        out.parent.coef_table[out.c0:out.c1] = identity_coef_row(out.data.device)
-    need_pred = need_pred and defer
-    pre_out = out.data if into_slice else None           # the convolution writes straight into the concat slice
+        cat.coef_table[out.c0:out.c1] = identity_coef_row(out.data.device)
+    # with fused statistics -> (pre, workspace, slots): out of the depthwise kernel, the GEMM epilogue or the Winograd output transform
     if conv.depthwise:
-        if fused_stats:                            # batch statistics come out of the producing kernel in every case
-            pre, st, slots = ops.dwconv(xd, conv.weight.data, conv.dilation, want_stats=True, bnl=x_bnl, want_minmax=need_pred)
-        else:
-            pre = ops.dwconv(xd, conv.weight.data, conv.dilation, bnl=x_bnl)
-    elif fused_stats:                              # GEMM epilogue, or the Winograd output transform
-        pre, st, slots = conv.fprop(xd, out=pre_out, want_stats=True, keep=tape is not None,
-                                    x_amax=amax_of(x) if conv.fprop_reads_amax else None, bnl=x_bnl, want_minmax=need_pred)
-    else:
-        pre = conv.fprop(xd, keep=tape is not None, x_amax=amax_of(x) if conv.fprop_reads_amax else None, bnl=x_bnl)
+        pre = ops.dwconv(xd, conv.weight.data, conv.dilation, want_stats=plan.fused_stats, bnl=x_bnl, want_minmax=need_pred)
+    else:           # (into a concat slice the convolution writes its pre-BN output straight into the buffer)
+        pre = conv.fprop(xd, out=out.data if into_slice else None, want_stats=plan.fused_stats, keep=tape is not None,
+                         x_amax=amax_of(x) if conv.fprop_reads_amax else None, bnl=x_bnl, want_minmax=need_pred)
+    pre, *stats = pre if plan.fused_stats else (pre,)
     saved_v = None if conv.depthwise else conv.saved_v
-    if _BN_EVAL:
-        assert tape is None, 'eval-mode BN is inference only'
-        mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + BN_EPS)
-    else:
-        if pre.shape[0] * pre.shape[2] * pre.shape[3] == 1:
-            # torch.nn.functional.batch_norm's own check: the image-pool BatchNorm of the ASPP head sees N x C x 1 x 1, so a per-GPU batch of
-            # one cannot train (SURVEY K7); same exception type and text as the reference raises
-            raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size(pre.shape)}')
-        want_coef = (tape is not None and FUSE_BN_BWD) or defer
-        gb = dict(gamma=bn.weight.data, beta=bn.bias.data) if want_coef else {}
-        pred_amax = (out.parent.amax if into_slice else ops.amax_slots(pre.device)) if need_pred else None
-        if fused_stats:
-            n, c, h, w = pre.shape
-            res = ops.bn_finalize_partials(st, slots, c, n * h * w, bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS, predict_amax=pred_amax,
-                                           relu=relu, coef_out=out.parent.coef_table[out.c0:out.c1] if into_slice else None, **gb)
-        else:
-            res = ops.bn_stats(pre, bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS, **gb)
-        mean, invstd = res[:2]
-        coef = res[2] if want_coef else None
-        bn._pending_batches += 1
+    mean, invstd, coef, pred_amax = _batch_stats(pre, bn, plan, tape, relu, stats, out if into_slice else None)
     out_var = None
     if isinstance(out, Var):                       # slice of a concat Var
         out_var, out = out, out.data
@@ -878,7 +922,7 @@ def conv_bn_act(x, conv, bn, tape, relu=True, residual=None, out=None, post_scal
     yv = out_var if out_var is not None else Var(None, tape is not None)
     if defer:
         yv.lazy, y = (pre, coef, bn), None           # no normalisation pass: the consumer applies (sc, sh) of `coef` and the ReLU as it loads `pre`
-        yv.lazy_norelu = as_residual                 # (a downsample layer: no ReLU -- only bn_apply's residual operand reads it)
+        yv.lazy_norelu = plan.dest == 'lazy_norelu'   # (a downsample layer: no ReLU -- only bn_apply's residual operand reads it)
         if need_pred and not into_slice:
             yv.amax = pred_amax                      # max |y| of the tensor that is never written (exact: bn_finalize_partials)
     else:
@@ -903,7 +947,7 @@ def conv_bn_act(x, conv, bn, tape, relu=True, residual=None, out=None, post_scal
     def need_dpre_amax():                 # does a kernel reading dL/dpre of this layer scale it from a published maximum?
         return not conv.depthwise and ((conv.dgrad_reads_amax and x.requires_grad) or conv.wgrad_route(*in_hw) in WGRAD_READS_AMAX)
 
-    if FUSE_RES_GATE and not relu and residual is None and out_var is None and post_scale is None and (not defer or as_residual) and not conv.depthwise \
+    if FUSE_RES_GATE and not relu and residual is None and out_var is None and post_scale is None and plan.dest in ('written', 'lazy_norelu') and not conv.depthwise \
             and (pre.shape[2] * pre.shape[3]) % 256 == 0:
         yv.gate_consumer = True           # a downsample layer (conv -> BN, no ReLU): its BatchNorm backward takes (g, mask) as its gated dy
         if FUSE_BN_BWD_DUAL:              # ... or rides in the bn3 backward of the block it is the residual of (same g: one reduction, one apply pass)
@@ -915,59 +959,52 @@ def conv_bn_act(x, conv, bn, tape, relu=True, residual=None, out=None, post_scal
                               gate if (BNB_GATE_FROM_MASK and relu and residual is not None) else None)
 
     def bwd():
+        # (dL/dpre, its amax group, the depthwise kernel's BatchNorm record) by one of four ways, then the convolution's backward
+        dpre = dw_bnb = None
         if yv.dual is not None and yv.dual['done'] is not None:
             # a downsample layer whose BatchNorm backward already ran inside the block's bn3 backward (pfst_bn_backward_dual)
             (dpre, dpre_amax), yv.dual = yv.dual['done'], None
-            conv_backward(x, conv, dpre, saved_v, final, dy_amax=dpre_amax)
-            if yv.parent is None:
-                yv.free_grad()
-            return
-        ext_gate = None
-        if yv.pending is not None and yv.grad_unwritten() and yv.gate_consumer and not relu and residual is None:
-            dy, ext_gate = yv.take_pending()          # downsample layer: dL/dy = g where the block's final ReLU passed; the mask is the gate
         else:
-            dy = yv.grad
-        dres = dacc = None
-        part, nslots = (yv.bn.partials, yv.bn.slots) if yv.bn is not None else (None, 0)
-        dpre_amax = ops.amax_slots(pre.device) if need_dpre_amax() else None
-        if residual is not None and residual.requires_grad:
-            if (FUSE_RES_GATE and gate is not None and relu and residual.gate_consumer and residual.pending is None and residual.parent is None
-                    and residual.grad_unwritten()):
-                dual = residual.dual if (FUSE_BN_BWD_DUAL and post_scale is None and not conv.depthwise) else None
-                if dual is not None:
-                    # the residual is a downsample layer's output: its BatchNorm backward and this layer's read the same gated gradient
-                    ds_amax = ops.amax_slots(pre.device) if dual['need_amax']() else None
-                    ds_bn = dual['bn']
-                    both = ops.bn_backward_dual(
-                        dy, gate,
-                        dict(x=pre, mean=mean, invstd=invstd, gamma=bn.weight.data, dgamma=bn.weight.grad, dbeta=bn.bias.grad, partials=part,
-                             slots=nslots, amax=dpre_amax),
-                        dict(x=dual['x'], mean=dual['mean'], invstd=dual['invstd'], gamma=ds_bn.weight.data, dgamma=ds_bn.weight.grad,
-                             dbeta=ds_bn.bias.grad, amax=ds_amax))
-                    if both is not None:
-                        dual['done'] = (both[1], ds_amax)
-                        conv_backward(x, conv, both[0], saved_v, final, dy_amax=dpre_amax)
-                        if yv.parent is None:
-                            yv.free_grad()
-                        return
-                residual.pending = (dy, gate)         # dL/dresidual = dy * gate: left to the launch that completes the residual's gradient
+            ext_gate = None
+            if yv.pending is not None and yv.grad_unwritten() and yv.gate_consumer and not relu and residual is None:
+                dy, ext_gate = yv.take_pending()          # downsample layer: dL/dy = g where the block's final ReLU passed; the mask is the gate
             else:
-                dres, dacc = residual.grad_target()
-        # without a residual the ReLU mask is recomputed from the pre-BN tensor (one HBM read less per pass)
-        ymask = y if (relu and residual is not None and gate is None) else None
-        if (conv.depthwise and relu and residual is None and gate is None
-                and post_scale is None and x.requires_grad):
-            # the depthwise backward forms dL/dpre itself from (dy, pre) and the record of the two sums: 3 N of traffic less
-            rec = ops.bn_backward_sums(dy, pre, mean, invstd, bn.weight.data, bn.bias.data, bn.weight.grad, bn.bias.grad, partials=part,
-                                       slots=nslots)
-            conv_backward(x, conv, dy, saved_v, final, dw_bnb=(pre, rec))
-            if yv.parent is None:
-                yv.free_grad()
-            return
-        dpre = ops.bn_backward(dy, ymask, pre, mean, invstd, bn.weight.data, bn.weight.grad, bn.bias.grad,
-                               relu or ext_gate is not None, dres, bool(dacc), beta=bn.bias.data, mask=gate if ext_gate is None else ext_gate,
-                               partials=part, slots=nslots, amax=dpre_amax, post=post_scale)
-        conv_backward(x, conv, dpre, saved_v, final, dy_amax=dpre_amax)
+                dy = yv.grad
+            dres = dacc = None
+            part, nslots = (yv.bn.partials, yv.bn.slots) if yv.bn is not None else (None, 0)
+            dpre_amax = ops.amax_slots(pre.device) if need_dpre_amax() else None
+            if residual is not None and residual.requires_grad:
+                if (FUSE_RES_GATE and gate is not None and relu and residual.gate_consumer and residual.pending is None and residual.parent is None
+                        and residual.grad_unwritten()):
+                    dual = residual.dual if (FUSE_BN_BWD_DUAL and post_scale is None and not conv.depthwise) else None
+                    if dual is not None:
+                        # the residual is a downsample layer's output: its BatchNorm backward and this layer's read the same gated gradient
+                        ds_amax = ops.amax_slots(pre.device) if dual['need_amax']() else None
+                        ds_bn = dual['bn']
+                        both = ops.bn_backward_dual(
+                            dy, gate,
+                            dict(x=pre, mean=mean, invstd=invstd, gamma=bn.weight.data, dgamma=bn.weight.grad, dbeta=bn.bias.grad, partials=part,
+                                 slots=nslots, amax=dpre_amax),
+                            dict(x=dual['x'], mean=dual['mean'], invstd=dual['invstd'], gamma=ds_bn.weight.data, dgamma=ds_bn.weight.grad,
+                                 dbeta=ds_bn.bias.grad, amax=ds_amax))
+                        if both is not None:
+                            dpre, dual['done'] = both[0], (both[1], ds_amax)
+                    if dpre is None:
+                        residual.pending = (dy, gate)     # dL/dresidual = dy * gate: left to the launch that completes the residual's gradient
+                else:
+                    dres, dacc = residual.grad_target()
+            if dpre is None and conv.depthwise and relu and residual is None and gate is None and post_scale is None and x.requires_grad:
+                # the depthwise backward forms dL/dpre itself from (dy, pre) and the record of the two sums: 3 N of traffic less
+                rec = ops.bn_backward_sums(dy, pre, mean, invstd, bn.weight.data, bn.bias.data, bn.weight.grad, bn.bias.grad, partials=part,
+                                           slots=nslots)
+                dpre, dw_bnb = dy, (pre, rec)
+            elif dpre is None:
+                # without a residual the ReLU mask is recomputed from the pre-BN tensor (one HBM read less per pass)
+                ymask = y if (relu and residual is not None and gate is None) else None
+                dpre = ops.bn_backward(dy, ymask, pre, mean, invstd, bn.weight.data, bn.weight.grad, bn.bias.grad,
+                                       relu or ext_gate is not None, dres, bool(dacc), beta=bn.bias.data, mask=gate if ext_gate is None else ext_gate,
+                                       partials=part, slots=nslots, amax=dpre_amax, post=post_scale)
+        conv_backward(x, conv, dpre, saved_v, final, dy_amax=dpre_amax, dw_bnb=dw_bnb)
         if yv.parent is None:
             yv.free_grad()
     tape.record(bwd, dict(op='conv_bn_act', conv=conv, bn=bn, x=x, residual=residual, relu=relu, out=yv))

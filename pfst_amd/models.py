@@ -49,19 +49,18 @@ class Bottleneck(nn.Module):
             self.downsample = nn.Sequential(Conv2dP(inplanes, planes * 4, 1, stride), BatchNorm2dP(planes * 4))
 
     def forward(self, x, tape):
-        # conv2 through the Winograd domain (layer2.1 ... layer4.2): its input transform normalises conv1's output as it loads it -- y1 is never
-        # written; the weight gradient of conv2 comes from the transformed input kept in forward, BatchNorm backward of bn1 from the pre-BN tensor
+        # Three of the block's four normalised tensors have ONE reader that can normalise on load (the layers.folds_into_* predicates say when;
+        # layers.norm_plan whether the producing layer can oblige) and are then never written: y1 where conv2 runs through the Winograd domain
+        # (layer2.1 ... layer4.2: its input transform normalises; the weight gradient of conv2 comes from the transformed input kept in forward,
+        # BatchNorm backward of bn1 from the pre-BN tensor), y2 where conv3 is a 1x1 on the 256-row f16x3 tile (its GEMM normalises between load
+        # and split, and so does its weight gradient), the downsample branch as the residual operand of bn3's normalisation pass
         h, w = x.data.shape[-2:]
-        fold = layers_mod.FOLD_BN_WINO and self.conv2.wino and self.conv2.bias is None and (tape is None or self.conv2.wino_wgrad_ok(h, w))
-        o = conv_bn_act(x, self.conv1, self.bn1, tape, defer='amax' if fold else False)
-        # conv3 (1x1 on the 256-row f16x3 tile) normalises conv2's output between load and split, and so does its weight gradient: y2 is never
-        # written either (layers.FOLD_BN_GEMM); conv2 -- the Winograd output transform, or layer1's direct GEMM -- emits the (min, max) partials
-        # that predict max |y2|
-        fold2 = layers_mod.FOLD_BN_GEMM and self.conv3.fprop_bnl_ok() and (h // self.conv2.stride) * (w // self.conv2.stride) % 128 == 0
-        o = conv_bn_act(o, self.conv2, self.bn2, tape, defer='amax' if fold2 else False)
+        o = conv_bn_act(x, self.conv1, self.bn1, tape, defer=layers_mod.folds_into_wino(self.conv2, h, w, tape is not None))
+        s2 = self.conv2.stride
+        o = conv_bn_act(o, self.conv2, self.bn2, tape, defer=layers_mod.folds_into_gemm(self.conv3, (h // s2) * (w // s2)))
         idt = x
         if self.downsample is not None:
-            idt = conv_bn_act(x, self.downsample[0], self.downsample[1], tape, relu=False, defer='residual')     # layers.FOLD_BN_RESIDUAL: normalised by bn3's pass
+            idt = conv_bn_act(x, self.downsample[0], self.downsample[1], tape, relu=False, defer=layers_mod.folds_into_residual())
         return conv_bn_act(o, self.conv3, self.bn3, tape, relu=True, residual=idt)
 
 
@@ -334,13 +333,10 @@ class DepthwiseSeparableASPPHead(BaseDecodeHead):
         # layers.FOLD_BN_CONCAT: the four conv -> BN -> ReLU writers leave their pre-normalisation outputs in the slices; the bottleneck's Winograd
         # input transform normalises per channel (the image-pool slice holds final values: identity rows) -- four normalisation passes over
         # 512-channel maps less per pass
-        bconv = self.bottleneck.conv
-        fold = (layers_mod.FOLD_BN_CONCAT and layers_mod.DEFER_BN_APPLY and not layers_mod._BN_EVAL and bconv.wino and bconv.bias is None
-                and (tape is None or bconv.wino_wgrad_ok(h, w)))
-        if fold:
+        sl = layers_mod.folds_into_concat(self.bottleneck.conv, h, w, tape is not None)
+        if sl:
             cat.coef_table = torch.empty(nb * ch, 4, device=x.data.device)
             cat.coef_table[:ch] = layers_mod.identity_coef_row(x.data.device)          # y = max(fma(v, 1, 0), 0) = v for the (non-negative) pooled values
-        sl = 'slice' if fold else False
         self.aspp_modules[0](x, tape, out=cat.slice(ch, 2 * ch), defer=sl)
         nd = len(self.dilations)
         # on the fused path the atrous branches' launch also forms the plane means of x, its backward their adjoint
@@ -372,7 +368,7 @@ class DepthwiseSeparableASPPHead(BaseDecodeHead):
             # order on the tape: gap-backward must run AFTER the image_pool conv's backward, pool-broadcast before it
             self._reorder_pool(tape, (bwd_gap, dict(op='gap', name='decode_head.gap', x=x, out=pooled)),
                                (bwd_pool, dict(op='broadcast', name='decode_head.image_pool.up', x=pa, out=cat.slice(0, ch))))
-        if fold:
+        if sl:
             # every writer deferred?  (a writer that could not -- no (min, max) partials for its shape -- wrote its slice normalised: identity rows)
             cat.lazy = (cat.data, cat.coef_table, None)
         feats = self.bottleneck(cat, tape)

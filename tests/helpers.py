@@ -47,6 +47,20 @@ def seeded_pfgst_state(oracle_mod, seed, num_classes=6, in_channels=3):
     return both, student, teacher
 
 
+# feature-map size each layer class READS at a 1024 x 1024 tile (ResNetV1c-50, output stride 8; the decoder's skip branch at stride 4)
+SIZES = [
+    (r'backbone\.stem\.0$', 1024),
+    (r'backbone\.stem\.[36]$', 512),
+    (r'backbone\.layer1\.', 256),
+    (r'backbone\.layer2\.0\.(conv1|conv2|downsample\.0)$', 256),
+    (r'backbone\.layer[234]\.', 128),
+    (r'decode_head\.image_pool\.', 1),
+    (r'decode_head\.(aspp_modules|bottleneck)\.', 128),
+    (r'decode_head\.(c1_bottleneck|sep_bottleneck|conv_seg)', 256),
+    (r'auxiliary_head\.', 128),
+]
+
+
 def to_dev(batch, dev):
     return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in batch.items()}
 

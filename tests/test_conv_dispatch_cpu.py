@@ -7,20 +7,7 @@ import re
 
 import pytest
 
-from helpers import model_cfg
-
-# feature-map size each layer class READS at a 1024 x 1024 tile (ResNetV1c-50, output stride 8; the decoder's skip branch at stride 4)
-SIZES = [
-    (r'backbone\.stem\.0$', 1024),
-    (r'backbone\.stem\.[36]$', 512),
-    (r'backbone\.layer1\.', 256),
-    (r'backbone\.layer2\.0\.(conv1|conv2|downsample\.0)$', 256),
-    (r'backbone\.layer[234]\.', 128),
-    (r'decode_head\.image_pool\.', 1),
-    (r'decode_head\.(aspp_modules|bottleneck)\.', 128),
-    (r'decode_head\.(c1_bottleneck|sep_bottleneck|conv_seg)', 256),
-    (r'auxiliary_head\.', 128),
-]
+from helpers import SIZES, model_cfg
 
 # families: 'fp32' the fp32-input MFMA kernel, 'bf16x6' / 'f16x3' the split kernels, 'wino_*' through the Winograd domain with that GEMM.
 # weight-gradient routes: Conv2dP.wgrad_route's answers.
