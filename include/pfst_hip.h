@@ -478,10 +478,16 @@ int pfst_cross_prob_bwd_k(const float* prob, const float* gP, int N, int C, int 
 int pfst_sim_loss_finalize_k(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg, float* out,
                              pfst_stream_t stream);
 
-/* ---- EMA teacher + AdamW on flat parameter arenas (pfgst.py:105-127, torch.optim.AdamW) ------ */
+/* ---- EMA teacher + AdamW + SGD on flat parameter arenas (pfgst.py:105-127, torch.optim.AdamW / SGD) ------ */
 int pfst_ema_update(float* teacher, const float* student, long long n, float alpha, pfst_stream_t stream);
 int pfst_adamw_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, int step, float grad_scale, pfst_stream_t stream);
+/* torch.optim.SGD, single-tensor form, maximize=False: d = g*grad_scale + weight_decay*p; with momentum != 0: buf = d when first_step, else
+ * momentum*buf + (1-dampening)*d, then d = d + momentum*buf (nesterov) or buf; p -= lr*d.  Each of these sums with a scaled term is one
+ * fused multiply-add, as in torch's add(alpha) kernels; momentum*buf rounds on its own.  buf is null iff momentum == 0.  Pointers that are
+ * all 16-byte aligned (a ParamArena) take the float4 body, others the scalar loop. */
+int pfst_sgd_step(float* p, const float* g, float* buf, long long n, float lr, float momentum, float dampening,
+                  float weight_decay, int nesterov, int first_step, float grad_scale, pfst_stream_t stream);
 
 /* ---- loss bookkeeping (base.py:177-222) ------------------------------------------------------- */
 /* out[0] = loss_weight*acc[0]/numel ; out[1] = 100*(acc[1]+eps)/(acc[2]+eps) ; out[2] = acc[3] (count of invalid labels) */

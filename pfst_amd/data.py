@@ -7,7 +7,9 @@ Sources:
   * TileFolder         -- a folder dataset of converted tiles (rsiseg/datasets/custom.py:85-175, isprs.py) read with PIL and pushed
                           through the config's own pipeline list (pfst_amd/pipeline.py);
   * UDADataset / UDADatasetV2 -- the source/target pairings + rare-class sampling of the reference, same NumPy RNG stream;
-  * epoch_indices / uda_batches -- the distributed sampler (samplers/distributed_sampler.py:11-70) and the collation."""
+  * epoch_indices / uda_batches -- the distributed sampler (samplers/distributed_sampler.py:11-70) and the collation.
+A plain dataset dict in cfg.data.train (no source / target: supervised training) goes through `build_dataset` to a TileFolder; its
+batches carry img / img_metas / gt_semantic_seg only."""
 import json
 import os
 
@@ -207,6 +209,17 @@ def build_uda_dataset(train_cfg):
     return UDA_DATASET_TYPES[kind](TileFolder(train_cfg['source']), TileFolder(train_cfg['target']), train_cfg)
 
 
+def build_dataset(train_cfg):
+    """cfg.data.train: a UDADataset / UDADatasetV2 dict (source / target pairs -> build_uda_dataset) or a plain dataset dict such as
+    dict(type='ISPRSDataset', data_root=..., img_dir=..., ann_dir=..., pipeline=...) -> TileFolder, whose items are img / gt_semantic_seg /
+    img_metas: the batches of supervised training (EncoderDecoder.train_step)"""
+    if train_cfg.get('type') in UDA_DATASET_TYPES:
+        return build_uda_dataset(train_cfg)
+    if 'source' in train_cfg or 'target' in train_cfg:
+        raise KeyError(f"dataset type {train_cfg.get('type')!r} with source / target entries: the pairing types are {sorted(UDA_DATASET_TYPES)}")
+    return TileFolder(train_cfg)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # sampler + collation
 # ----------------------------------------------------------------------------------------------------------------------
@@ -232,7 +245,8 @@ def collate(items, device):
         if key in items[0]:
             batch[key] = torch.stack([it[key] for it in items]).to(device, non_blocking=True)
     batch['img_metas'] = [it['img_metas'] for it in items]
-    batch['target_img_metas'] = [it['target_img_metas'] for it in items]
+    if 'target_img_metas' in items[0]:          # items of a plain dataset (supervised training) have no target side
+        batch['target_img_metas'] = [it['target_img_metas'] for it in items]
     return batch
 
 
@@ -309,7 +323,8 @@ def _collate_cpu(items):
         if key in items[0]:
             batch[key] = torch.stack([it[key] for it in items])
     batch['img_metas'] = [it['img_metas'] for it in items]
-    batch['target_img_metas'] = [it['target_img_metas'] for it in items]
+    if 'target_img_metas' in items[0]:          # items of a plain dataset (supervised training) have no target side
+        batch['target_img_metas'] = [it['target_img_metas'] for it in items]
     return batch
 
 

@@ -1169,6 +1169,15 @@ def adamw_step_(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=1.0):
          float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale), _stream())
 
 
+def sgd_step_(p, g, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first_step=False, grad_scale=1.0):
+    """pfst_sgd_step: torch.optim.SGD's single-tensor update of the flat fp32 tensor `p` in place; `buf` (the momentum buffer, same size) is
+    None exactly when momentum == 0; first_step: the buffer is written (= the decayed gradient) without being read"""
+    n = p.numel()
+    assert g.numel() == n and (buf is None) == (momentum == 0) and (buf is None or buf.numel() == n)
+    call('pfst_sgd_step', _dense(p).data_ptr(), _dense(g).data_ptr(), None if buf is None else _dense(buf).data_ptr(), n, float(lr),
+         float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), int(bool(first_step)), float(grad_scale), _stream())
+
+
 # ---------------------------------------------------------------- strong augmentation
 def color_jitter_(img, params, mean3, std3, denorm=True):
     _dense(img)

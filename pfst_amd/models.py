@@ -699,6 +699,24 @@ class EncoderDecoder(nn.Module):
             return self.forward_train(img, img_metas, **kwargs)
         return self.forward_test(img, img_metas, **kwargs)
 
+    # ------------------------------------------------------------------ supervised training (encoder_decoder.py:127-164)
+    def train_step(self, data_batch, optimizer, **kwargs):
+        """One supervised iteration on `img` / `img_metas` / `gt_semantic_seg` (any other key is an error) ->
+        dict(loss, log_vars, num_samples, states).  The reference's train_step (encoder_decoder.py:127-164, base.py:177-222) PLUS what
+        mmcv's OptimizerHook does after it under `optimizer_config = dict()` (no grad_clip): zero_grad, backward, step -- this project's
+        runner has no hooks, and PFGST.train_step steps inside as well.  log_vars holds the reference's keys in the reference's order
+        (decode.loss_ce, decode.acc_seg, aux.loss_ce, aux.acc_seg, loss) as Python floats; `loss` stays in it (base.py:214 -- only
+        PFGST pops it) and is the top-level `loss` too.  `states` is {} unless `self.return_vis_states` is set.  Labels outside
+        [0, C) other than ignore_index raise ValueError after the step's single read.  The step itself: pfst_amd/supervised.py."""
+        from . import supervised
+        return supervised.train_step(self, data_batch, optimizer)
+
+    @property
+    def param_arena(self):
+        """the flat parameter / gradient arena of the supervised step (None before the first train_step)"""
+        from . import supervised
+        return supervised.step_state(self).arena
+
     def forward_train(self, img, img_metas, gt_semantic_seg, seg_weight=None, return_feats=False,
                       return_decoded_feats=False, return_logits=False, return_states=False, tape=None, grad_scale=1.0,
                       grad_ready=None):

@@ -42,6 +42,10 @@ def uda_cfg(num_classes=6, in_channels=3, dropout=0.1, blur=True, color_jitter_p
 OPTIMIZER = dict(type='AdamW', lr=6e-5, betas=(0.9, 0.999), weight_decay=0.01)
 LR_CONFIG = dict(policy='poly', warmup='linear', warmup_iters=1500, warmup_ratio=1e-6, power=1.0, min_lr=0.0, by_epoch=False)
 
+# configs/_base_/schedules/schedule_40k.py:2-5 (the supervised schedules; 20k ... 320k differ in max_iters and the intervals only)
+SGD_OPTIMIZER = dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0005)
+SGD_LR_CONFIG = dict(policy='poly', power=0.9, min_lr=1e-4, by_epoch=False)
+
 # BASELINE.json configs[1..4]: name -> (num_classes, in_channels, tile size, per-GPU batch, PFGSTLoss downscale)
 WORKLOADS = {
     'pfst_pots_irrg2vaih_irrg_deeplabv3plus_r50-d8': dict(num_classes=6, in_channels=3, size=1024, per_gpu_batch=8, downscale=0.5),

@@ -59,6 +59,24 @@ def find_latest_checkpoint(path, suffix='pth'):
     return best
 
 
+def init_student_from(model, path):
+    """A bare-keyed segmentor checkpoint (backbone.* / decode_head.* / auxiliary_head.*: what a supervised run saves) into BOTH networks of
+    a UDA wrapper -- `model.*` and `ema_model.*`, parameters and BatchNorm buffers -- so that self-training starts from a source-trained
+    student.  Fails on any missing or unexpected key: a half-initialised student would train without a word."""
+    if not (hasattr(model, 'get_model') and hasattr(model, 'get_ema_model')):
+        raise TypeError(f'init_student_from needs a UDA wrapper with a student and an EMA teacher, got {type(model).__name__}')
+    ckpt = torch.load(path, map_location='cpu', weights_only=False)
+    sd = ckpt.get('state_dict', ckpt)
+    own = model.get_model().state_dict()
+    missing = [k for k in own if k not in sd]
+    unexpected = [k for k in sd if k not in own]
+    if missing or unexpected:
+        raise KeyError(f'{path}: {len(missing)} segmentor keys missing (first: {missing[:3]}), {len(unexpected)} unexpected '
+                       f'(first: {unexpected[:3]}); expected the bare keys of a supervised checkpoint')
+    model.get_model().load_state_dict(sd, strict=True)
+    model.get_ema_model().load_state_dict(sd, strict=True)
+
+
 def is_main():
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 

@@ -6,7 +6,14 @@
 
 `--synthetic` trains on seeded synthetic tiles (benchmarks); otherwise `cfg.data.train` (UDADataset: source / target folders of
 converted tiles, each with the config's own pipeline list) is read by pfst_amd/data.py + pfst_amd/pipeline.py, and
-`cfg.data.val` is evaluated every `evaluation.interval` iterations unless --no-validate (rsiseg/apis/train.py:152-168)."""
+`cfg.data.val` is evaluated every `evaluation.interval` iterations unless --no-validate (rsiseg/apis/train.py:152-168).
+
+Supervised training (source-only / target-only baselines, a source-trained start for self-training): a config WITHOUT a `uda` section
+builds a bare EncoderDecoder (registry.build_train_model) whose own train_step runs; `cfg.data.train` is then a plain dataset dict
+(type / data_root / img_dir / ann_dir / pipeline) and the optimizer usually the SGD of configs/_base_/schedules/schedule_*.py.
+`--supervised` drops the `uda` section of a config or preset (a UDADataset in data.train is replaced by its `source` entry; a preset takes
+schedule_40k's SGD + poly schedule).  Checkpoints of such a run have bare keys: tools/test.py reads them without key revision, and
+`--init-student-from CKPT` starts a self-training run (a `uda` config) with them in both the student and the EMA teacher."""
 import argparse
 import os
 import sys
@@ -19,6 +26,9 @@ def parse_args(argv=None):
     p.add_argument('config', help='train config file path (reference format) or a preset name from pfst_amd.presets')
     p.add_argument('--work-dir')
     p.add_argument('--load-from')
+    p.add_argument('--init-student-from', help='a bare-keyed segmentor checkpoint (backbone.* / decode_head.* / auxiliary_head.*, e.g. of a '
+                                               'supervised run) loaded into the student AND the EMA teacher of a `uda` config; every key must match')
+    p.add_argument('--supervised', action='store_true', help='drop the `uda` section: train the bare segmentor on img / gt_semantic_seg')
     p.add_argument('--resume-from')
     p.add_argument('--no-validate', action='store_true')
     g = p.add_mutually_exclusive_group()
@@ -55,12 +65,13 @@ def parse_args(argv=None):
 
 def load_cfg(args):
     from pfst_amd.config import Config, parse_cfg_options
-    from pfst_amd.presets import LR_CONFIG, OPTIMIZER, WORKLOADS, workload_cfg
+    from pfst_amd.presets import LR_CONFIG, OPTIMIZER, SGD_LR_CONFIG, SGD_OPTIMIZER, WORKLOADS, workload_cfg
     if os.path.exists(args.config):
         cfg = Config.fromfile(args.config)
     elif args.config in WORKLOADS:
         uda, w = workload_cfg(args.config)
-        cfg = Config(dict(model=uda.pop('model'), uda=uda, optimizer=dict(OPTIMIZER), lr_config=dict(LR_CONFIG),
+        opt, lr = (SGD_OPTIMIZER, SGD_LR_CONFIG) if args.supervised else (OPTIMIZER, LR_CONFIG)
+        cfg = Config(dict(model=uda.pop('model'), uda=uda, optimizer=dict(opt), lr_config=dict(lr),
                           runner=dict(type='IterBasedRunner', max_iters=40000), checkpoint_config=dict(by_epoch=False, interval=4000),
                           evaluation=dict(interval=4000, metric='mIoU'), log_config=dict(interval=50),
                           data=dict(samples_per_gpu=w['per_gpu_batch']), seed=0))
@@ -70,6 +81,14 @@ def load_cfg(args):
         cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
     if args.max_iters:
         cfg.runner['max_iters'] = args.max_iters
+    if args.supervised:
+        cfg.pop('uda', None)
+        train = (cfg.get('data') or {}).get('train')
+        if train is not None and 'source' in train:          # a source / target pairing: the supervised run reads its source entry
+            cfg.data['train'] = train['source']
+    if 'uda' not in cfg and ((cfg.get('optimizer_config') or {}).get('grad_clip') is not None):
+        raise NotImplementedError('optimizer_config.grad_clip: EncoderDecoder.train_step implements the hook without gradient clipping '
+                                  '(optimizer_config = dict(), every shipped schedule)')
     return cfg
 
 
@@ -79,11 +98,11 @@ def main(argv=None):
     import torch.distributed as dist
     import pfst_amd  # noqa: F401
     from pfst_amd import dist as pdist
-    from pfst_amd.data import build_loader, build_uda_dataset, synthetic_loader
+    from pfst_amd.data import build_dataset, build_loader, synthetic_loader
     from pfst_amd.evaluation import build_eval_fn
     from pfst_amd.optim import build_optimizer
     from pfst_amd.registry import build_train_model
-    from pfst_amd.runner import IterBasedRunner, find_latest_checkpoint, init_random_seed, set_random_seed
+    from pfst_amd.runner import IterBasedRunner, find_latest_checkpoint, init_random_seed, init_student_from, set_random_seed
 
     cfg = load_cfg(args)
     distributed = args.launcher != 'none'
@@ -100,6 +119,9 @@ def main(argv=None):
     seed = seed + rank if args.diff_seed else seed
     set_random_seed(seed, args.deterministic)
 
+    supervised = 'uda' not in cfg
+    if args.init_student_from and supervised:
+        raise SystemExit('--init-student-from fills the student and the teacher of a `uda` wrapper; a supervised run takes --load-from')
     load_from = args.load_from or cfg.get('load_from')
     resume = args.resume_from or cfg.get('resume_from')
     if resume is None and args.auto_resume:
@@ -107,7 +129,7 @@ def main(argv=None):
     pretrained = cfg.model.get('pretrained')
     if pretrained and not os.path.exists(str(pretrained)):
         # e.g. 'open-mmlab://resnet50_v1c': a model-zoo URL cannot be fetched here.  Never silently replace it by random weights.
-        if not (load_from or resume or args.random_init or args.synthetic):
+        if not (load_from or resume or args.init_student_from or args.random_init or args.synthetic):
             raise SystemExit(f'cfg.model.pretrained={pretrained!r} cannot be loaded offline: give --load-from / --resume-from a '
                              'checkpoint, point `pretrained` to a local file, or pass --random-init explicitly')
         cfg.model['pretrained'] = None
@@ -128,6 +150,9 @@ def main(argv=None):
         runner.log('deterministic mode: weight gradients / BatchNorm-backward / depthwise / bias sums in a fixed order -- bit-reproducible '
                    'gradients run to run and for any stream schedule; about 3 % slower (compare the `time` column with a run without '
                    '--deterministic)')
+    if args.init_student_from and not resume:            # a resumed run continues from its own checkpoint
+        init_student_from(model, args.init_student_from)
+        runner.log(f'student and EMA teacher initialised from {args.init_student_from}')
     if load_from:
         runner.load_checkpoint(load_from)
     if resume:
@@ -140,9 +165,11 @@ def main(argv=None):
     cin = cfg.model.backbone.get('in_channels', 3)
     if args.synthetic or 'train' not in data_cfg:
         loader = synthetic_loader(bs, args.crop_size or 1024, nc, cin, seed=1234 + rank, device=dev)
+        if supervised:                       # the synthetic batches without their target side
+            loader = ({k: v for k, v in b.items() if not k.startswith('target_')} for b in loader)
     else:
         # img_scale / ratio_range / crop_size / reduce_zero_label / flips / photometric steps all come from the config's pipelines
-        dataset = build_uda_dataset(data_cfg['train'])
+        dataset = build_dataset(data_cfg['train'])
         model.CLASSES = dataset.CLASSES
         model.PALETTE = dataset.PALETTE
         # the RESOLVED seed (--seed / cfg.seed / the broadcast random one) drives the sampler's shuffle (apis/train.py:74-89 passes
