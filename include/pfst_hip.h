@@ -356,6 +356,30 @@ int pfst_tta_accumulate(const float* src, long long src_bs, int N, int C, int Hs
 /* seg_logit /= views, then seg_logit.argmax(dim=1) (:367-368) in one pass: labels equal to pfst_div_scalar + pfst_argmax_nchw's */
 int pfst_tta_finalize(const float* acc, int N, int C, int HW, int views, unsigned char* label_u8, pfst_stream_t stream);
 
+/* ---- whole-scene prediction (pfst_amd/scene.py): slide_inference (:220-263) over a uint8 scene resident on the device, the windows forwarded
+ * in batches.  win_yx is a HOST array of B (y1, x1) pairs, B <= PFST_SCENE_MAX_WINDOWS: the offsets travel by value in the kernel arguments
+ * (no copy, no synchronisation); every window of size h x w must lie inside the H x W scene. */
+#define PFST_SCENE_MAX_WINDOWS 16
+/* out[b][c][i][j] = (scene[y1_b + i][x1_b + j][to_rgb ? 2 - c : c] - mean[c]) / std[c], float32 [B][3][h][w]: mmcv.imnormalize
+ * (pfst_amd.pipeline.normalize) of each window of the H x W x 3 uint8 scene (BGR as read), transposed to CHW, bit for bit */
+int pfst_scene_windows(const unsigned char* scene_u8, int H, int W, const int* win_yx, int B, int h, int w, float mean0, float mean1, float mean2,
+                       float std0, float std1, float std2, int to_rgb, float* out, pfst_stream_t stream);
+/* sums[C][H][W] += the batch's window logits resized to h x w, window by window in index order: bit-identical to B x (pfst_resize_bilinear of
+ * logits[b] ([C][hl][wl], batch stride logits_bs) to h x w, then pfst_window_accumulate at (y1_b, x1_b)).  Pixels that no window of the
+ * batch covers are neither read nor written.  Any C >= 1. */
+int pfst_scene_accumulate(const float* logits, long long logits_bs, int B, int C, int hl, int wl, const int* win_yx, int h, int w, float* sums,
+                          int H, int W, pfst_stream_t stream);
+/* sums -> label_u8 [H][W] (+ conf_u8 [H][W] = rint(p_max * 255), + probs [C][H][W]; either may be NULL): sums / count, softmax, first maximal
+ * class -- bit-identical to pfst_window_normalize -> pfst_softmax_nchw -> pfst_argmax_nchw.  The cover count of (y, x) is
+ * row_count[y] * col_count[x] (device int tables of H and W entries, all >= 1); there is no H x W count plane. */
+int pfst_scene_finalize(const float* sums, int C, int H, int W, const int* row_count, const int* col_count, unsigned char* label_u8,
+                        unsigned char* conf_u8, float* probs, pfst_stream_t stream);
+/* BaseSegmentor.show_result (segmentors/base.py:278-285): out_rgb[H][W][3] = palette_rgb[label] (colours <= 256 rows; labels beyond: 0), or with
+ * scene_bgr (H x W x 3 uint8, BGR) uint8(img * keep + colour * opacity) per channel in double arithmetic, truncated, img in RGB order;
+ * keep = 1 - opacity formed in double by the caller.  Bit-identical to the NumPy expression for every opacity in [0, 1]. */
+int pfst_paint_labels(const unsigned char* label_u8, int H, int W, const unsigned char* palette_rgb, int colours, const unsigned char* scene_bgr,
+                      double keep, double opacity, unsigned char* out_rgb, pfst_stream_t stream);
+
 /* ---- fused bilinear-upsample + softmax cross-entropy + accuracy (decode_head.py:249-283,
  * cross_entropy_loss.py:45-65, accuracy.py:6-61).  logits are [N][C][h][w]; labels/weights [N][H][W].
  * acc[0] += sum_i w_i*cw[y_i]*nll_i (0 at ignore), acc[1] += #correct, acc[2] += #non-ignored, acc[3] += #labels that are neither

@@ -962,6 +962,86 @@ def tta_finalize(acc, views):
     return lab
 
 
+# ---------------------------------------------------------------- whole-scene prediction (pfst_amd/scene.py)
+SCENE_MAX_WINDOWS = 16          # PFST_SCENE_MAX_WINDOWS: window offsets that travel by value with one launch
+
+
+def _win_yx(windows):
+    """[(y1, x1), ...] -> a host int array for the C ABI (copied into the kernel arguments by the entry point: no device copy)"""
+    if not 1 <= len(windows) <= SCENE_MAX_WINDOWS:
+        raise ValueError(f'1 .. {SCENE_MAX_WINDOWS} windows per launch, got {len(windows)}')
+    flat = [int(v) for yx in windows for v in yx]
+    return (ctypes.c_int * len(flat))(*flat)
+
+
+def scene_windows(scene_u8, windows, size, mean, std, to_rgb, out=None):
+    """the windows [(y1, x1), ...] of size (h, w) of a device uint8 [H, W, 3] scene (BGR as read), normalised as pipeline.normalize does
+    ((BGR -> RGB,) subtract mean, divide by std, fp32) -> float32 [B, 3, h, w], bit for bit"""
+    _dense(scene_u8, U8)
+    if scene_u8.dim() != 3 or scene_u8.shape[2] != 3 or len(mean) != 3 or len(std) != 3:
+        raise ValueError(f'scene must be [H, W, 3] with three means / stds, got {tuple(scene_u8.shape)}')
+    H, W = scene_u8.shape[:2]
+    h, w = int(size[0]), int(size[1])
+    b = len(windows)
+    if out is None:
+        out = torch.empty(b, 3, h, w, device=scene_u8.device)
+    assert tuple(_dense(out).shape) == (b, 3, h, w)
+    call('pfst_scene_windows', scene_u8.data_ptr(), H, W, _win_yx(windows), b, h, w, float(mean[0]), float(mean[1]), float(mean[2]),
+         float(std[0]), float(std[1]), float(std[2]), int(bool(to_rgb)), out.data_ptr(), _stream())
+    return out
+
+
+def scene_accumulate_(sums, logits, windows, size):
+    """sums (dense [C, H, W]) += the low-resolution logits [B, C, hl, wl] of the windows [(y1, x1), ...] of size (h, w), each resized to
+    (h, w) and added in place, window by window in index order: bit for bit resize_bilinear + window_accumulate_ per window"""
+    _dense(sums)
+    b, c, hl, wl = logits.shape
+    if sums.dim() != 3 or sums.shape[0] != c or b != len(windows):
+        raise ValueError(f'sums {tuple(sums.shape)} / logits {tuple(logits.shape)} / {len(windows)} windows do not match')
+    call('pfst_scene_accumulate', logits.data_ptr(), _bs(logits), b, c, hl, wl, _win_yx(windows), int(size[0]), int(size[1]),
+         sums.data_ptr(), sums.shape[1], sums.shape[2], _stream())
+    return sums
+
+
+def scene_finalize(sums, row_count, col_count, confidence=False, return_probs=False):
+    """sums [C, H, W] / (row_count[y] * col_count[x]) -> softmax -> first maximal class: (labels uint8 [H, W], confidence uint8 [H, W] =
+    rint(p_max * 255) or None, probabilities [C, H, W] or None), bit for bit window_normalize_ -> softmax_nchw -> argmax_nchw"""
+    _dense(sums)
+    c, h, w = sums.shape
+    I32 = torch.int32
+    if _dense(row_count, I32).numel() != h or _dense(col_count, I32).numel() != w:
+        raise ValueError('row_count / col_count must hold H / W entries')
+    dev = sums.device
+    lab = torch.empty(h, w, dtype=U8, device=dev)
+    conf = torch.empty(h, w, dtype=U8, device=dev) if confidence else None
+    probs = torch.empty(c, h, w, device=dev) if return_probs else None
+    call('pfst_scene_finalize', sums.data_ptr(), c, h, w, row_count.data_ptr(), col_count.data_ptr(), lab.data_ptr(), _p(conf), _p(probs),
+         _stream())
+    return lab, conf, probs
+
+
+def paint_labels(labels, palette, scene_u8=None, opacity=None):
+    """labels uint8 [H, W] through palette (uint8 [<= 256, 3], RGB) -> uint8 [H, W, 3] RGB; with a scene (uint8 [H, W, 3], BGR) and an opacity
+    in [0, 1] the blend of show_result, uint8(img * (1 - opacity) + colour * opacity) in double arithmetic: NumPy's bytes"""
+    _dense(labels, U8), _dense(palette, U8)
+    h, w = labels.shape
+    if palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256:
+        raise ValueError(f'palette must be [<= 256, 3], got {tuple(palette.shape)}')
+    if (scene_u8 is None) != (opacity is None):
+        raise ValueError('an overlay needs both the scene and an opacity')
+    keep = op = 0.0
+    if scene_u8 is not None:
+        if tuple(_dense(scene_u8, U8).shape) != (h, w, 3):
+            raise ValueError(f'scene {tuple(scene_u8.shape)} does not match labels {(h, w)}')
+        op = float(opacity)
+        if not 0.0 <= op <= 1.0:
+            raise ValueError(f'opacity must lie in [0, 1], got {opacity}')
+        keep = 1 - op                      # in double, as Python forms it in show_result
+    out = torch.empty(h, w, 3, dtype=U8, device=labels.device)
+    call('pfst_paint_labels', labels.data_ptr(), h, w, palette.data_ptr(), palette.shape[0], _p(scene_u8), keep, op, out.data_ptr(), _stream())
+    return out
+
+
 # ---------------------------------------------------------------- losses
 def ce_upsample_fwd(logits, label_u8, pix_weight=None, class_weight=None, ignore_index=255):
     """-> (lse [N,H,W], acc float64[4] = (weighted nll sum, #correct, #valid, #labels outside [0,C) that are not ignore_index))"""
