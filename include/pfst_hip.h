@@ -380,6 +380,25 @@ int pfst_scene_finalize(const float* sums, int C, int H, int W, const int* row_c
 int pfst_paint_labels(const unsigned char* label_u8, int H, int W, const unsigned char* palette_rgb, int colours, const unsigned char* scene_bgr,
                       double keep, double opacity, unsigned char* out_rgb, pfst_stream_t stream);
 
+/* ---- test-time augmentation on whole scenes (pfst_amd/scene.py predict_scene_tta): aug_test (:355-372) over slide_inference, the views of
+ * MultiScaleFlipAug with img_scale=None (test_time_aug.py:98-126).  scene_tta.hip. */
+/* out_u8 [Hr][Wr][3] = the bilinear resize of src_u8 [h][w][3] (pfst_amd.pipeline.resize_bilinear_u8 / pfst_cpu_resize_window_u8, bit for bit),
+ * written mirrored horizontally / vertically when asked (RandomFlip after Resize).  y_index / x_index: DEVICE int tables [2][Hr] / [2][Wr], the
+ * lower then the upper source index of every output row / column; y_frac / x_frac: device float tables [Hr] / [Wr], the weight of the upper
+ * index -- pipeline._src_index's, so the geometry has one definition (indices are clamped into the source).  Equal sizes: an exact copy. */
+int pfst_scene_resize_u8(const unsigned char* src_u8, int h, int w, const int* y_index, const float* y_frac, const int* x_index, const float* x_frac,
+                         int Hr, int Wr, int hflip, int vflip, unsigned char* out_u8, pfst_stream_t stream);
+/* one view in one pass: acc [C][H][W] = (accumulate ? acc : 0) + flip(softmax(resize(sums / count, (H, W)))), bit-identical to the chain
+ * pfst_window_normalize -> pfst_resize_bilinear (skipped when Hr x Wr = H x W) -> pfst_softmax_nchw -> pfst_flip_planes -> pfst_axpy_f32.  sums:
+ * the view's window sums [C][Hr][Wr]; its cover count at (y, x) is row_count[y] * col_count[x] (device int tables, all >= 1): neither a count
+ * plane nor a normalised copy of the sums is written.  C <= PFST_TTA_MAX_C (larger C: -1, the caller runs the chain). */
+int pfst_scene_tta_accumulate(const float* sums, int C, int Hr, int Wr, const int* row_count, const int* col_count, int hflip, int vflip, float* acc,
+                              int H, int W, int accumulate, pfst_stream_t stream);
+/* acc / views -> label_u8 [H][W], the first maximal class (+ conf_u8 = rint(p_max * 255), + probs [C][H][W] = acc / views; either may be NULL):
+ * bit-identical to pfst_div_scalar -> pfst_argmax_nchw.  Any C <= 255; acc is left as it is. */
+int pfst_scene_tta_finalize(const float* acc, int C, int H, int W, int views, unsigned char* label_u8, unsigned char* conf_u8, float* probs,
+                            pfst_stream_t stream);
+
 /* ---- fused bilinear-upsample + softmax cross-entropy + accuracy (decode_head.py:249-283,
  * cross_entropy_loss.py:45-65, accuracy.py:6-61).  logits are [N][C][h][w]; labels/weights [N][H][W].
  * acc[0] += sum_i w_i*cw[y_i]*nll_i (0 at ignore), acc[1] += #correct, acc[2] += #non-ignored, acc[3] += #labels that are neither

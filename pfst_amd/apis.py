@@ -6,7 +6,7 @@ import torch
 
 from . import hip_ops as ops
 from .config import Config
-from .scene import predict_scene
+from .scene import predict_scene, predict_scene_tta
 
 DEFAULT_WINDOW, DEFAULT_STRIDE = 1024, 512
 
@@ -77,9 +77,12 @@ def init_segmentor(config, checkpoint=None, device='cuda:0', revise_checkpoint_k
     return model
 
 
-def predict_image(model, img, window=None, stride=None, windows_per_batch=8, confidence=False, return_probs=False):
+def predict_image(model, img, window=None, stride=None, windows_per_batch=8, confidence=False, return_probs=False, ratios=None, flip=False,
+                  flip_direction='horizontal'):
     """img: a path or an H x W x 3 BGR uint8 array -> dict(scene, labels, confidence, probs, windows, batches, window): device tensors
-    (confidence / probs None unless asked for) and the window / batch counts.  The scene is predicted at its native resolution."""
+    (confidence / probs None unless asked for) and the window / batch counts.  The scene is predicted at its native resolution; with
+    `ratios` (floats that multiply the scene's size) and / or `flip` it is predicted with test-time augmentation, the probabilities of
+    every resized / mirrored view averaged at the scene's size (scene.predict_scene_tta; the dict then also holds views and view_windows)."""
     from .data import _read_image_bgr
     if isinstance(img, (str, bytes)) or hasattr(img, '__fspath__'):
         img = _read_image_bgr(img)
@@ -94,13 +97,18 @@ def predict_image(model, img, window=None, stride=None, windows_per_batch=8, con
     scene = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
     stats = {}
     with torch.no_grad():
-        labels, conf, probs = predict_scene(model, scene, norm, crop, step, windows_per_batch, confidence, return_probs, stats)
+        if ratios is None and not flip:
+            labels, conf, probs = predict_scene(model, scene, norm, crop, step, windows_per_batch, confidence, return_probs, stats)
+        else:
+            labels, conf, probs = predict_scene_tta(model, scene, norm, crop, step, [1.0] if ratios is None else ratios, flip, flip_direction,
+                                                    windows_per_batch, confidence, return_probs, stats)
     return dict(scene=scene, labels=labels, confidence=conf, probs=probs, **stats)
 
 
 def inference_segmentor(model, img, **options):
     """-> [labels]: a list holding the H x W uint8 label array of the image, as the reference returns a list (with confidence=True /
-    return_probs=True those arrays follow the labels).  options: window, stride, windows_per_batch, confidence, return_probs."""
+    return_probs=True those arrays follow the labels).  options: window, stride, windows_per_batch, confidence, return_probs, and for
+    test-time augmentation ratios, flip, flip_direction."""
     out = predict_image(model, img, **options)
     res = [out['labels'].cpu().numpy()]
     res += [out[k].cpu().numpy() for k in ('confidence', 'probs') if out[k] is not None]

@@ -1020,6 +1020,76 @@ def scene_finalize(sums, row_count, col_count, confidence=False, return_probs=Fa
     return lab, conf, probs
 
 
+_resize_tables = {}
+
+
+def _src_tables(n_out, n_in, dev):
+    """pipeline._src_index of one axis on the device, uploaded once per (sizes, device): (int32 [2, n_out] lower / upper source index,
+    float32 [n_out] weight of the upper one)"""
+    import numpy as np
+    from .pipeline import _src_index
+    key = (n_out, n_in, str(dev))
+    t = _resize_tables.get(key)
+    if t is None:
+        if len(_resize_tables) >= 32:
+            _resize_tables.clear()
+        lo, hi, f = _src_index(n_out, n_in)
+        # through pinned staging buffers of their own (h2d_small, one tag per table): the upload does not make the host wait for the stream
+        t = _resize_tables[key] = (h2d_small(torch.from_numpy(np.stack([lo, hi]).astype(np.int32)), dev, ('src_index', 'i') + key),
+                                   h2d_small(torch.from_numpy(np.ascontiguousarray(f)), dev, ('src_index', 'f') + key))
+    return t
+
+
+def scene_resize_u8(scene_u8, out_hw, hflip=False, vflip=False):
+    """device uint8 [h, w, 3] -> uint8 [Hr, Wr, 3]: pipeline.resize_bilinear_u8(scene, out_hw), mirrored horizontally / vertically when asked
+    (np.flip of it along axis 1 / 0), bit for bit; with equal sizes an exact (mirrored) copy"""
+    _dense(scene_u8, U8)
+    if scene_u8.dim() != 3 or scene_u8.shape[2] != 3:
+        raise ValueError(f'scene must be [H, W, 3], got {tuple(scene_u8.shape)}')
+    h, w = scene_u8.shape[:2]
+    hr, wr = int(out_hw[0]), int(out_hw[1])
+    if hr < 1 or wr < 1:
+        raise ValueError(f'resize to {out_hw}')
+    dev = scene_u8.device
+    yi, fy = _src_tables(hr, h, dev)
+    xi, fx = _src_tables(wr, w, dev)
+    out = torch.empty(hr, wr, 3, dtype=U8, device=dev)
+    call('pfst_scene_resize_u8', scene_u8.data_ptr(), h, w, yi.data_ptr(), fy.data_ptr(), xi.data_ptr(), fx.data_ptr(), hr, wr, int(bool(hflip)),
+         int(bool(vflip)), out.data_ptr(), _stream())
+    return out
+
+
+def scene_tta_accumulate_(acc, sums, row_count, col_count, hflip=False, vflip=False, accumulate=True):
+    """acc (dense [C, H, W]) = (acc if accumulate else 0) + flip(softmax(resize(sums / (row_count[y] * col_count[x]), (H, W)))), bit for bit
+    what window_normalize_ -> resize_bilinear (skipped between equal sizes) -> softmax_nchw -> flip_planes -> axpy_ computes from the view's
+    window sums [C, Hr, Wr]; C <= TTA_MAX_C"""
+    _dense(acc), _dense(sums)
+    if acc.dim() != 3 or sums.dim() != 3 or acc.shape[0] != sums.shape[0]:
+        raise ValueError(f'acc {tuple(acc.shape)} / sums {tuple(sums.shape)} do not match')
+    c, hr, wr = sums.shape
+    I32 = torch.int32
+    if _dense(row_count, I32).numel() != hr or _dense(col_count, I32).numel() != wr:
+        raise ValueError('row_count / col_count must hold the view\'s Hr / Wr entries')
+    call('pfst_scene_tta_accumulate', sums.data_ptr(), c, hr, wr, row_count.data_ptr(), col_count.data_ptr(), int(bool(hflip)), int(bool(vflip)),
+         acc.data_ptr(), acc.shape[1], acc.shape[2], int(bool(accumulate)), _stream())
+    return acc
+
+
+def scene_tta_finalize(acc, views, confidence=False, return_probs=False):
+    """acc [C, H, W] / views -> first maximal class: (labels uint8 [H, W], confidence uint8 [H, W] = rint(p_max * 255) or None, probabilities
+    [C, H, W] or None), bit for bit div_scalar_ -> argmax_nchw; acc is left as it is"""
+    _dense(acc)
+    if acc.dim() != 3:
+        raise ValueError(f'acc must be [C, H, W], got {tuple(acc.shape)}')
+    c, h, w = acc.shape
+    dev = acc.device
+    lab = torch.empty(h, w, dtype=U8, device=dev)
+    conf = torch.empty(h, w, dtype=U8, device=dev) if confidence else None
+    probs = torch.empty(c, h, w, device=dev) if return_probs else None
+    call('pfst_scene_tta_finalize', acc.data_ptr(), c, h, w, int(views), lab.data_ptr(), _p(conf), _p(probs), _stream())
+    return lab, conf, probs
+
+
 def paint_labels(labels, palette, scene_u8=None, opacity=None):
     """labels uint8 [H, W] through palette (uint8 [<= 256, 3], RGB) -> uint8 [H, W, 3] RGB; with a scene (uint8 [H, W, 3], BGR) and an opacity
     in [0, 1] the blend of show_result, uint8(img * (1 - opacity) + colour * opacity) in double arithmetic: NumPy's bytes"""
