@@ -444,8 +444,14 @@ int pfst_color_jitter(float* img, const float* params, const float* mean3, const
 int pfst_gaussian_blur(const float* x, float* tmp, float* y, const float* taps_y, int Ky, const float* taps_x, int Kx,
                        int N, int C, int H, int W, int reach, pfst_stream_t stream);
 
-/* ---- PFGSTLoss (pfgst_loss.py:44-234), kernel 3x3 ------------------------------------------------ */
-/* sim_type 0: sim[n][k][y][x] = cos(f[n][:,y,x], f[n][:,y+dy_k,x+dx_k]) (0 outside); norm[n][y][x] = |f|
+/* ---- PFGSTLoss (pfgst_loss.py:44-234), kernel K x K for ksize K in {3, 5, 7} ------------------------------------
+ * Tap order (nn.Unfold(K, dilation dil, padding r*dil)): k = (dy+r)*ksize + (dx+r), r = ksize/2, neighbour offset (dy*dil, dx*dil),
+ * dy, dx in [-r, r]; maps with taps are [N][ksize*ksize][H][W].  The mirror tap of k is ksize*ksize-1-k: pixel r is that tap of its
+ * k-neighbour r+D_k.  A neighbour in the zero-padding band has label 0 (a real class) and similarity against a zero vector.
+ * Every entry with a `ksize` argument refuses values outside {3, 5, 7}.
+ *
+ * Similarity map, 3x3 (the shipped configs: strip kernels for the cosine type on whole-row 256-pixel strips, generic kernels otherwise):
+ * sim_type 0: sim[n][k][y][x] = cos(f[n][:,y,x], f[n][:,y+dy_k,x+dx_k]) (0 outside); norm[n][y][x] = |f|
  * sim_type 1: sim = exp(-|f(neighbour) - f(centre)|^2 / sigma^2), the zero padding counting as f = 0 (pfgst_loss.py:199-201) */
 int pfst_sim_map(const float* feat, int N, int C, int H, int W, int dil, int sim_type, float sigma, float* sim, float* norm,
                  pfst_stream_t stream);
@@ -454,16 +460,22 @@ int pfst_sim_map_bwd(const float* feat, const float* sim, const float* norm, con
                      int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream);
 /* coef_ws: 10*N*H*W floats of scratch (per-pixel stencil coefficients) for the strip kernel of the cosine path; NULL selects the
  * generic kernel */
+/* Similarity map and adjoint, K x K, any map size: (16 + 2*r*dil)^2 halo tiles staged in LDS, so r*dil <= 37 */
+int pfst_sim_map_k(const float* feat, int N, int C, int H, int W, int ksize, int dil, int sim_type, float sigma, float* sim, float* norm,
+                   pfst_stream_t stream);
+/* coef_ws (required, both sim types): (ksize*ksize + 1)*N*H*W floats of scratch (per-pixel stencil coefficients) */
+int pfst_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int ksize,
+                       int dil, int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream);
 /* source statistics: sets (neighbour label == / != centre label, centre != 255) of src sims.
  * gt is full resolution [N][Hg][Wg] uint8, nearest-sampled to HxW.
  * loss_type 0 (mean_std): stats[0..5] = n_pos, sum_pos, sumsq_pos, n_neg, sum_neg, sumsq_neg
  * loss_type 1 / 2 (margin / margin2, pfgst_loss.py:116-131): stats[1] = sum relu(margin_pos - s)^e over positive pairs,
  *   stats[4] = sum relu(s - margin_neg)^e over negative pairs, e = loss_type */
-int pfst_src_sim_stats(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int dil, int loss_type,
+int pfst_src_sim_stats(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, int loss_type,
                        float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream);
 /* loss_type 0: losses[0..3] = -w*mean_pos, w*mean_neg, w*std_pos, w*std_neg; 1 / 2: losses[0..1] = w_pos*mean hinge_pos,
  * w_neg*mean hinge_neg (losses[2..3] = 0); gsim = d(sum of the losses)/d sim */
-int pfst_src_sim_grad(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int dil, int loss_type,
+int pfst_src_sim_grad(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, int loss_type,
                       float margin_pos, float margin_neg, const double* stats,
                       float w_pos, float w_neg, float w_pos_std, float w_neg_std, float* gsim, float* losses, const void* select, pfst_stream_t stream);
 /* src_perc (pfgst_loss.py:98-102: only the int(n * src_perc) smallest positive / largest negative similarities enter the source
@@ -471,55 +483,30 @@ int pfst_src_sim_grad(const float* sim, const unsigned char* gt, int N, int H, i
  * ties that lies inside the sorted prefix; pass the filled `select` buffer (pfst_src_sim_select_bytes() bytes, 8-byte aligned) to
  * pfst_src_sim_stats / pfst_src_sim_grad, or NULL for all pairs. */
 int pfst_src_sim_select_bytes(void);
-int pfst_src_sim_select(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int dil, double src_perc,
+int pfst_src_sim_select(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, double src_perc,
                         void* select, pfst_stream_t stream);
 /* prob[n][c][y][x] = softmax_c(logits[n][c][y*ds][x*ds]) (nearest down-scaling by ds) */
 int pfst_softmax_down(const float* logits, int N, int C, int h, int w, int ds, float* prob, int H, int W, pfst_stream_t stream);
-/* valid[n][y][x] = (gt != 255) && all 9 dilated neighbours un-mixed; count[0] = #valid */
-int pfst_trg_valid_mask(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int dil,
-                        unsigned char* valid, unsigned char* all9, unsigned long long* count, pfst_stream_t stream);
-/* top-k target losses (top_k = 0: all nine pairs, the reference's top_k=None); acc[0] += sum loc_pos, acc[1] += sum loc_neg
- * over valid pixels; gP[n][9][y][x] = d(w_pos*mean loc_pos + w_neg*mean loc_neg)/d cross_prob (0 when count <= 1) */
+/* valid = (gt != 255) && all ksize*ksize dilated neighbours inside the map and un-mixed; all_in = the second condition alone;
+ * count[0] = #valid */
+int pfst_trg_valid_mask(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                        unsigned char* valid, unsigned char* all_in, unsigned long long* count, pfst_stream_t stream);
+/* top-k target losses, 0 <= top_k <= ksize*ksize - 1 (0: all pairs, the reference's top_k=None); acc[0] += sum loc_pos,
+ * acc[1] += sum loc_neg over valid pixels; gP[n][k][y][x] = d(w_pos*mean loc_pos + w_neg*mean loc_neg)/d cross_prob (0 when
+ * count <= 1).  Ranks: stable descending similarity, the lower tap index first on ties; the top-(top_k+1) and bottom-top_k sets
+ * may overlap (2*top_k + 1 > ksize*ksize): a pair in both counts in both losses and both gradient terms.
+ * g_sim != NULL: also d(losses)/d ema_sim [N][ksize*ksize][H][W] -- needed only when the similarity has trainable inputs (proj_net) */
 int pfst_sim_topk_loss(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
-                       int N, int C, int H, int W, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc, float* g_sim, pfst_stream_t stream);
-/* g_sim != NULL: also d(losses)/d ema_sim [N][9][H][W] -- needed only when the similarity has trainable inputs (proj_net) */
+                       int N, int C, int H, int W, int ksize, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
+                       float* g_sim, pfst_stream_t stream);
 /* d logits[n][c][y*ds][x*ds] += softmax-backward( sum_k gP[k] * prob_c(neighbour k) ); unfold_grad != 0 (detach_unfold=False)
- * adds the gradient through the unfolded factor: coefficient gP[k][r] + gP[8-k][r+D_k] */
-int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, int C, int H, int W, int dil, int ds, int unfold_grad,
+ * adds the gradient through the unfolded factor: coefficient gP[k][r] + gP[ksize*ksize-1-k][r+D_k] */
+int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, int C, int H, int W, int ksize, int dil, int ds, int unfold_grad,
                         float* dlogits, int h, int w, pfst_stream_t stream);
-/* out[0] = w_pos*acc[0]/((top_k+1)*count), out[1] = w_neg*acc[1]/(top_k*count); top_k = 0: both /(9*count)  (zeros when count <= 1) */
-int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int top_k, float w_pos, float w_neg, float* out, pfst_stream_t stream);
-
-/* ---- PFGSTLoss, kernel K x K for ksize K in {3, 5, 7}: the entries above with `int ksize` before `dil`, the same semantics otherwise.
- * Tap order (nn.Unfold's): k = (dy+r)*ksize + (dx+r), r = ksize/2, neighbour offset (dy*dil, dx*dil), dy, dx in [-r, r]; maps with
- * taps are [N][ksize*ksize][H][W].  The similarity map and its adjoint stage (16 + 2*r*dil)^2 halo tiles in LDS: r*dil <= 37. */
-int pfst_sim_map_k(const float* feat, int N, int C, int H, int W, int ksize, int dil, int sim_type, float sigma, float* sim, float* norm,
-                   pfst_stream_t stream);
-/* coef_ws (required, both sim types): (ksize*ksize + 1)*N*H*W floats of scratch (per-pixel stencil coefficients) */
-int pfst_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int ksize,
-                       int dil, int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream);
-/* source pairs: centre label != 255; a neighbour in the zero-padding band has label 0 and similarity against a zero vector */
-int pfst_src_sim_stats_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, int loss_type,
-                         float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream);
-int pfst_src_sim_grad_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, int loss_type,
-                        float margin_pos, float margin_neg, const double* stats,
-                        float w_pos, float w_neg, float w_pos_std, float w_neg_std, float* gsim, float* losses, const void* select, pfst_stream_t stream);
-int pfst_src_sim_select_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil, double src_perc,
-                          void* select, pfst_stream_t stream);
-/* valid = (gt != 255) && all ksize*ksize dilated neighbours inside the map and un-mixed; all_in = the second condition alone */
-int pfst_trg_valid_mask_k(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
-                          unsigned char* valid, unsigned char* all_in, unsigned long long* count, pfst_stream_t stream);
-/* 0 <= top_k <= ksize*ksize - 1 (0: all pairs).  Ranks: stable descending similarity, the lower tap index first on ties; the
- * top-(top_k+1) and bottom-top_k sets may overlap (2*top_k + 1 > ksize*ksize): a pair in both counts in both losses */
-int pfst_sim_topk_loss_k(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
-                         int N, int C, int H, int W, int ksize, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
-                         float* g_sim, pfst_stream_t stream);
-/* unfold_grad: coefficient gP[k][r] + gP[ksize*ksize-1-k][r+D_k] */
-int pfst_cross_prob_bwd_k(const float* prob, const float* gP, int N, int C, int H, int W, int ksize, int dil, int ds, int unfold_grad,
-                          float* dlogits, int h, int w, pfst_stream_t stream);
-/* top_k = 0: both sums / (ksize*ksize*count) */
-int pfst_sim_loss_finalize_k(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg, float* out,
-                             pfst_stream_t stream);
+/* out[0] = w_pos*acc[0]/((top_k+1)*count), out[1] = w_neg*acc[1]/(top_k*count); top_k = 0: both /(ksize*ksize*count)  (zeros when
+ * count <= 1); top_k as for pfst_sim_topk_loss */
+int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg, float* out,
+                           pfst_stream_t stream);
 
 /* ---- EMA teacher + AdamW + SGD on flat parameter arenas (pfgst.py:105-127, torch.optim.AdamW / SGD) ------ */
 int pfst_ema_update(float* teacher, const float* student, long long n, float alpha, pfst_stream_t stream);

@@ -1,11 +1,13 @@
 // PFGSTLoss: local pseudo-feature similarity losses, fused so that the reference's unfold tensors
 // (b x 512 x 9 x H x W, 302 MB per image per call at S=1024) never exist.
-// Reference: rsiseg/models/losses/pfgst_loss.py:44-234: kernel 3, dilation d, cross_prob_type 'trg'; the shipped options
-// (sim_type 'cosine', detach_unfold=True, src_loss_type 'mean_std', top_k, downscale 0.5) and the variants reachable from
-// the same configs: sim_type 'gaussian' (:199-201), src_loss_type 'margin' / 'margin2' (:116-131), detach_unfold=False
-// (:151-152), top_k=None (:229-231), downscale None / 1.
-// Neighbour index k = ty*3+tx, offset ((ty-1)*d, (tx-1)*d) -- the order nn.Unfold produces.
-// kernel_size 5 / 7 and top_k > 4: the templated K x K kernels and the `_k` entries at the end of the file.
+// Reference: rsiseg/models/losses/pfgst_loss.py:44-234: kernel K in {3, 5, 7}, dilation d, cross_prob_type 'trg'; the shipped
+// options (kernel 3, sim_type 'cosine', detach_unfold=True, src_loss_type 'mean_std', top_k, downscale 0.5) and the variants
+// reachable from the same configs: sim_type 'gaussian' (:199-201), src_loss_type 'margin' / 'margin2' (:116-131),
+// detach_unfold=False (:151-152), top_k=None (:229-231) and up to K^2 - 1, downscale None / 1.
+// Neighbour index k = (dy+r)*K + (dx+r), r = K/2, offset (dy*d, dx*d), dy, dx in [-r, r] -- the order nn.Unfold(K, dilation d,
+// padding r*d) produces; the mirror tap of k is K^2-1-k.
+// Layout: the similarity map and its adjoint have two implementations (3x3 strip / generic kernels behind pfst_sim_map[_bwd], K x K
+// halo-tile kernels behind pfst_sim_map[_bwd]_k); everything that works on labels and taps is ONE `template <int K>` kernel per job.
 #include "common.h"
 #include <stdlib.h>
 #include "../../include/pfst_hip.h"
@@ -266,35 +268,47 @@ __global__ __launch_bounds__(64 * NW) void sim_map_cos_q_kernel(const float* __r
 }
 
 // adjoint, same data movement: dF(r) = B(r) F(r) + sum_k A_k(r) F(r + D_k).  The per-pixel coefficients (sim_map_bwd_kernel's
-// prologue) are computed once by sim_bwd_coef_kernel into coef[n][10][HW] = (A_0..A_8 with A_4 = 0, B); the stencil kernel then
-// reads them as ten aligned float4 and streams the channels: three 16-byte loads + one 16-byte store each.
+// prologue) are computed once by sim_bwd_coef_kernel<3, false> into coef[n][10][HW] = (A_0..A_8 with A_4 = 0, B); the stencil kernel
+// then reads them as ten aligned float4 and streams the channels: three 16-byte loads + one 16-byte store each.
+// ---- adjoint coefficients, K x K taps and both similarity types (also the prologue of the halo-tile adjoint below):
+// coef[n][K^2 + 1][HW] = (A_0 .. A_{K^2-1} with A_centre = 0, B).  Pixel r is the mirror tap K^2-1-k of its k-neighbour r + D_k.
 // grid: (blocks over H*W, N)
+template <int K, bool GAUSS>
 __global__ __launch_bounds__(256) void sim_bwd_coef_kernel(const float* __restrict__ sim, const float* __restrict__ norm,
-                                                           const float* __restrict__ gsim, int H, int W, int dil, float* __restrict__ coef) {
-  const int n = blockIdx.y;
-  const int HW = H * W;
-  const float* sp = sim + (i64)n * 9 * HW;
-  const float* gp = gsim + (i64)n * 9 * HW;
+                                                           const float* __restrict__ gsim, int H, int W, int dil, float inv_sigma2,
+                                                           float* __restrict__ coef) {
+  constexpr int R = K / 2, KK = K * K;
+  const int n = blockIdx.y, HW = H * W;
+  const float* sp = sim + (i64)n * KK * HW;
+  const float* gp = gsim + (i64)n * KK * HW;
   const float* np_ = norm + (i64)n * HW;
-  float* cp = coef + (i64)n * 10 * HW;
+  float* cp = coef + (i64)n * (KK + 1) * HW;
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
     const int y = p / W, x = p - y * W;
-    const float nr = fmaxf(np_[p], COS_EPS);
+    const float nr = GAUSS ? 1.f : fmaxf(np_[p], COS_EPS);
     float b = 0.f;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int sy = y + (k / 3 - 1) * dil, sx = x + (k % 3 - 1) * dil;
-      const bool ok = sy >= 0 && sy < H && sx >= 0 && sx < W && k != 4;
+    for (int k = 0; k < KK; ++k) {
+      const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
+      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
       float a = 0.f;
-      if (ok) {
-        const int q = sy * W + sx;
-        const float g1 = gp[(i64)k * HW + p], g2 = gp[(i64)(8 - k) * HW + q];
-        a = (g1 + g2) / (nr * fmaxf(np_[q], COS_EPS));
-        b -= g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)(8 - k) * HW + q];
+      if (in && k != KK / 2) {
+        const int q = sy * W + sx, m = KK - 1 - k;
+        const float g1 = gp[(i64)k * HW + p], g2 = gp[(i64)m * HW + q];
+        if (GAUSS) {
+          const float c = -2.f * inv_sigma2 * (g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)m * HW + q]);
+          a = -c;
+          b += c;
+        } else {
+          a = (g1 + g2) / (nr * fmaxf(np_[q], COS_EPS));
+          b -= g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)m * HW + q];
+        }
+      } else if (GAUSS && !in) {
+        b += -2.f * inv_sigma2 * gp[(i64)k * HW + p] * sp[(i64)k * HW + p];    // neighbour is the constant 0: centre side only
       }
       cp[(i64)k * HW + p] = a;
     }
-    cp[(i64)9 * HW + p] = b / (nr * nr);
+    cp[(i64)KK * HW + p] = GAUSS ? b : b / (nr * nr);
   }
 }
 
@@ -347,582 +361,9 @@ inline bool simq_ok(const void* a, const void* b, int C, int H, int W, int dil) 
          ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
 }
 
-// ---- source statistics.  grid: (blocks over H*W, N)
-__device__ __forceinline__ int src_pair_class(const unsigned char* __restrict__ gt, int Hg, int Wg, float sgy, float sgx, int H, int W,
-                                               int y, int x, int k, int dil, int ctr) {
-  // returns 0 = skip, 1 = positive pair, 2 = negative pair
-  const int sy = y + (k / 3 - 1) * dil, sx = x + (k % 3 - 1) * dil;
-  int nb = 0;  // nn.Unfold zero padding: label 0 outside
-  if (sy >= 0 && sy < H && sx >= 0 && sx < W) nb = gt[(i64)nearest_src(sy, sgy, Hg) * Wg + nearest_src(sx, sgx, Wg)];
-  return nb == ctr ? 1 : 2;
-}
-
-// ---- src_perc (pfgst_loss.py:98-102): only the hardest fraction of the source pairs enters the source losses -- the smallest
-// positive and the largest negative similarities: `sorted[:int(n * src_perc)]`.  A sorted prefix is {s < t} plus some of the ties
-// {s == t}, t the K-th smallest value, so no sort is needed: an exact radix select (4 passes of 8 bits over order-preserving
-// integer keys) finds t and the number of ties inside the prefix; ties share that number equally (they are equal values, so the
-// losses are the reference's; only the split of the gradient among EXACTLY equal similarities is even instead of by sort position).
-// Negative pairs use the complemented key (descending order).
-struct SrcSel {                       // one per set (0: positive pairs, 1: negative pairs)
-  unsigned int prefix;                // key bits fixed so far; after the last pass: key of the K-th element
-  unsigned int shift;                 // bit position of the digit the next histogram pass resolves (24, 16, 8, 0)
-  unsigned long long rank;            // 1-based rank of the wanted element among the keys matching `prefix`
-  unsigned long long K;               // int(n * src_perc)
-  float w_tie;                        // weight of the elements whose key == prefix (ties inside the prefix / all ties)
-  int done;
-};
-__device__ __forceinline__ unsigned int order_key(float v, bool descending) {
-  const unsigned int u = __float_as_uint(v);
-  const unsigned int k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return descending ? ~k : k;
-}
-__device__ __forceinline__ float sel_weight(const SrcSel* __restrict__ sel, int set, float v) {
-  if (!sel) return 1.f;
-  const unsigned int k = order_key(v, set == 1);
-  return k < sel[set].prefix ? 1.f : (k == sel[set].prefix ? sel[set].w_tie : 0.f);
-}
-
-// grid: (blocks over H*W, N): histogram of the current digit of the keys matching the prefix
-__global__ __launch_bounds__(256) void src_sel_hist_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
-                                                           int Hg, int Wg, int dil, const SrcSel* __restrict__ sel, unsigned int* __restrict__ hist) {
-  __shared__ unsigned int sh[2 * 256];
-  sh[threadIdx.x] = 0; sh[256 + threadIdx.x] = 0;
-  __syncthreads();
-  const int n = blockIdx.y, HW = H * W;
-  const unsigned char* g = gt + (i64)n * Hg * Wg;
-  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
-  const unsigned int shift0 = sel[0].shift, shift1 = sel[1].shift;
-  // keys match when their bits ABOVE the current digit equal the prefix (first pass: shift = 24, nothing fixed yet)
-  const unsigned int hi0 = shift0 >= 24 ? 0u : (0xFFFFFFFFu << (shift0 + 8)), hi1 = shift1 >= 24 ? 0u : (0xFFFFFFFFu << (shift1 + 8));
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
-    if (ctr == 255) continue;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int cls = src_pair_class(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
-      const float v = sim[((i64)n * 9 + k) * HW + p];
-      if (cls == 1) {
-        const unsigned int key = order_key(v, false);
-        if (((key ^ sel[0].prefix) & hi0) == 0) atomicAdd(&sh[(key >> shift0) & 255u], 1u);
-      } else {
-        const unsigned int key = order_key(v, true);
-        if (((key ^ sel[1].prefix) & hi1) == 0) atomicAdd(&sh[256 + ((key >> shift1) & 255u)], 1u);
-      }
-    }
-  }
-  __syncthreads();
-  if (sh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], sh[threadIdx.x]);
-  if (sh[256 + threadIdx.x]) atomicAdd(&hist[256 + threadIdx.x], sh[256 + threadIdx.x]);
-}
-
-// one block, 2 threads used: resolve the digit, advance the state, clear the histogram
-// first: 2 = initialise the state (before the first histogram), 1 = first digit (also fixes K from the set size), 0 = later digits
-__global__ void src_sel_scan_kernel(SrcSel* __restrict__ sel, unsigned int* __restrict__ hist, double perc, int first) {
-  const int set = threadIdx.x;
-  if (first == 2) {
-    if (set < 2) {
-      sel[set].prefix = 0; sel[set].shift = 24; sel[set].rank = 0; sel[set].K = 0; sel[set].w_tie = 0.f; sel[set].done = 0;
-    }
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) hist[i] = 0;
-    return;
-  }
-  if (set < 2) {
-    SrcSel& st = sel[set];
-    unsigned int* h = hist + 256 * set;
-    if (first) {
-      unsigned long long n = 0;
-      for (int d = 0; d < 256; ++d) n += h[d];
-      st.K = (unsigned long long)((double)n * perc);         // int(n * src_perc): truncation of the double product
-      st.rank = st.K;
-      st.prefix = 0;
-      st.done = st.K == 0;
-      st.w_tie = 0.f;                                          // K == 0: nothing selected (no key is below prefix 0)
-    }
-    if (!st.done) {
-      unsigned long long cum = 0;
-      int d = 0;
-      for (; d < 256; ++d) {
-        if (cum + h[d] >= st.rank) break;
-        cum += h[d];
-      }
-      st.prefix |= (unsigned int)d << st.shift;
-      st.rank -= cum;
-      if (st.shift == 0) {
-        st.w_tie = (float)((double)st.rank / (double)h[d]);   // `rank` of the h[d] ties lie inside the sorted prefix
-        st.done = 1;
-      }
-    }
-    st.shift = st.shift >= 8 ? st.shift - 8 : 0;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 512; i += blockDim.x) hist[i] = 0;
-}
-
-// loss_type 0: count / sum / sum of squares (mean & unbiased std, :107-115); 1 / 2: count / sum of relu(m0 - s)^e for positive
-// pairs and relu(s - m1)^e for negative pairs, e = loss_type (:116-131).
-__global__ __launch_bounds__(256) void src_stats_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
-                                                        int Hg, int Wg, int dil, int loss_type, float m0, float m1,
-                                                        double* __restrict__ stats, const SrcSel* __restrict__ sel,
-                                                        double* __restrict__ det_part = nullptr) {
-  // det_part != NULL (deterministic mode, api.cpp): this block's six sums go to slot blockIdx.y * gridDim.x + blockIdx.x of det_part[slots][6]
-  // instead of being added atomically into stats; src_stats_det_sum_kernel adds the slots in index order
-  __shared__ double sm[16];
-  const int n = blockIdx.y, HW = H * W;
-  const unsigned char* g = gt + (i64)n * Hg * Wg;
-  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
-  double a[6] = {0, 0, 0, 0, 0, 0};
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
-    if (ctr == 255) continue;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int cls = src_pair_class(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
-      const float sv = sim[((i64)n * 9 + k) * HW + p];
-      const double s = (double)sv;
-      const double wt = (double)sel_weight(sel, cls == 1 ? 0 : 1, sv);       // src_perc: 1 inside the kept prefix, 0 outside
-      const int o = cls == 1 ? 0 : 3;
-      if (loss_type == 0) {
-        a[o] += wt; a[o + 1] += wt * s; a[o + 2] += wt * s * s;
-      } else {
-        const double h = cls == 1 ? fmax((double)m0 - s, 0.0) : fmax(s - (double)m1, 0.0);
-        a[o] += wt; a[o + 1] += wt * (loss_type == 1 ? h : h * h);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const double r = block_sum_d(a[i], sm);
-    if (threadIdx.x == 0) {
-      if (det_part) det_part[((i64)blockIdx.y * gridDim.x + blockIdx.x) * 6 + i] = r;
-      else if (r != 0.0) atomicAdd(&stats[i], r);
-    }
-  }
-}
-__global__ void src_stats_det_sum_kernel(const double* __restrict__ part, int T, double* __restrict__ stats) {
-  const int i = threadIdx.x;
-  if (i >= 6) return;
-  double a = 0.0;
-  for (int k = 0; k < T; ++k) a += part[(i64)k * 6 + i];
-  stats[i] = a;
-}
-
-struct SrcMoments { double n, mean, std; };
-__device__ __forceinline__ SrcMoments moments(const double* st) {
-  SrcMoments m;
-  m.n = st[0];
-  m.mean = st[0] > 0 ? st[1] / st[0] : 0.0;
-  const double var = st[0] > 1 ? (st[2] - st[1] * st[1] / st[0]) / (st[0] - 1.0) : 0.0;
-  m.std = var > 0 ? sqrt(var) : 0.0;
-  return m;
-}
-
-__global__ __launch_bounds__(256) void src_grad_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
-                                                       int Hg, int Wg, int dil, int loss_type, float m0, float m1,
-                                                       const double* __restrict__ stats, float w_pos,
-                                                       float w_neg, float w_pos_std, float w_neg_std, float* __restrict__ gsim,
-                                                       float* __restrict__ losses, const SrcSel* __restrict__ sel) {
-  const int n = blockIdx.y, HW = H * W;
-  const unsigned char* g = gt + (i64)n * Hg * Wg;
-  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
-  if (loss_type != 0) {       // hinge losses: mean over the pairs of relu(.)^e; d/ds = -/+ e relu(.)^(e-1) w / n
-    const double np = stats[0], nn = stats[3];
-    if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
-      losses[0] = np > 0 ? (float)((double)w_pos * stats[1] / np) : 0.f;     // (an empty set gives NaN in the reference)
-      losses[1] = nn > 0 ? (float)((double)w_neg * stats[4] / nn) : 0.f;
-      losses[2] = 0.f;
-      losses[3] = 0.f;
-    }
-    const double cp = np > 0 ? (double)w_pos / np : 0.0, cn = nn > 0 ? (double)w_neg / nn : 0.0;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-      const int y = p / W, x = p - y * W;
-      const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const i64 o = ((i64)n * 9 + k) * HW + p;
-        float gr = 0.f;
-        if (ctr != 255) {
-          const int cls = src_pair_class(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
-          const double s = (double)sim[o];
-          const double h = cls == 1 ? (double)m0 - s : s - (double)m1;
-          if (h > 0.0) gr = (float)((cls == 1 ? -cp : cn) * (loss_type == 1 ? 1.0 : 2.0 * h)) * sel_weight(sel, cls == 1 ? 0 : 1, sim[o]);
-        }
-        gsim[o] = gr;
-      }
-    }
-    return;
-  }
-  const SrcMoments mp = moments(stats), mn = moments(stats + 3);
-  if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
-    losses[0] = (float)(-mp.mean * w_pos);
-    losses[1] = (float)(mn.mean * w_neg);
-    losses[2] = (float)(mp.std * w_pos_std);
-    losses[3] = (float)(mn.std * w_neg_std);
-  }
-  // d(-w mean)/ds = -w/n ; d(w std)/ds = w (s-mean)/((n-1) std)
-  const double pa = mp.n > 0 ? -(double)w_pos / mp.n : 0.0;
-  const double pb = (mp.n > 1 && mp.std > 0) ? (double)w_pos_std / ((mp.n - 1.0) * mp.std) : 0.0;
-  const double na = mn.n > 0 ? (double)w_neg / mn.n : 0.0;
-  const double nb = (mn.n > 1 && mn.std > 0) ? (double)w_neg_std / ((mn.n - 1.0) * mn.std) : 0.0;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const i64 o = ((i64)n * 9 + k) * HW + p;
-      float gr = 0.f;
-      if (ctr != 255) {
-        const int cls = src_pair_class(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
-        const double s = (double)sim[o];
-        gr = (cls == 1 ? (float)(pa + pb * (s - mp.mean)) : (float)(na + nb * (s - mn.mean))) * sel_weight(sel, cls == 1 ? 0 : 1, sim[o]);
-      }
-      gsim[o] = gr;
-    }
-  }
-}
-
-// ---- softmax of the nearest-down-scaled student logits.  grid: (blocks over H*W, N)
-__global__ void softmax_down_kernel(const float* __restrict__ logits, int C, int h, int w, int ds, float* __restrict__ prob, int H, int W) {
-  const int n = blockIdx.y, HW = H * W;
-  const float* lp = logits + (i64)n * C * h * w;
-  float* pp = prob + (i64)n * C * HW;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    const int so = (y * ds) * w + x * ds;
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lp[(i64)c * h * w + so]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(lp[(i64)c * h * w + so] - mx);
-    const float inv = 1.f / se;
-    for (int c = 0; c < C; ++c) pp[(i64)c * HW + p] = expf(lp[(i64)c * h * w + so] - mx) * inv;
-  }
-}
-
-// ---- target validity: centre label != 255 and all nine dilated neighbours un-mixed (and inside the map)
-__global__ __launch_bounds__(256) void trg_valid_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ mix,
-                                                        int H, int W, int Hg, int Wg, int dil, unsigned char* __restrict__ valid,
-                                                        unsigned char* __restrict__ all9, unsigned long long* __restrict__ count) {
-  __shared__ double sm[16];
-  const int n = blockIdx.y, HW = H * W;
-  const unsigned char* g = gt + (i64)n * Hg * Wg;
-  const unsigned char* m = mix + (i64)n * Hg * Wg;
-  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
-  double cnt = 0.0;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    bool all = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int sy = y + (k / 3 - 1) * dil, sx = x + (k % 3 - 1) * dil;
-      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
-      all = all && in && (m[(i64)nearest_src(in ? sy : 0, sgy, Hg) * Wg + nearest_src(in ? sx : 0, sgx, Wg)] == 0);
-    }
-    const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
-    const bool v = all && ctr != 255;
-    valid[(i64)n * HW + p] = v;
-    if (all9) all9[(i64)n * HW + p] = all;
-    cnt += v ? 1.0 : 0.0;
-  }
-  cnt = block_sum_d(cnt, sm);
-  if (threadIdx.x == 0 && cnt > 0.0) atomicAdd(count, (unsigned long long)cnt);
-}
-
-// ---- top-k target losses.  One thread per pixel: 9-element sort in registers.
-__global__ __launch_bounds__(256) void topk_loss_kernel(const float* __restrict__ ema_sim, const float* __restrict__ prob,
-                                                        const unsigned char* __restrict__ valid, const unsigned long long* __restrict__ count,
-                                                        int C, int H, int W, int dil, int top_k, float w_pos, float w_neg,
-                                                        float* __restrict__ gP, double* __restrict__ acc, float* __restrict__ gS) {
-  __shared__ double sm[16];
-  const int n = blockIdx.y, HW = H * W;
-  const double cnt = (double)count[0];
-  const bool all_pairs = top_k == 0;          // top_k=None in the reference: every one of the 9 pairs, both losses (:229-231)
-  const float cpos = cnt > 1.0 ? (float)((double)w_pos / (cnt * (all_pairs ? 9 : top_k + 1))) : 0.f;
-  const float cneg = cnt > 1.0 ? (float)((double)w_neg / (cnt * (all_pairs ? 9 : top_k))) : 0.f;
-  const float* pp = prob + (i64)n * C * HW;
-  double spos = 0.0, sneg = 0.0;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const i64 base = (i64)n * 9 * HW + p;
-    if (!valid[(i64)n * HW + p]) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        gP[base + (i64)k * HW] = 0.f;
-        if (gS) gS[base + (i64)k * HW] = 0.f;
-      }
-      continue;
-    }
-    const int y = p / W, x = p - y * W;
-    float s[9], P[9];
-    int id[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      s[k] = ema_sim[base + (i64)k * HW];
-      id[k] = k;
-      const int sy = y + (k / 3 - 1) * dil, sx = x + (k % 3 - 1) * dil;  // always inside for valid pixels
-      const int q = sy * W + sx;
-      float d = 0.f;
-      for (int c = 0; c < C; ++c) d = fmaf(pp[(i64)c * HW + p], pp[(i64)c * HW + q], d);
-      P[k] = d;
-    }
-    if (all_pairs) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        spos += (double)(-s[k] * P[k]);
-        sneg += (double)(-(1.f - s[k]) * (1.f - P[k]));
-        gP[base + (i64)k * HW] = -s[k] * cpos + (1.f - s[k]) * cneg;
-        if (gS) gS[base + (i64)k * HW] = -P[k] * cpos + (1.f - P[k]) * cneg;     // d/d sim: the teacher side (proj_net's weights)
-      }
-      continue;
-    }
-    // stable insertion sort, descending similarity (ties keep the lower index first)
-#pragma unroll
-    for (int i = 1; i < 9; ++i) {
-#pragma unroll
-      for (int j = i; j > 0; --j) {
-        if (s[j] > s[j - 1]) {
-          const float ts = s[j]; s[j] = s[j - 1]; s[j - 1] = ts;
-          const float tp = P[j]; P[j] = P[j - 1]; P[j - 1] = tp;
-          const int ti = id[j]; id[j] = id[j - 1]; id[j - 1] = ti;
-        }
-      }
-    }
-    float g[9], gs[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { g[k] = 0.f; gs[k] = 0.f; }
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      float gj = 0.f, gsj = 0.f;
-      if (j <= top_k) {            // top-(k+1) largest: loc_pos = -sim * P
-        spos += (double)(-s[j] * P[j]);
-        gj = -s[j] * cpos;
-        gsj = -P[j] * cpos;
-      } else if (j >= 9 - top_k) { // top-k smallest: loc_neg = -(1-sim) * (1-P)
-        sneg += (double)(-(1.f - s[j]) * (1.f - P[j]));
-        gj = (1.f - s[j]) * cneg;
-        gsj = (1.f - P[j]) * cneg;
-      }
-#pragma unroll
-      for (int k = 0; k < 9; ++k) if (id[j] == k) { g[k] = gj; gs[k] = gsj; }
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      gP[base + (i64)k * HW] = g[k];
-      if (gS) gS[base + (i64)k * HW] = gs[k];
-    }
-  }
-  spos = block_sum_d(spos, sm);
-  sneg = block_sum_d(sneg, sm);
-  if (threadIdx.x == 0) {
-    if (spos != 0.0) atomicAdd(&acc[0], spos);
-    if (sneg != 0.0) atomicAdd(&acc[1], sneg);
-  }
-}
-
-// ---- gradient of the cross-probabilities P_k(r) = sum_c p_c(r) p_c(r+D_k) into the (full 1/4-res) student logits.
-// detach_unfold=True: only the centre factor p_c(r) carries gradient.  unfold_grad (detach_unfold=False): the unfolded
-// factor does too -- pixel r is the k-neighbour of r+D_{8-k}, so its coefficient gains gP[8-k, r+D_k] (gather form, no atomics).
-__global__ __launch_bounds__(256) void cross_prob_bwd_kernel(const float* __restrict__ prob, const float* __restrict__ gP, int C, int H,
-                                                             int W, int dil, int ds, int unfold_grad, float* __restrict__ dlogits, int h, int w) {
-  const int n = blockIdx.y, HW = H * W;
-  const float* pp = prob + (i64)n * C * HW;
-  float* dl = dlogits + (i64)n * C * h * w;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    float g[9];
-    int off[9];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      g[k] = gP[((i64)n * 9 + k) * HW + p];
-      const int sy = y + (k / 3 - 1) * dil, sx = x + (k % 3 - 1) * dil;
-      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
-      off[k] = in ? sy * W + sx : -1;
-      if (unfold_grad && in) g[k] += gP[((i64)n * 9 + (8 - k)) * HW + off[k]];
-      any = any || g[k] != 0.f;
-    }
-    if (!any) continue;
-    float dot = 0.f;  // sum_j p_j * dprob_j
-    for (int c = 0; c < C; ++c) {
-      float d = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) if (off[k] >= 0) d = fmaf(g[k], pp[(i64)c * HW + off[k]], d);
-      dot = fmaf(pp[(i64)c * HW + p], d, dot);
-    }
-    const int so = (y * ds) * w + x * ds;
-    for (int c = 0; c < C; ++c) {
-      float d = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) if (off[k] >= 0) d = fmaf(g[k], pp[(i64)c * HW + off[k]], d);
-      dl[(i64)c * h * w + so] += pp[(i64)c * HW + p] * (d - dot);
-    }
-  }
-}
-
-__global__ void sim_loss_finalize_kernel(const double* __restrict__ acc, const unsigned long long* __restrict__ count, int top_k,
-                                         float w_pos, float w_neg, float* __restrict__ out) {
-  const double cnt = (double)count[0];
-  out[0] = cnt > 1.0 ? (float)((double)w_pos * acc[0] / (cnt * (top_k == 0 ? 9 : top_k + 1))) : 0.f;
-  out[1] = cnt > 1.0 ? (float)((double)w_neg * acc[1] / (cnt * (top_k == 0 ? 9 : top_k))) : 0.f;
-}
-
-inline int px_blocks(i64 n) {
-  i64 g = (n + 255) / 256;
-  if (g > 4096) g = 4096;
-  return g < 1 ? 1 : (int)g;
-}
-
-}  // namespace
-
-extern "C" int pfst_sim_map(const float* feat, int N, int C, int H, int W, int dil, int sim_type, float sigma, float* sim, float* norm,
-                            pfst_stream_t stream) {
-  PFST_CHECK_ARG(feat && sim && norm && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
-  PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
-  const dim3 grid(px_blocks((i64)H * W), N);
-  if (sim_type == 0 && simq_ok(feat, sim, C, H, W, dil) && (reinterpret_cast<uintptr_t>(norm) & 15) == 0) {
-    const dim3 gq((unsigned)(((i64)H * W) / 256), N);
-    const size_t lds = 4 * SIMQ_VALS * 64 * sizeof(float);
-    if (C % 8 == 0 && C >= 64) {                   // 8 channel slices per strip: 16 waves per CU at the BASELINE shape
-      if (dil == 1) hipLaunchKernelGGL((sim_map_cos_q_kernel<1, 8>), gq, dim3(512), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
-      else hipLaunchKernelGGL((sim_map_cos_q_kernel<2, 8>), gq, dim3(512), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
-    } else {
-      if (dil == 1) hipLaunchKernelGGL((sim_map_cos_q_kernel<1, 4>), gq, dim3(256), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
-      else hipLaunchKernelGGL((sim_map_cos_q_kernel<2, 4>), gq, dim3(256), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
-    }
-  } else if (sim_type == 1)
-    hipLaunchKernelGGL(sim_map_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, feat, C, H, W, dil, 1.f / (sigma * sigma), sim, norm);
-  else
-    hipLaunchKernelGGL(sim_map_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, feat, C, H, W, dil, 0.f, sim, norm);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_sim_map_bwd(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int dil,
-                                int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream) {
-  PFST_CHECK_ARG(feat && sim && norm && gsim && dfeat && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
-  PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
-  const dim3 grid(px_blocks((i64)H * W), N);
-  if (sim_type == 0 && coef_ws && simq_ok(feat, dfeat, C, H, W, dil) && (reinterpret_cast<uintptr_t>(coef_ws) & 15) == 0) {
-    PFST_CHECK_ARG(coef_ws != nullptr);
-    hipLaunchKernelGGL(sim_bwd_coef_kernel, grid, dim3(256), 0, (hipStream_t)stream, sim, norm, gsim, H, W, dil, coef_ws);
-    const int cpw = 16;                                   // channels per wave
-    const dim3 gq((unsigned)(((i64)H * W) / 256), cdiv(C, 4 * cpw), N);
-    if (dil == 1) hipLaunchKernelGGL(sim_map_bwd_cos_q_kernel<1>, gq, dim3(256), 0, (hipStream_t)stream, feat, coef_ws, C, H, W, cpw, dfeat, accumulate);
-    else hipLaunchKernelGGL(sim_map_bwd_cos_q_kernel<2>, gq, dim3(256), 0, (hipStream_t)stream, feat, coef_ws, C, H, W, cpw, dfeat, accumulate);
-  } else if (sim_type == 1)
-    hipLaunchKernelGGL(sim_map_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, feat, sim, norm, gsim, C, H, W, dil,
-                       1.f / (sigma * sigma), dfeat, accumulate);
-  else
-    hipLaunchKernelGGL(sim_map_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, feat, sim, norm, gsim, C, H, W, dil, 0.f, dfeat,
-                       accumulate);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_src_sim_stats(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int dil, int loss_type,
-                                  float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream) {
-  PFST_CHECK_ARG(sim && gt && stats && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1);
-  PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(stats, 0, 6 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  const int gxs = px_blocks((i64)H * W);
-  double* det = nullptr;
-  if (pfst_deterministic()) {
-    det = static_cast<double*>(pfst_det_scratch((size_t)gxs * N * 6 * sizeof(double), s));
-    PFST_CHECK_DET(det != nullptr);
-  }
-  hipLaunchKernelGGL(src_stats_kernel, dim3(gxs, N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, loss_type, margin_pos,
-                     margin_neg, stats, reinterpret_cast<const SrcSel*>(select), det);
-  if (det) hipLaunchKernelGGL(src_stats_det_sum_kernel, dim3(1), dim3(64), 0, s, det, gxs * N, stats);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_src_sim_grad(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int dil, int loss_type,
-                                 float margin_pos, float margin_neg, const double* stats,
-                                 float w_pos, float w_neg, float w_pos_std, float w_neg_std, float* gsim, float* losses,
-                                 const void* select, pfst_stream_t stream) {
-  PFST_CHECK_ARG(sim && gt && stats && gsim && losses && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1);
-  PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
-  hipLaunchKernelGGL(src_grad_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, sim, gt, H, W, Hg, Wg, dil,
-                     loss_type, margin_pos, margin_neg, stats, w_pos, w_neg, w_pos_std, w_neg_std, gsim, losses,
-                     reinterpret_cast<const SrcSel*>(select));
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_src_sim_select_bytes(void) { return (int)(2 * sizeof(SrcSel) + 512 * sizeof(unsigned int)); }
-
-extern "C" int pfst_src_sim_select(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int dil, double src_perc,
-                                   void* select, pfst_stream_t stream) {
-  PFST_CHECK_ARG(sim && gt && select && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1);
-  PFST_CHECK_ARG(src_perc >= 0.0 && src_perc <= 1.0 && (reinterpret_cast<uintptr_t>(select) & 7) == 0);
-  hipStream_t s = (hipStream_t)stream;
-  SrcSel* st = reinterpret_cast<SrcSel*>(select);
-  unsigned int* hist = reinterpret_cast<unsigned int*>(st + 2);
-  for (int pass = 0; pass < 4; ++pass) {
-    if (pass == 0) hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, 2);   // initialise shift = 24
-    hipLaunchKernelGGL(src_sel_hist_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, st, hist);
-    hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, pass == 0 ? 1 : 0);
-  }
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_softmax_down(const float* logits, int N, int C, int h, int w, int ds, float* prob, int H, int W, pfst_stream_t stream) {
-  PFST_CHECK_ARG(logits && prob && N > 0 && N <= 65535 && C > 0 && h > 0 && w > 0 && ds >= 1 && H > 0 && W > 0);
-  PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
-  hipLaunchKernelGGL(softmax_down_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, ds, prob, H, W);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_trg_valid_mask(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int dil,
-                                   unsigned char* valid, unsigned char* all9, unsigned long long* count, pfst_stream_t stream) {
-  PFST_CHECK_ARG(gt && mix_mask && valid && count && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1);
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  hipLaunchKernelGGL(trg_valid_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, gt, mix_mask, H, W, Hg, Wg, dil, valid, all9, count);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_sim_topk_loss(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
-                                  int N, int C, int H, int W, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
-                                  float* g_sim, pfst_stream_t stream) {
-  PFST_CHECK_ARG(ema_sim && prob && valid && count && gP && acc && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
-  PFST_CHECK_ARG(top_k >= 0 && 2 * top_k + 1 <= 9);    // 0 = all nine pairs (top_k=None)
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(acc, 0, 2 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  hipLaunchKernelGGL(topk_loss_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, ema_sim, prob, valid, count, C, H, W, dil, top_k,
-                     w_pos, w_neg, gP, acc, g_sim);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, int C, int H, int W, int dil, int ds, int unfold_grad,
-                                   float* dlogits, int h, int w, pfst_stream_t stream) {
-  PFST_CHECK_ARG(prob && gP && dlogits && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 && ds >= 1);
-  PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
-  hipLaunchKernelGGL(cross_prob_bwd_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, prob, gP, C, H, W, dil, ds,
-                     unfold_grad, dlogits, h, w);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-extern "C" int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int top_k, float w_pos, float w_neg, float* out, pfst_stream_t stream) {
-  PFST_CHECK_ARG(acc && count && out && top_k >= 0);
-  hipLaunchKernelGGL(sim_loss_finalize_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, acc, count, top_k, w_pos, w_neg, out);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-// ===========================================================================================================================
-// Kernel sizes 3, 5 and 7 (the `_k` entries): nn.Unfold(K, dilation d, padding (K//2) d), tap k = (dy+r) K + (dx+r), r = K//2,
-// offset (dy d, dx d), dy, dx in [-r, r].  The 3x3 entries above stay the production path of the shipped configs (kernel_size 3,
-// top_k <= 4); hip_ops sends everything else here.
-// ===========================================================================================================================
-namespace {
-
+// ---------------------------------------------------------------------------------------------------------------------------
+// Similarity map and adjoint for kernel sizes 3, 5 and 7 (pfst_sim_map_k / pfst_sim_map_bwd_k): halo tiles in LDS, any W and H.
+// ---------------------------------------------------------------------------------------------------------------------------
 constexpr int KT = 16;                  // pixel tile of the K x K stencil kernels: 16 x 16 pixels, one per thread
 constexpr int KT_LDS_FLOATS = 16384;    // 64 KB of LDS per workgroup: a channel chunk of halo tiles (+ the squared-norm tile)
 constexpr int KT_MAX_CC = 8;            // channels per chunk
@@ -1016,47 +457,6 @@ __global__ __launch_bounds__(256) void sim_map_k_kernel(const float* __restrict_
   norm[(i64)n * HW + p] = sqrtf(nsq[ctr]);
 }
 
-// ---- adjoint coefficients, both similarity types: coef[n][K^2 + 1][HW] = (A_0 .. A_{K^2-1} with A_centre = 0, B), so that
-// dF(r) = B(r) F(r) + sum_k A_k(r) F(r + D_k).  Pixel r is the mirror tap K^2-1-k of its k-neighbour r + D_k (see sim_map_bwd_kernel).
-template <int K, bool GAUSS>
-__global__ __launch_bounds__(256) void sim_bwd_coef_k_kernel(const float* __restrict__ sim, const float* __restrict__ norm,
-                                                             const float* __restrict__ gsim, int H, int W, int dil, float inv_sigma2,
-                                                             float* __restrict__ coef) {
-  constexpr int R = K / 2, KK = K * K;
-  const int n = blockIdx.y, HW = H * W;
-  const float* sp = sim + (i64)n * KK * HW;
-  const float* gp = gsim + (i64)n * KK * HW;
-  const float* np_ = norm + (i64)n * HW;
-  float* cp = coef + (i64)n * (KK + 1) * HW;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    const float nr = GAUSS ? 1.f : fmaxf(np_[p], COS_EPS);
-    float b = 0.f;
-#pragma unroll
-    for (int k = 0; k < KK; ++k) {
-      const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
-      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
-      float a = 0.f;
-      if (in && k != KK / 2) {
-        const int q = sy * W + sx, m = KK - 1 - k;
-        const float g1 = gp[(i64)k * HW + p], g2 = gp[(i64)m * HW + q];
-        if (GAUSS) {
-          const float c = -2.f * inv_sigma2 * (g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)m * HW + q]);
-          a = -c;
-          b += c;
-        } else {
-          a = (g1 + g2) / (nr * fmaxf(np_[q], COS_EPS));
-          b -= g1 * sp[(i64)k * HW + p] + g2 * sp[(i64)m * HW + q];
-        }
-      } else if (GAUSS && !in) {
-        b += -2.f * inv_sigma2 * gp[(i64)k * HW + p] * sp[(i64)k * HW + p];    // neighbour is the constant 0: centre side only
-      }
-      cp[(i64)k * HW + p] = a;
-    }
-    cp[(i64)KK * HW + p] = GAUSS ? b : b / (nr * nr);
-  }
-}
-
 // ---- the adjoint's stencil: same tiling as sim_map_k_kernel, K^2 + 1 coefficients per thread in registers.
 // grid: (ceil(W / 16), ceil(H / 16), N), 256 threads, cc * la floats of dynamic LDS
 template <int K, int D>
@@ -1097,10 +497,14 @@ __global__ __launch_bounds__(256) void sim_map_bwd_k_kernel(const float* __restr
   }
 }
 
-// ---- source pairs, K x K: 0 = skip, 1 = positive pair, 2 = negative pair (nn.Unfold's zero padding has label 0, a real class)
+// ---------------------------------------------------------------------------------------------------------------------------
+// Label, top-k and gradient kernels: one `template <int K>` kernel per job, instantiated for K = 3, 5, 7 (PFST_KSIZE_SWITCH).
+// One thread per pixel of the loss grid, tap loop inside.  grid: (blocks over H*W, N)
+// ---------------------------------------------------------------------------------------------------------------------------
+// ---- source pairs: 1 = positive pair (same label), 2 = negative pair (nn.Unfold's zero padding has label 0, a real class)
 template <int K>
-__device__ __forceinline__ int src_pair_class_k(const unsigned char* __restrict__ gt, int Hg, int Wg, float sgy, float sgx, int H, int W,
-                                                int y, int x, int k, int dil, int ctr) {
+__device__ __forceinline__ int src_pair_class(const unsigned char* __restrict__ gt, int Hg, int Wg, float sgy, float sgx, int H, int W,
+                                              int y, int x, int k, int dil, int ctr) {
   constexpr int R = K / 2;
   const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
   int nb = 0;
@@ -1108,10 +512,36 @@ __device__ __forceinline__ int src_pair_class_k(const unsigned char* __restrict_
   return nb == ctr ? 1 : 2;
 }
 
+// ---- src_perc (pfgst_loss.py:98-102): only the hardest fraction of the source pairs enters the source losses -- the smallest
+// positive and the largest negative similarities: `sorted[:int(n * src_perc)]`.  A sorted prefix is {s < t} plus some of the ties
+// {s == t}, t the K-th smallest value, so no sort is needed: an exact radix select (4 passes of 8 bits over order-preserving
+// integer keys) finds t and the number of ties inside the prefix; ties share that number equally (they are equal values, so the
+// losses are the reference's; only the split of the gradient among EXACTLY equal similarities is even instead of by sort position).
+// Negative pairs use the complemented key (descending order).
+struct SrcSel {                       // one per set (0: positive pairs, 1: negative pairs)
+  unsigned int prefix;                // key bits fixed so far; after the last pass: key of the K-th element
+  unsigned int shift;                 // bit position of the digit the next histogram pass resolves (24, 16, 8, 0)
+  unsigned long long rank;            // 1-based rank of the wanted element among the keys matching `prefix`
+  unsigned long long K;               // int(n * src_perc)
+  float w_tie;                        // weight of the elements whose key == prefix (ties inside the prefix / all ties)
+  int done;
+};
+__device__ __forceinline__ unsigned int order_key(float v, bool descending) {
+  const unsigned int u = __float_as_uint(v);
+  const unsigned int k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return descending ? ~k : k;
+}
+__device__ __forceinline__ float sel_weight(const SrcSel* __restrict__ sel, int set, float v) {
+  if (!sel) return 1.f;
+  const unsigned int k = order_key(v, set == 1);
+  return k < sel[set].prefix ? 1.f : (k == sel[set].prefix ? sel[set].w_tie : 0.f);
+}
+
+// grid: (blocks over H*W, N): histogram of the current digit of the keys matching the prefix
 template <int K>
-__global__ __launch_bounds__(256) void src_sel_hist_k_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
-                                                             int Hg, int Wg, int dil, const SrcSel* __restrict__ sel,
-                                                             unsigned int* __restrict__ hist) {
+__global__ __launch_bounds__(256) void src_sel_hist_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
+                                                           int Hg, int Wg, int dil, const SrcSel* __restrict__ sel,
+                                                           unsigned int* __restrict__ hist) {
   constexpr int KK = K * K;
   __shared__ unsigned int sh[2 * 256];
   sh[threadIdx.x] = 0; sh[256 + threadIdx.x] = 0;
@@ -1120,13 +550,14 @@ __global__ __launch_bounds__(256) void src_sel_hist_k_kernel(const float* __rest
   const unsigned char* g = gt + (i64)n * Hg * Wg;
   const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
   const unsigned int shift0 = sel[0].shift, shift1 = sel[1].shift;
+  // keys match when their bits ABOVE the current digit equal the prefix (first pass: shift = 24, nothing fixed yet)
   const unsigned int hi0 = shift0 >= 24 ? 0u : (0xFFFFFFFFu << (shift0 + 8)), hi1 = shift1 >= 24 ? 0u : (0xFFFFFFFFu << (shift1 + 8));
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
     const int y = p / W, x = p - y * W;
     const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
     if (ctr == 255) continue;
     for (int k = 0; k < KK; ++k) {
-      const int cls = src_pair_class_k<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+      const int cls = src_pair_class<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
       const float v = sim[((i64)n * KK + k) * HW + p];
       if (cls == 1) {
         const unsigned int key = order_key(v, false);
@@ -1142,12 +573,58 @@ __global__ __launch_bounds__(256) void src_sel_hist_k_kernel(const float* __rest
   if (sh[256 + threadIdx.x]) atomicAdd(&hist[256 + threadIdx.x], sh[256 + threadIdx.x]);
 }
 
+// one block, 2 threads used: resolve the digit, advance the state, clear the histogram
+// first: 2 = initialise the state (before the first histogram), 1 = first digit (also fixes K from the set size), 0 = later digits
+__global__ void src_sel_scan_kernel(SrcSel* __restrict__ sel, unsigned int* __restrict__ hist, double perc, int first) {
+  const int set = threadIdx.x;
+  if (first == 2) {
+    if (set < 2) {
+      sel[set].prefix = 0; sel[set].shift = 24; sel[set].rank = 0; sel[set].K = 0; sel[set].w_tie = 0.f; sel[set].done = 0;
+    }
+    for (int i = threadIdx.x; i < 512; i += blockDim.x) hist[i] = 0;
+    return;
+  }
+  if (set < 2) {
+    SrcSel& st = sel[set];
+    unsigned int* h = hist + 256 * set;
+    if (first) {
+      unsigned long long n = 0;
+      for (int d = 0; d < 256; ++d) n += h[d];
+      st.K = (unsigned long long)((double)n * perc);         // int(n * src_perc): truncation of the double product
+      st.rank = st.K;
+      st.prefix = 0;
+      st.done = st.K == 0;
+      st.w_tie = 0.f;                                          // K == 0: nothing selected (no key is below prefix 0)
+    }
+    if (!st.done) {
+      unsigned long long cum = 0;
+      int d = 0;
+      for (; d < 256; ++d) {
+        if (cum + h[d] >= st.rank) break;
+        cum += h[d];
+      }
+      st.prefix |= (unsigned int)d << st.shift;
+      st.rank -= cum;
+      if (st.shift == 0) {
+        st.w_tie = (float)((double)st.rank / (double)h[d]);   // `rank` of the h[d] ties lie inside the sorted prefix
+        st.done = 1;
+      }
+    }
+    st.shift = st.shift >= 8 ? st.shift - 8 : 0;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 512; i += blockDim.x) hist[i] = 0;
+}
+
+// ---- source statistics.  loss_type 0: count / sum / sum of squares (mean & unbiased std, :107-115); 1 / 2: count / sum of relu(m0 - s)^e for positive
+// pairs and relu(s - m1)^e for negative pairs, e = loss_type (:116-131).
 template <int K>
-__global__ __launch_bounds__(256) void src_stats_k_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
-                                                          int Hg, int Wg, int dil, int loss_type, float m0, float m1,
-                                                          double* __restrict__ stats, const SrcSel* __restrict__ sel,
-                                                          double* __restrict__ det_part) {
-  // det_part != NULL (deterministic mode): the block's six sums go to its slot of det_part[slots][6] (see src_stats_kernel)
+__global__ __launch_bounds__(256) void src_stats_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
+                                                        int Hg, int Wg, int dil, int loss_type, float m0, float m1,
+                                                        double* __restrict__ stats, const SrcSel* __restrict__ sel,
+                                                        double* __restrict__ det_part) {
+  // det_part != NULL (deterministic mode, api.cpp): this block's six sums go to slot blockIdx.y * gridDim.x + blockIdx.x of det_part[slots][6]
+  // instead of being added atomically into stats; src_stats_det_sum_kernel adds the slots in index order
   constexpr int KK = K * K;
   __shared__ double sm[16];
   const int n = blockIdx.y, HW = H * W;
@@ -1159,7 +636,7 @@ __global__ __launch_bounds__(256) void src_stats_k_kernel(const float* __restric
     const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
     if (ctr == 255) continue;
     for (int k = 0; k < KK; ++k) {
-      const int cls = src_pair_class_k<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+      const int cls = src_pair_class<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
       const float sv = sim[((i64)n * KK + k) * HW + p];
       const double s = (double)sv;
       const double wt = (double)sel_weight(sel, cls == 1 ? 0 : 1, sv);
@@ -1181,35 +658,71 @@ __global__ __launch_bounds__(256) void src_stats_k_kernel(const float* __restric
     }
   }
 }
+__global__ void src_stats_det_sum_kernel(const double* __restrict__ part, int T, double* __restrict__ stats) {
+  const int i = threadIdx.x;
+  if (i >= 6) return;
+  double a = 0.0;
+  for (int k = 0; k < T; ++k) a += part[(i64)k * 6 + i];
+  stats[i] = a;
+}
+
+struct SrcMoments { double n, mean, std; };
+__device__ __forceinline__ SrcMoments moments(const double* st) {
+  SrcMoments m;
+  m.n = st[0];
+  m.mean = st[0] > 0 ? st[1] / st[0] : 0.0;
+  const double var = st[0] > 1 ? (st[2] - st[1] * st[1] / st[0]) / (st[0] - 1.0) : 0.0;
+  m.std = var > 0 ? sqrt(var) : 0.0;
+  return m;
+}
 
 template <int K>
-__global__ __launch_bounds__(256) void src_grad_k_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
-                                                         int Hg, int Wg, int dil, int loss_type, float m0, float m1,
-                                                         const double* __restrict__ stats, float w_pos, float w_neg, float w_pos_std,
-                                                         float w_neg_std, float* __restrict__ gsim, float* __restrict__ losses,
-                                                         const SrcSel* __restrict__ sel) {
+__global__ __launch_bounds__(256) void src_grad_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ gt, int H, int W,
+                                                       int Hg, int Wg, int dil, int loss_type, float m0, float m1,
+                                                       const double* __restrict__ stats, float w_pos, float w_neg, float w_pos_std,
+                                                       float w_neg_std, float* __restrict__ gsim, float* __restrict__ losses,
+                                                       const SrcSel* __restrict__ sel) {
   constexpr int KK = K * K;
   const int n = blockIdx.y, HW = H * W;
   const unsigned char* g = gt + (i64)n * Hg * Wg;
   const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W;
-  const bool hinge = loss_type != 0;
-  const SrcMoments mp = moments(stats), mn = moments(stats + 3);
-  const double np = stats[0], nn = stats[3];
-  if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
-    if (hinge) {
+  // One loop per loss type with the taps unrolled, not one loop that branches per tap: at K = 3 the merged loop was 0.5 us slower
+  // (profiles/pfgst_family_merge.txt)
+  if (loss_type != 0) {       // hinge losses: mean over the pairs of relu(.)^e; d/ds = -/+ e relu(.)^(e-1) w / n
+    const double np = stats[0], nn = stats[3];
+    if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
       losses[0] = np > 0 ? (float)((double)w_pos * stats[1] / np) : 0.f;     // (an empty set gives NaN in the reference)
       losses[1] = nn > 0 ? (float)((double)w_neg * stats[4] / nn) : 0.f;
       losses[2] = 0.f;
       losses[3] = 0.f;
-    } else {
-      losses[0] = (float)(-mp.mean * w_pos);
-      losses[1] = (float)(mn.mean * w_neg);
-      losses[2] = (float)(mp.std * w_pos_std);
-      losses[3] = (float)(mn.std * w_neg_std);
     }
+    const double cp = np > 0 ? (double)w_pos / np : 0.0, cn = nn > 0 ? (double)w_neg / nn : 0.0;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+      const int y = p / W, x = p - y * W;
+      const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+#pragma unroll
+      for (int k = 0; k < KK; ++k) {
+        const i64 o = ((i64)n * KK + k) * HW + p;
+        float gr = 0.f;
+        if (ctr != 255) {
+          const int cls = src_pair_class<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+          const double s = (double)sim[o];
+          const double h = cls == 1 ? (double)m0 - s : s - (double)m1;
+          if (h > 0.0) gr = (float)((cls == 1 ? -cp : cn) * (loss_type == 1 ? 1.0 : 2.0 * h)) * sel_weight(sel, cls == 1 ? 0 : 1, sim[o]);
+        }
+        gsim[o] = gr;
+      }
+    }
+    return;
   }
-  // hinge: d/ds = -/+ e relu(.)^(e-1) w / n;  mean_std: d(-w mean)/ds = -w/n, d(w std)/ds = w (s-mean)/((n-1) std)
-  const double cp = np > 0 ? (double)w_pos / np : 0.0, cn = nn > 0 ? (double)w_neg / nn : 0.0;
+  const SrcMoments mp = moments(stats), mn = moments(stats + 3);
+  if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
+    losses[0] = (float)(-mp.mean * w_pos);
+    losses[1] = (float)(mn.mean * w_neg);
+    losses[2] = (float)(mp.std * w_pos_std);
+    losses[3] = (float)(mn.std * w_neg_std);
+  }
+  // d(-w mean)/ds = -w/n ; d(w std)/ds = w (s-mean)/((n-1) std)
   const double pa = mp.n > 0 ? -(double)w_pos / mp.n : 0.0;
   const double pb = (mp.n > 1 && mp.std > 0) ? (double)w_pos_std / ((mp.n - 1.0) * mp.std) : 0.0;
   const double na = mn.n > 0 ? (double)w_neg / mn.n : 0.0;
@@ -1217,30 +730,42 @@ __global__ __launch_bounds__(256) void src_grad_k_kernel(const float* __restrict
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
     const int y = p / W, x = p - y * W;
     const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+#pragma unroll
     for (int k = 0; k < KK; ++k) {
       const i64 o = ((i64)n * KK + k) * HW + p;
       float gr = 0.f;
       if (ctr != 255) {
-        const int cls = src_pair_class_k<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
+        const int cls = src_pair_class<K>(g, Hg, Wg, sgy, sgx, H, W, y, x, k, dil, ctr);
         const double s = (double)sim[o];
-        const float wt = sel_weight(sel, cls == 1 ? 0 : 1, sim[o]);
-        if (hinge) {
-          const double h = cls == 1 ? (double)m0 - s : s - (double)m1;
-          if (h > 0.0) gr = (float)((cls == 1 ? -cp : cn) * (loss_type == 1 ? 1.0 : 2.0 * h)) * wt;
-        } else {
-          gr = (cls == 1 ? (float)(pa + pb * (s - mp.mean)) : (float)(na + nb * (s - mn.mean))) * wt;
-        }
+        gr = (cls == 1 ? (float)(pa + pb * (s - mp.mean)) : (float)(na + nb * (s - mn.mean))) * sel_weight(sel, cls == 1 ? 0 : 1, sim[o]);
       }
       gsim[o] = gr;
     }
   }
 }
 
+// ---- softmax of the nearest-down-scaled student logits.  grid: (blocks over H*W, N)
+__global__ void softmax_down_kernel(const float* __restrict__ logits, int C, int h, int w, int ds, float* __restrict__ prob, int H, int W) {
+  const int n = blockIdx.y, HW = H * W;
+  const float* lp = logits + (i64)n * C * h * w;
+  float* pp = prob + (i64)n * C * HW;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    const int so = (y * ds) * w + x * ds;
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lp[(i64)c * h * w + so]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(lp[(i64)c * h * w + so] - mx);
+    const float inv = 1.f / se;
+    for (int c = 0; c < C; ++c) pp[(i64)c * HW + p] = expf(lp[(i64)c * h * w + so] - mx) * inv;
+  }
+}
+
 // ---- target validity: centre label != 255 and all K^2 dilated neighbours inside the map and un-mixed
 template <int K>
-__global__ __launch_bounds__(256) void trg_valid_k_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ mix,
-                                                          int H, int W, int Hg, int Wg, int dil, unsigned char* __restrict__ valid,
-                                                          unsigned char* __restrict__ all_in, unsigned long long* __restrict__ count) {
+__global__ __launch_bounds__(256) void trg_valid_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ mix,
+                                                        int H, int W, int Hg, int Wg, int dil, unsigned char* __restrict__ valid,
+                                                        unsigned char* __restrict__ all_in, unsigned long long* __restrict__ count) {
   constexpr int R = K / 2, KK = K * K;
   __shared__ double sm[16];
   const int n = blockIdx.y, HW = H * W;
@@ -1251,9 +776,11 @@ __global__ __launch_bounds__(256) void trg_valid_k_kernel(const unsigned char* _
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
     const int y = p / W, x = p - y * W;
     bool all = true;
-    for (int k = 0; k < KK && all; ++k) {
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {       // every tap, no early exit: faster at K = 3 than leaving the loop (profiles/pfgst_family_merge.txt)
       const int sy = y + (k / K - R) * dil, sx = x + (k % K - R) * dil;
-      all = sy >= 0 && sy < H && sx >= 0 && sx < W && m[(i64)nearest_src(sy, sgy, Hg) * Wg + nearest_src(sx, sgx, Wg)] == 0;
+      const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
+      all = all && in && (m[(i64)nearest_src(in ? sy : 0, sgy, Hg) * Wg + nearest_src(in ? sx : 0, sgx, Wg)] == 0);
     }
     const int ctr = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
     const bool v = all && ctr != 255;
@@ -1265,15 +792,17 @@ __global__ __launch_bounds__(256) void trg_valid_k_kernel(const unsigned char* _
   if (threadIdx.x == 0 && cnt > 0.0) atomicAdd(count, (unsigned long long)cnt);
 }
 
-// ---- top-k target losses, K x K.  Rank-count selection instead of a sort (no dynamic indexing of the per-thread arrays):
-// rank_j = #{i : s_i > s_j or (s_i == s_j and i < j)} -- stable descending order, lower index first on ties, as the 3x3 kernel's
-// insertion sort.  The top-(top_k+1) set is ranks 0..top_k, the bottom-top_k set ranks K^2-top_k..K^2-1; for 2 top_k + 1 > K^2 the
+// ---- top-k target losses.  Rank-count selection instead of a sort (no dynamic indexing of the per-thread arrays):
+// rank_j = #{i : s_i > s_j or (s_i == s_j and i < j)} -- stable descending order, lower tap index first on ties.
+// The top-(top_k+1) set is ranks 0..top_k, the bottom-top_k set ranks K^2-top_k..K^2-1; for 2 top_k + 1 > K^2 the
 // sets overlap and a pair in both contributes to both losses and both gradient terms (torch.topk + gather in the reference).
+// (A 9-element insertion sort in registers used to serve K = 3 with disjoint sets: 90 VGPRs against 36, same outputs bit for bit and
+// not faster at the bench shape, profiles/pfgst_family_merge.txt.)
 template <int K>
-__global__ __launch_bounds__(256) void topk_loss_k_kernel(const float* __restrict__ ema_sim, const float* __restrict__ prob,
-                                                          const unsigned char* __restrict__ valid, const unsigned long long* __restrict__ count,
-                                                          int C, int H, int W, int dil, int top_k, float w_pos, float w_neg,
-                                                          float* __restrict__ gP, double* __restrict__ acc, float* __restrict__ gS) {
+__global__ __launch_bounds__(256) void topk_loss_kernel(const float* __restrict__ ema_sim, const float* __restrict__ prob,
+                                                        const unsigned char* __restrict__ valid, const unsigned long long* __restrict__ count,
+                                                        int C, int H, int W, int dil, int top_k, float w_pos, float w_neg,
+                                                        float* __restrict__ gP, double* __restrict__ acc, float* __restrict__ gS) {
   constexpr int R = K / 2, KK = K * K;
   __shared__ double sm[16];
   const int n = blockIdx.y, HW = H * W;
@@ -1334,10 +863,12 @@ __global__ __launch_bounds__(256) void topk_loss_k_kernel(const float* __restric
   }
 }
 
-// ---- gradient of the cross-probabilities into the student logits, K x K (cross_prob_bwd_kernel; mirror tap K^2-1-k)
+// ---- gradient of the cross-probabilities P_k(r) = sum_c p_c(r) p_c(r+D_k) into the (full 1/4-res) student logits.
+// detach_unfold=True: only the centre factor p_c(r) carries gradient.  unfold_grad (detach_unfold=False): the unfolded
+// factor does too -- pixel r is the k-neighbour of r+D_{K^2-1-k}, so its coefficient gains gP[K^2-1-k, r+D_k] (gather form, no atomics).
 template <int K>
-__global__ __launch_bounds__(256) void cross_prob_bwd_k_kernel(const float* __restrict__ prob, const float* __restrict__ gP, int C, int H,
-                                                               int W, int dil, int ds, int unfold_grad, float* __restrict__ dlogits, int h, int w) {
+__global__ __launch_bounds__(256) void cross_prob_bwd_kernel(const float* __restrict__ prob, const float* __restrict__ gP, int C, int H,
+                                                             int W, int dil, int ds, int unfold_grad, float* __restrict__ dlogits, int h, int w) {
   constexpr int R = K / 2, KK = K * K;
   const int n = blockIdx.y, HW = H * W;
   const float* pp = prob + (i64)n * C * HW;
@@ -1374,11 +905,17 @@ __global__ __launch_bounds__(256) void cross_prob_bwd_k_kernel(const float* __re
   }
 }
 
-__global__ void sim_loss_finalize_k_kernel(const double* __restrict__ acc, const unsigned long long* __restrict__ count, int kk, int top_k,
-                                           float w_pos, float w_neg, float* __restrict__ out) {
+__global__ void sim_loss_finalize_kernel(const double* __restrict__ acc, const unsigned long long* __restrict__ count, int kk, int top_k,
+                                         float w_pos, float w_neg, float* __restrict__ out) {
   const double cnt = (double)count[0];
   out[0] = cnt > 1.0 ? (float)((double)w_pos * acc[0] / (cnt * (top_k == 0 ? kk : top_k + 1))) : 0.f;
   out[1] = cnt > 1.0 ? (float)((double)w_neg * acc[1] / (cnt * (top_k == 0 ? kk : top_k))) : 0.f;
+}
+
+inline int px_blocks(i64 n) {
+  i64 g = (n + 255) / 256;
+  if (g > 4096) g = 4096;
+  return g < 1 ? 1 : (int)g;
 }
 
 inline bool ksize_ok(int ksize) { return ksize == 3 || ksize == 5 || ksize == 7; }
@@ -1405,8 +942,8 @@ template <int K>
 void launch_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int dil,
                           int gauss, float inv_sigma2, int cc, float* dfeat, int accumulate, float* coef, hipStream_t s) {
   const dim3 gp(px_blocks((i64)H * W), N);
-  if (gauss) hipLaunchKernelGGL((sim_bwd_coef_k_kernel<K, true>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, inv_sigma2, coef);
-  else hipLaunchKernelGGL((sim_bwd_coef_k_kernel<K, false>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, 0.f, coef);
+  if (gauss) hipLaunchKernelGGL((sim_bwd_coef_kernel<K, true>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, inv_sigma2, coef);
+  else hipLaunchKernelGGL((sim_bwd_coef_kernel<K, false>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, 0.f, coef);
   const int hal = (K / 2) * dil, la = kt_edge(hal) * kt_edge(hal);
   const dim3 grid(cdiv(W, KT), cdiv(H, KT), N);
   const size_t lds = (size_t)cc * la * sizeof(float);
@@ -1416,6 +953,51 @@ void launch_sim_map_bwd_k(const float* feat, const float* sim, const float* norm
 }
 
 }  // namespace
+
+extern "C" int pfst_sim_map(const float* feat, int N, int C, int H, int W, int dil, int sim_type, float sigma, float* sim, float* norm,
+                            pfst_stream_t stream) {
+  PFST_CHECK_ARG(feat && sim && norm && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
+  PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
+  const dim3 grid(px_blocks((i64)H * W), N);
+  if (sim_type == 0 && simq_ok(feat, sim, C, H, W, dil) && (reinterpret_cast<uintptr_t>(norm) & 15) == 0) {
+    const dim3 gq((unsigned)(((i64)H * W) / 256), N);
+    const size_t lds = 4 * SIMQ_VALS * 64 * sizeof(float);
+    if (C % 8 == 0 && C >= 64) {                   // 8 channel slices per strip: 16 waves per CU at the BASELINE shape
+      if (dil == 1) hipLaunchKernelGGL((sim_map_cos_q_kernel<1, 8>), gq, dim3(512), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
+      else hipLaunchKernelGGL((sim_map_cos_q_kernel<2, 8>), gq, dim3(512), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
+    } else {
+      if (dil == 1) hipLaunchKernelGGL((sim_map_cos_q_kernel<1, 4>), gq, dim3(256), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
+      else hipLaunchKernelGGL((sim_map_cos_q_kernel<2, 4>), gq, dim3(256), lds, (hipStream_t)stream, feat, C, H, W, sim, norm);
+    }
+  } else if (sim_type == 1)
+    hipLaunchKernelGGL(sim_map_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, feat, C, H, W, dil, 1.f / (sigma * sigma), sim, norm);
+  else
+    hipLaunchKernelGGL(sim_map_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, feat, C, H, W, dil, 0.f, sim, norm);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_sim_map_bwd(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int dil,
+                                int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream) {
+  PFST_CHECK_ARG(feat && sim && norm && gsim && dfeat && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
+  PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
+  const dim3 grid(px_blocks((i64)H * W), N);
+  if (sim_type == 0 && coef_ws && simq_ok(feat, dfeat, C, H, W, dil) && (reinterpret_cast<uintptr_t>(coef_ws) & 15) == 0) {
+    PFST_CHECK_ARG(coef_ws != nullptr);
+    hipLaunchKernelGGL((sim_bwd_coef_kernel<3, false>), grid, dim3(256), 0, (hipStream_t)stream, sim, norm, gsim, H, W, dil, 0.f, coef_ws);
+    const int cpw = 16;                                   // channels per wave
+    const dim3 gq((unsigned)(((i64)H * W) / 256), cdiv(C, 4 * cpw), N);
+    if (dil == 1) hipLaunchKernelGGL(sim_map_bwd_cos_q_kernel<1>, gq, dim3(256), 0, (hipStream_t)stream, feat, coef_ws, C, H, W, cpw, dfeat, accumulate);
+    else hipLaunchKernelGGL(sim_map_bwd_cos_q_kernel<2>, gq, dim3(256), 0, (hipStream_t)stream, feat, coef_ws, C, H, W, cpw, dfeat, accumulate);
+  } else if (sim_type == 1)
+    hipLaunchKernelGGL(sim_map_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, feat, sim, norm, gsim, C, H, W, dil,
+                       1.f / (sigma * sigma), dfeat, accumulate);
+  else
+    hipLaunchKernelGGL(sim_map_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, feat, sim, norm, gsim, C, H, W, dil, 0.f, dfeat,
+                       accumulate);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
 
 extern "C" int pfst_sim_map_k(const float* feat, int N, int C, int H, int W, int ksize, int dil, int sim_type, float sigma, float* sim,
                               float* norm, pfst_stream_t stream) {
@@ -1448,8 +1030,8 @@ extern "C" int pfst_sim_map_bwd_k(const float* feat, const float* sim, const flo
   return PFST_OK;
 }
 
-extern "C" int pfst_src_sim_stats_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
-                                    int loss_type, float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream) {
+extern "C" int pfst_src_sim_stats(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                                  int loss_type, float margin_pos, float margin_neg, double* stats, const void* select, pfst_stream_t stream) {
   PFST_CHECK_ARG(sim && gt && stats && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
   PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
   hipStream_t s = (hipStream_t)stream;
@@ -1460,28 +1042,30 @@ extern "C" int pfst_src_sim_stats_k(const float* sim, const unsigned char* gt, i
     det = static_cast<double*>(pfst_det_scratch((size_t)gxs * N * 6 * sizeof(double), s));
     PFST_CHECK_DET(det != nullptr);
   }
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_stats_k_kernel<K_>, dim3(gxs, N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, loss_type,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_stats_kernel<K_>, dim3(gxs, N), dim3(256), 0, s, sim, gt, H, W, Hg, Wg, dil, loss_type,
                                               margin_pos, margin_neg, stats, reinterpret_cast<const SrcSel*>(select), det));
   if (det) hipLaunchKernelGGL(src_stats_det_sum_kernel, dim3(1), dim3(64), 0, s, det, gxs * N, stats);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
 
-extern "C" int pfst_src_sim_grad_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
-                                   int loss_type, float margin_pos, float margin_neg, const double* stats, float w_pos, float w_neg,
-                                   float w_pos_std, float w_neg_std, float* gsim, float* losses, const void* select, pfst_stream_t stream) {
+extern "C" int pfst_src_sim_grad(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                                 int loss_type, float margin_pos, float margin_neg, const double* stats, float w_pos, float w_neg,
+                                 float w_pos_std, float w_neg_std, float* gsim, float* losses, const void* select, pfst_stream_t stream) {
   PFST_CHECK_ARG(sim && gt && stats && gsim && losses && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 &&
                  ksize_ok(ksize));
   PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_grad_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, sim,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_grad_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, sim,
                                               gt, H, W, Hg, Wg, dil, loss_type, margin_pos, margin_neg, stats, w_pos, w_neg, w_pos_std,
                                               w_neg_std, gsim, losses, reinterpret_cast<const SrcSel*>(select)));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
 
-extern "C" int pfst_src_sim_select_k(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
-                                     double src_perc, void* select, pfst_stream_t stream) {
+extern "C" int pfst_src_sim_select_bytes(void) { return (int)(2 * sizeof(SrcSel) + 512 * sizeof(unsigned int)); }
+
+extern "C" int pfst_src_sim_select(const float* sim, const unsigned char* gt, int N, int H, int W, int Hg, int Wg, int ksize, int dil,
+                                   double src_perc, void* select, pfst_stream_t stream) {
   PFST_CHECK_ARG(sim && gt && select && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
   PFST_CHECK_ARG(src_perc >= 0.0 && src_perc <= 1.0 && (reinterpret_cast<uintptr_t>(select) & 7) == 0);
   hipStream_t s = (hipStream_t)stream;
@@ -1489,7 +1073,7 @@ extern "C" int pfst_src_sim_select_k(const float* sim, const unsigned char* gt, 
   unsigned int* hist = reinterpret_cast<unsigned int*>(st + 2);
   for (int pass = 0; pass < 4; ++pass) {
     if (pass == 0) hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, 2);
-    PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_sel_hist_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, sim, gt, H, W,
+    PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_sel_hist_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, sim, gt, H, W,
                                                 Hg, Wg, dil, st, hist));
     hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, pass == 0 ? 1 : 0);
   }
@@ -1497,45 +1081,53 @@ extern "C" int pfst_src_sim_select_k(const float* sim, const unsigned char* gt, 
   return PFST_OK;
 }
 
-extern "C" int pfst_trg_valid_mask_k(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int ksize,
-                                     int dil, unsigned char* valid, unsigned char* all_in, unsigned long long* count, pfst_stream_t stream) {
+extern "C" int pfst_softmax_down(const float* logits, int N, int C, int h, int w, int ds, float* prob, int H, int W, pfst_stream_t stream) {
+  PFST_CHECK_ARG(logits && prob && N > 0 && N <= 65535 && C > 0 && h > 0 && w > 0 && ds >= 1 && H > 0 && W > 0);
+  PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
+  hipLaunchKernelGGL(softmax_down_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, ds, prob, H, W);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_trg_valid_mask(const unsigned char* gt, const unsigned char* mix_mask, int N, int H, int W, int Hg, int Wg, int ksize,
+                                   int dil, unsigned char* valid, unsigned char* all_in, unsigned long long* count, pfst_stream_t stream) {
   PFST_CHECK_ARG(gt && mix_mask && valid && count && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(count, 0, sizeof(unsigned long long), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(trg_valid_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, gt, mix_mask, H, W,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(trg_valid_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, gt, mix_mask, H, W,
                                               Hg, Wg, dil, valid, all_in, count));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
 
-extern "C" int pfst_sim_topk_loss_k(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
-                                    int N, int C, int H, int W, int ksize, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
-                                    float* g_sim, pfst_stream_t stream) {
+extern "C" int pfst_sim_topk_loss(const float* ema_sim, const float* prob, const unsigned char* valid, const unsigned long long* count,
+                                  int N, int C, int H, int W, int ksize, int dil, int top_k, float w_pos, float w_neg, float* gP, double* acc,
+                                  float* g_sim, pfst_stream_t stream) {
   PFST_CHECK_ARG(ema_sim && prob && valid && count && gP && acc && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 &&
                  ksize_ok(ksize));
   PFST_CHECK_ARG(top_k >= 0 && top_k <= ksize * ksize - 1);     // 0 = all K^2 pairs (top_k=None)
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(acc, 0, 2 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(topk_loss_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, ema_sim, prob, valid,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(topk_loss_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, ema_sim, prob, valid,
                                               count, C, H, W, dil, top_k, w_pos, w_neg, gP, acc, g_sim));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
 
-extern "C" int pfst_cross_prob_bwd_k(const float* prob, const float* gP, int N, int C, int H, int W, int ksize, int dil, int ds,
-                                     int unfold_grad, float* dlogits, int h, int w, pfst_stream_t stream) {
+extern "C" int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, int C, int H, int W, int ksize, int dil, int ds,
+                                   int unfold_grad, float* dlogits, int h, int w, pfst_stream_t stream) {
   PFST_CHECK_ARG(prob && gP && dlogits && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 && ds >= 1 && ksize_ok(ksize));
   PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(cross_prob_bwd_k_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(cross_prob_bwd_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream,
                                               prob, gP, C, H, W, dil, ds, unfold_grad, dlogits, h, w));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
 
-extern "C" int pfst_sim_loss_finalize_k(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg,
-                                        float* out, pfst_stream_t stream) {
+extern "C" int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg,
+                                      float* out, pfst_stream_t stream) {
   PFST_CHECK_ARG(acc && count && out && ksize_ok(ksize) && top_k >= 0 && top_k <= ksize * ksize - 1);
-  hipLaunchKernelGGL(sim_loss_finalize_k_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, acc, count, ksize * ksize, top_k, w_pos, w_neg, out);
+  hipLaunchKernelGGL(sim_loss_finalize_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, acc, count, ksize * ksize, top_k, w_pos, w_neg, out);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }

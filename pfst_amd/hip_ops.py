@@ -1202,7 +1202,8 @@ SRC_LOSS_TYPES = {'mean_std': 0, 'margin': 1, 'margin2': 2}
 
 
 def sim_map(feat, dil, sim_type='cosine', sigma=30.0, ksize=3):
-    """-> (sim [N, ksize^2, H, W], norm [N, H, W]).  ksize 3: the 3x3 entry (production path); 5 / 7: pfst_sim_map_k"""
+    """-> (sim [N, ksize^2, H, W], norm [N, H, W]).  ksize 3: the 3x3 entry (strip kernels, production path); 5 / 7: pfst_sim_map_k.
+    The similarity map and its adjoint are the only PFGSTLoss pieces with two implementations; the rest take `ksize` as an argument"""
     _dense(feat)
     n, c, h, w = feat.shape
     sim = torch.empty(n, ksize * ksize, h, w, device=feat.device)
@@ -1238,18 +1239,17 @@ def src_sim_losses(sim, gt_u8, dil, w_pos, w_neg, w_pos_std=0.0, w_neg_std=0.0, 
     n, _, h, w = sim.shape
     hg, wg = gt_u8.shape[-2:]
     lt = SRC_LOSS_TYPES[loss_type]
-    kx, ka = ('', ()) if ksize == 3 else ('_k', (ksize,))      # the 3x3 entries, or the _k family with its `ksize` argument
     sel = None
     if src_perc is not None:
         sel = torch.empty(lib().pfst_src_sim_select_bytes() // 8 + 1, dtype=I64, device=sim.device)       # 8-byte aligned scratch
-        call('pfst_src_sim_select' + kx, _dense(sim).data_ptr(), _dense(gt_u8, U8).data_ptr(), n, h, w, hg, wg, *ka, dil, float(src_perc),
+        call('pfst_src_sim_select', _dense(sim).data_ptr(), _dense(gt_u8, U8).data_ptr(), n, h, w, hg, wg, ksize, dil, float(src_perc),
              sel.data_ptr(), _stream())
     stats = torch.empty(6, dtype=F64, device=sim.device)
-    call('pfst_src_sim_stats' + kx, _dense(sim).data_ptr(), _dense(gt_u8, U8).data_ptr(), n, h, w, hg, wg, *ka, dil, lt, float(margin[0]),
+    call('pfst_src_sim_stats', _dense(sim).data_ptr(), _dense(gt_u8, U8).data_ptr(), n, h, w, hg, wg, ksize, dil, lt, float(margin[0]),
          float(margin[1]), stats.data_ptr(), _p(sel), _stream())
     gsim = torch.empty_like(sim)
     losses = torch.empty(4, device=sim.device)
-    call('pfst_src_sim_grad' + kx, sim.data_ptr(), gt_u8.data_ptr(), n, h, w, hg, wg, *ka, dil, lt, float(margin[0]), float(margin[1]),
+    call('pfst_src_sim_grad', sim.data_ptr(), gt_u8.data_ptr(), n, h, w, hg, wg, ksize, dil, lt, float(margin[0]), float(margin[1]),
          stats.data_ptr(), float(w_pos), float(w_neg), float(w_pos_std), float(w_neg_std), gsim.data_ptr(), losses.data_ptr(), _p(sel),
          _stream())
     return losses, gsim
@@ -1270,15 +1270,14 @@ def trg_valid_mask(gt_u8, mix_mask_u8, hw, dil, ksize=3):
     valid = torch.empty(n, 1, hw[0], hw[1], dtype=U8, device=gt_u8.device)
     all9 = torch.empty(n, 1, hw[0], hw[1], dtype=U8, device=gt_u8.device)
     cnt = torch.empty(1, dtype=I64, device=gt_u8.device)
-    kx, ka = ('', ()) if ksize == 3 else ('_k', (ksize,))
-    call('pfst_trg_valid_mask' + kx, _dense(gt_u8, U8).data_ptr(), _dense(mix_mask_u8, U8).data_ptr(), n, hw[0], hw[1], hg, wg, *ka, dil,
+    call('pfst_trg_valid_mask', _dense(gt_u8, U8).data_ptr(), _dense(mix_mask_u8, U8).data_ptr(), n, hw[0], hw[1], hg, wg, ksize, dil,
          valid.data_ptr(), all9.data_ptr(), cnt.data_ptr(), _stream())
     return valid, all9, cnt
 
 
 def sim_topk_loss(ema_sim, prob, valid, count, dil, top_k, w_pos, w_neg, want_sim_grad=False, ksize=3):
-    """top_k None / 0 = all ksize^2 pairs.  -> (losses float32[2], gP [N,ksize^2,H,W][, d losses / d ema_sim [N,ksize^2,H,W]]).
-    ksize 3 with top_k <= 4 (disjoint top / bottom sets): the 3x3 entries; otherwise the _k family"""
+    """top_k None / 0 = all ksize^2 pairs, else 1 .. ksize^2 - 1 (the top / bottom sets overlap above (ksize^2 - 1) / 2).
+    -> (losses float32[2], gP [N,ksize^2,H,W][, d losses / d ema_sim [N,ksize^2,H,W]])"""
     top_k = int(top_k or 0)
     n, c, h, w = prob.shape
     kk = ksize * ksize
@@ -1286,22 +1285,16 @@ def sim_topk_loss(ema_sim, prob, valid, count, dil, top_k, w_pos, w_neg, want_si
     gS = torch.empty(n, kk, h, w, device=prob.device) if want_sim_grad else None
     acc = torch.empty(2, dtype=F64, device=prob.device)
     out = torch.empty(2, device=prob.device)
-    if ksize == 3 and top_k <= 4:
-        call('pfst_sim_topk_loss', _dense(ema_sim).data_ptr(), _dense(prob).data_ptr(), _dense(valid, U8).data_ptr(), count.data_ptr(),
-             n, c, h, w, dil, top_k, float(w_pos), float(w_neg), gP.data_ptr(), acc.data_ptr(), _p(gS), _stream())
-        call('pfst_sim_loss_finalize', acc.data_ptr(), count.data_ptr(), top_k, float(w_pos), float(w_neg), out.data_ptr(), _stream())
-    else:
-        call('pfst_sim_topk_loss_k', _dense(ema_sim).data_ptr(), _dense(prob).data_ptr(), _dense(valid, U8).data_ptr(), count.data_ptr(),
-             n, c, h, w, ksize, dil, top_k, float(w_pos), float(w_neg), gP.data_ptr(), acc.data_ptr(), _p(gS), _stream())
-        call('pfst_sim_loss_finalize_k', acc.data_ptr(), count.data_ptr(), ksize, top_k, float(w_pos), float(w_neg), out.data_ptr(), _stream())
+    call('pfst_sim_topk_loss', _dense(ema_sim).data_ptr(), _dense(prob).data_ptr(), _dense(valid, U8).data_ptr(), count.data_ptr(),
+         n, c, h, w, ksize, dil, top_k, float(w_pos), float(w_neg), gP.data_ptr(), acc.data_ptr(), _p(gS), _stream())
+    call('pfst_sim_loss_finalize', acc.data_ptr(), count.data_ptr(), ksize, top_k, float(w_pos), float(w_neg), out.data_ptr(), _stream())
     return (out, gP, gS) if want_sim_grad else (out, gP)
 
 
 def cross_prob_bwd_(dlogits, prob, gP, dil, ds, unfold_grad=False, ksize=3):
     n, c, H, W = prob.shape
     h, w = dlogits.shape[-2:]
-    kx, ka = ('', ()) if ksize == 3 else ('_k', (ksize,))
-    call('pfst_cross_prob_bwd' + kx, _dense(prob).data_ptr(), _dense(gP).data_ptr(), n, c, H, W, *ka, dil, ds, int(unfold_grad),
+    call('pfst_cross_prob_bwd', _dense(prob).data_ptr(), _dense(gP).data_ptr(), n, c, H, W, ksize, dil, ds, int(unfold_grad),
          _dense(dlogits).data_ptr(), h, w, _stream())
     return dlogits
 

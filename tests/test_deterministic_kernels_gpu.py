@@ -443,8 +443,8 @@ def test_dwconv_multi_bwd(ops, H, W, dils, bnb):
 # ------------------------------------------------------------------------------------------------------------------ PFGSTLoss source statistics
 @pytest.mark.parametrize('K,d', [(3, 1), (5, 2), (7, 3)])
 def test_src_sim_losses(ops, K, d):
-    """the six source sums as gxs * N fp64 slots (22 x 26 pixels: 3 pixel blocks x 2 images), for mean_std, margin2 and src_perc; K = 3 runs the
-    3x3 entry points, 5 and 7 the _k family; the inputs of tests/test_pfgst_kernel_size_gpu.py::test_source_target_and_cross_prob_k_against_torch"""
+    """the six source sums as gxs * N fp64 slots (22 x 26 pixels: 3 pixel blocks x 2 images), for mean_std, margin2 and src_perc, at each
+    kernel size of the one K x K kernel family; the inputs of tests/test_pfgst_kernel_size_gpu.py::test_source_target_and_cross_prob_k_against_torch"""
     gen = torch.Generator().manual_seed(100 + K * 10 + d)
     n, H, W = 2, 22, 26
     assert cdiv(H * W, 256) * n > 1

@@ -1041,11 +1041,11 @@ def test_src_perc_selection_counts(ops):
         from pfst_amd._lib import lib
         sel = torch.empty(lib().pfst_src_sim_select_bytes() // 8 + 1, dtype=torch.int64, device=DEV)
         hg = gt.shape[-1]
-        ops.call('pfst_src_sim_select', sim.to(DEV).data_ptr(), gt8.data_ptr(), n, H, H, hg, hg, 2, float(perc), sel.data_ptr(), 0)
+        ops.call('pfst_src_sim_select', sim.to(DEV).data_ptr(), gt8.data_ptr(), n, H, H, hg, hg, 3, 2, float(perc), sel.data_ptr(), 0)
         stats = torch.zeros(6, dtype=torch.float64, device=DEV)
-        ops.call('pfst_src_sim_stats', sim.to(DEV).data_ptr(), gt8.data_ptr(), n, H, H, hg, hg, 2, 0, 0.5, 0.5, stats.data_ptr(), sel.data_ptr(), 0)
+        ops.call('pfst_src_sim_stats', sim.to(DEV).data_ptr(), gt8.data_ptr(), n, H, H, hg, hg, 3, 2, 0, 0.5, 0.5, stats.data_ptr(), sel.data_ptr(), 0)
         full = torch.zeros(6, dtype=torch.float64, device=DEV)
-        ops.call('pfst_src_sim_stats', sim.to(DEV).data_ptr(), gt8.data_ptr(), n, H, H, hg, hg, 2, 0, 0.5, 0.5, full.data_ptr(), 0, 0)
+        ops.call('pfst_src_sim_stats', sim.to(DEV).data_ptr(), gt8.data_ptr(), n, H, H, hg, hg, 3, 2, 0, 0.5, 0.5, full.data_ptr(), 0, 0)
         torch.cuda.synchronize()
         for o in (0, 3):
             assert abs(float(stats[o]) - int(float(full[o]) * perc)) < 1e-3, (perc, o, float(stats[o]), float(full[o]))

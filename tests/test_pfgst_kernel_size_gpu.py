@@ -1,6 +1,7 @@
-"""PFGSTLoss at kernel_size 3 / 5 / 7 and top_k up to kernel_size^2 - 1 on the GPU: every `_k` entry of the C ABI against plain torch
-(fp64), the `_k` entries at K = 3 against the 3x3 entries (exact ties included), the PFGSTLoss module against the executed reference's
-vectors (tests/golden/pfgst_kernel_size.npz), one whole train step at kernel_size 5 against the oracle, and deterministic mode."""
+"""PFGSTLoss at kernel_size 3 / 5 / 7 and top_k up to kernel_size^2 - 1 on the GPU: every entry of the C ABI that takes `ksize` against
+plain torch (fp64), the two similarity-map implementations at K = 3 against each other, the top-k selection under exact ties against a
+stable sort, the PFGSTLoss module against the executed reference's vectors (tests/golden/pfgst_kernel_size.npz), one whole train step
+at kernel_size 5 against the oracle, and deterministic mode."""
 import os
 import random
 
@@ -67,7 +68,7 @@ def t_valid(gt, mix, H, W, K, d):
     return all_in & (g != 255), all_in
 
 
-# ---------------------------------------------------------------------------------------------------------------------------- _k vs torch
+# ----------------------------------------------------------------------------------------------------------------- K x K vs torch
 KD = [(K, d) for K in (3, 5, 7) for d in (1, 2, 3)]
 
 
@@ -191,17 +192,25 @@ def test_out_of_range_arguments_are_refused(ops):
     cnt = torch.zeros(1, dtype=torch.int64, device=DEV)
     out = torch.empty(2, device=DEV)
     with pytest.raises(PfstHipError):
-        ops.call('pfst_sim_loss_finalize_k', acc.data_ptr(), cnt.data_ptr(), 5, 25, 0.1, 0.1, out.data_ptr(), 0)
+        ops.call('pfst_sim_loss_finalize', acc.data_ptr(), cnt.data_ptr(), 5, 25, 0.1, 0.1, out.data_ptr(), 0)
+    prob = torch.softmax(torch.randn(1, 6, 16, 16, device=DEV), 1)
+    valid = torch.zeros(1, 1, 16, 16, dtype=torch.uint8, device=DEV)
+    for K, top_k in ((4, 1), (3, 9)):                 # an even kernel; top_k beyond K^2 - 1
+        ema, gP = torch.zeros(1, K * K, 16, 16, device=DEV), torch.empty(1, K * K, 16, 16, device=DEV)
+        with pytest.raises(PfstHipError):
+            ops.call('pfst_sim_topk_loss', ema.data_ptr(), prob.data_ptr(), valid.data_ptr(), cnt.data_ptr(), 1, 6, 16, 16, K, 1, top_k,
+                     0.1, 0.1, gP.data_ptr(), acc.data_ptr(), 0, 0)
 
 
-# ------------------------------------------------------------------------------------------------------ _k at K = 3 vs the 3x3 entries
+# ------------------------------------------------------------------------------------- the two similarity maps at K = 3 against each other
 @pytest.mark.parametrize('d', [1, 2, 3])
 @pytest.mark.parametrize('sim_type', ['cosine', 'gaussian'])
 def test_k3_entries_match_the_3x3_entries(ops, d, sim_type):
-    """same inputs, exact ties included (duplicated feature columns give similarities equal to the centre tap's): labels, masks,
-    counts and the top-k gradients equal, floats within 1e-6 of each other"""
+    """pfst_sim_map / _bwd (3x3 strip and generic kernels) against pfst_sim_map_k / _bwd_k (halo tiles) at K = 3, the one job of the
+    loss with two implementations: same inputs, exact ties included (duplicated feature columns give similarities equal to the
+    centre tap's), floats within 1e-6 of each other"""
     gen = torch.Generator().manual_seed(40 + d)
-    n, C, H, W, Cc = 2, 64, 32, 64, 6                      # W = 64: the 3x3 cosine entry takes its strip kernel at d = 1, 2
+    n, C, H, W = 2, 64, 32, 64                             # W = 64: the 3x3 cosine entry takes its strip kernel at d = 1, 2
     x = torch.randn(n, C, H, W, generator=gen)
     x[:, :, :, 6] = x[:, :, :, 5]
     x[:, :, 9, :] = x[:, :, 8, :]
@@ -218,46 +227,56 @@ def test_k3_entries_match_the_3x3_entries(ops, d, sim_type):
     ops.call('pfst_sim_map_bwd_k', xf.data_ptr(), s3.data_ptr(), n3.data_ptr(), gs.data_ptr(), n, C, H, W, 3, d, ops.SIM_TYPES[sim_type], sigma,
              bk.data_ptr(), 0, coef.data_ptr(), 0)
     assert rel_err(bk, b3) < 1e-6
-    gt, mix = labels(n, H, W, 9 + d)
-    gt8, mm8 = ops.to_u8(gt.to(DEV)), ops.to_u8(mix.to(DEV))
-    hg, wg = gt.shape[-2:]
-    for perc in (None, 0.5):
-        l3, g3 = ops.src_sim_losses(s3, gt8, d, *W4, src_perc=perc)
-        sel = None
-        if perc is not None:
-            from pfst_amd._lib import lib
-            sel = torch.empty(lib().pfst_src_sim_select_bytes() // 8 + 1, dtype=torch.int64, device=DEV)
-            ops.call('pfst_src_sim_select_k', s3.data_ptr(), gt8.data_ptr(), n, H, W, hg, wg, 3, d, perc, sel.data_ptr(), 0)
-        stats = torch.empty(6, dtype=torch.float64, device=DEV)
-        ops.call('pfst_src_sim_stats_k', s3.data_ptr(), gt8.data_ptr(), n, H, W, hg, wg, 3, d, 0, 0.5, 0.5, stats.data_ptr(),
-                 0 if sel is None else sel.data_ptr(), 0)
-        gk, lk = torch.empty_like(s3), torch.empty(4, device=DEV)
-        ops.call('pfst_src_sim_grad_k', s3.data_ptr(), gt8.data_ptr(), n, H, W, hg, wg, 3, d, 0, 0.5, 0.5, stats.data_ptr(), *W4,
-                 gk.data_ptr(), lk.data_ptr(), 0 if sel is None else sel.data_ptr(), 0)
-        assert rel_err(lk, l3) < 1e-6 and rel_err(gk, g3) < 1e-6, perc
-        assert torch.equal(gk == 0, g3 == 0)                # the same pairs (and, with src_perc, the same selection)
-    v3, a3, c3 = ops.trg_valid_mask(gt8, mm8, (H, W), d)
-    vk, ak = torch.empty_like(v3), torch.empty_like(a3)
-    ck = torch.empty(1, dtype=torch.int64, device=DEV)
-    ops.call('pfst_trg_valid_mask_k', gt8.data_ptr(), mm8.data_ptr(), n, H, W, hg, wg, 3, d, vk.data_ptr(), ak.data_ptr(), ck.data_ptr(), 0)
-    assert torch.equal(vk, v3) and torch.equal(ak, a3) and int(ck) == int(c3) > 1
-    prob = torch.softmax(torch.randn(n, Cc, H, W, generator=gen), 1).to(DEV)
-    ties = int((s3.unsqueeze(1) == s3.unsqueeze(2)).sum()) - s3.numel()
+
+
+# ------------------------------------------------------------------------------------------------- top-k selection under exact ties
+@pytest.mark.parametrize('K', [3, 5])
+def test_topk_selection_under_exact_ties_against_torch(ops, K):
+    """similarities on a grid of 21 values, so that most pixels hold equal taps: the selected sets must be those of a STABLE descending
+    sort (the lower tap index first on ties), for disjoint and overlapping top / bottom sets and for all pairs.  gP and g_sim within
+    1e-6 of the oracle's values (the same fp32 expressions), the losses within 1e-5, and for disjoint sets the zero pattern of g_sim
+    equal to the oracle's selection"""
+    gen = torch.Generator().manual_seed(60 + K)
+    n, Cc, H, W, d, kk = 2, 6, 22, 26, 2, K * K
+    ema = ((torch.rand(n, kk, H, W, generator=gen) * 2 - 1) * 10).round() / 10
+    ties = int((ema.unsqueeze(1) == ema.unsqueeze(2)).sum()) - ema.numel()
     assert ties > 0, 'the input must hold exact ties'
-    for top_k in (None, 1, 3, 4):
-        o3, gP3, gS3 = ops.sim_topk_loss(s3, prob, v3, c3, d, top_k, 0.3, 0.7, want_sim_grad=True)
-        gPk, gSk = torch.empty_like(gP3), torch.empty_like(gS3)
-        acc, ok = torch.empty(2, dtype=torch.float64, device=DEV), torch.empty(2, device=DEV)
-        ops.call('pfst_sim_topk_loss_k', s3.data_ptr(), prob.data_ptr(), v3.data_ptr(), c3.data_ptr(), n, Cc, H, W, 3, d, int(top_k or 0),
-                 0.3, 0.7, gPk.data_ptr(), acc.data_ptr(), gSk.data_ptr(), 0)
-        ops.call('pfst_sim_loss_finalize_k', acc.data_ptr(), c3.data_ptr(), 3, int(top_k or 0), 0.3, 0.7, ok.data_ptr(), 0)
-        assert torch.equal(gPk, gP3) and torch.equal(gSk, gS3), top_k          # the same selection under ties, the same expressions
-        assert rel_err(ok, o3) < 1e-6, top_k
-        for ug in (0, 1):
-            d3 = ops.cross_prob_bwd_(torch.zeros(n, Cc, 2 * H, 2 * W, device=DEV), prob, gP3, d, 2, bool(ug))
-            dk = torch.zeros_like(d3)
-            ops.call('pfst_cross_prob_bwd_k', prob.data_ptr(), gP3.data_ptr(), n, Cc, H, W, 3, d, 2, ug, dk.data_ptr(), 2 * H, 2 * W, 0)
-            assert rel_err(dk, d3) < 1e-6, (top_k, ug)
+    gt, mix = labels(n, H, W, 11 + K)
+    gt8, mm8 = ops.to_u8(gt.to(DEV)), ops.to_u8(mix.to(DEV))
+    valid, _, cnt = ops.trg_valid_mask(gt8, mm8, (H, W), d, ksize=K)
+    count = int(cnt)
+    assert count > 1, 'the test input must have valid target pixels'
+    vm = valid.cpu().bool()                                                   # [n, 1, H, W]
+    prob = torch.softmax(torch.randn(n, Cc, H, W, generator=gen), 1)          # fp32, the kernel's input
+    P = (prob.double().unsqueeze(2) * unfold(prob.double(), K, d)).sum(1)     # cross-probabilities [n, kk, H, W]
+    Pv = P.float()[vm.expand_as(P)]
+    assert bool((Pv > 0).all()) and bool((1 - Pv > 0).all()), 'prob must be a strict softmax: neither P nor 1 - P is 0'
+    # rank of every tap in a stable descending sort == #{i : s_i > s_j or (s_i == s_j and i < j)}
+    order = torch.sort(ema, dim=1, descending=True, stable=True)[1]
+    rank = torch.empty_like(order).scatter_(1, order, torch.arange(kk).view(1, kk, 1, 1).expand_as(order))
+    si, sj = ema.unsqueeze(2), ema.unsqueeze(1)                               # [n, i, 1, ..], [n, 1, j, ..]
+    lower = torch.arange(kk).view(kk, 1) < torch.arange(kk).view(1, kk)       # i < j
+    assert torch.equal(rank, ((si > sj) | ((si == sj) & lower.view(1, kk, kk, 1, 1))).sum(1))
+    s = ema.double()
+    w_pos, w_neg = 0.3, 0.7
+    half = (kk - 1) // 2
+    for top_k in (None, 1, half, half + 1, kk - 1):
+        if top_k is None:
+            pos, neg, npos, nneg = torch.ones_like(rank, dtype=torch.bool), torch.ones_like(rank, dtype=torch.bool), kk, kk
+        else:
+            pos, neg, npos, nneg = rank <= top_k, rank >= kk - top_k, top_k + 1, top_k
+        pos, neg = pos & vm, neg & vm
+        cpos, cneg = w_pos / (count * npos), w_neg / (count * nneg)
+        want = torch.stack([(-s * P)[pos].sum() * cpos, (-(1 - s) * (1 - P))[neg].sum() * cneg])
+        want_gP = torch.where(pos, -s * cpos, 0.0) + torch.where(neg, (1 - s) * cneg, 0.0)
+        want_gS = torch.where(pos, -P * cpos, 0.0) + torch.where(neg, (1 - P) * cneg, 0.0)
+        out, gP, gS = ops.sim_topk_loss(ema.to(DEV), prob.to(DEV), valid, cnt, d, top_k, w_pos, w_neg, want_sim_grad=True, ksize=K)
+        e = dict(gP=rel_err(gP, want_gP), g_sim=rel_err(gS, want_gS), losses=rel_err(out, want))
+        print(f'K={K} top_k={top_k}: ' + ' '.join(f'{k} {v:.3e}' for k, v in e.items()))
+        assert e['gP'] < 1e-6 and e['g_sim'] < 1e-6, (top_k, e)
+        assert e['losses'] < 1e-5, (top_k, e)
+        if top_k is not None and top_k <= half:             # disjoint sets: a tap is in at most one, and its g_sim term is not 0
+            assert torch.equal(gS.cpu() != 0, pos | neg), top_k
 
 
 # --------------------------------------------------------------------------------------------------------- PFGSTLoss vs the reference
