@@ -507,6 +507,21 @@ int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, int C, int H,
  * count <= 1); top_k as for pfst_sim_topk_loss */
 int pfst_sim_loss_finalize(const double* acc, const unsigned long long* count, int ksize, int top_k, float w_pos, float w_neg, float* out,
                            pfst_stream_t stream);
+/* Pair statistics of a similarity map against a prediction and an annotation: the counters of the reference's PlotStatisticsHook
+ * (rsiseg/core/hook/plot_statistics_hook.py), restated in DESIGN.md 8g.  sim: [N][ksize^2][H][W] as pfst_sim_map / pfst_sim_map_k write it;
+ * pred [N][Hp][Wp] and gt [N][Hg][Wg] uint8 (gt 255 = ignore), nearest-sampled to H x W.  A centre pixel counts when all its ksize^2 taps lie
+ * inside the map and its gt is not 255.  edges: bins + 1 ascending floats on the device, 1 <= bins <= 256.
+ * counters (unsigned 64-bit, ADDED to, never cleared here), pfst_sim_pair_stats_counters(ksize, bins) of them, in this order:
+ *   hist[4][bins + 2]   per case 0 (1a: pred same, gt same), 1 (1b: pred same, gt different), 2 (2b: both different), 3 (2a: pred different,
+ *                       gt same) the similarities of (correctly predicted centre, non-centre tap with gt != 255): slot #{edges <= s} - 1,
+ *                       s == edges[bins] in the last bin; slot bins: s < edges[0]; slot bins + 1: s > edges[bins] (or NaN)
+ *   rank[ksize^2 - 1][2] per rank of a non-centre tap in its centre's order (descending similarity, stable, lower tap first on ties, as
+ *                       pfst_sim_topk_loss): [0] taps with the centre's gt, [1] taps with another gt; taps with gt 255 keep their rank and
+ *                       count nowhere
+ *   n_centres, n_correct_centres */
+int pfst_sim_pair_stats_counters(int ksize, int bins);
+int pfst_sim_pair_stats(const float* sim, const unsigned char* pred, const unsigned char* gt, int N, int H, int W, int Hp, int Wp, int Hg, int Wg,
+                        int ksize, int dil, const float* edges, int bins, unsigned long long* counters, pfst_stream_t stream);
 
 /* ---- EMA teacher + AdamW + SGD on flat parameter arenas (pfgst.py:105-127, torch.optim.AdamW / SGD) ------ */
 int pfst_ema_update(float* teacher, const float* student, long long n, float alpha, pfst_stream_t stream);

@@ -912,6 +912,96 @@ __global__ void sim_loss_finalize_kernel(const double* __restrict__ acc, const u
   out[1] = cnt > 1.0 ? (float)((double)w_neg * acc[1] / (cnt * (top_k == 0 ? kk : top_k))) : 0.f;
 }
 
+// ---- pair statistics of a similarity map against a prediction and an annotation (the counters of the reference's
+// PlotStatisticsHook, rsiseg/core/hook/plot_statistics_hook.py, restated): for every centre pixel whose K^2 taps all lie inside the map
+// (trg_valid_kernel's rule) and whose annotation is not 255,
+//   rank[r][same ? 0 : 1] += 1 for the non-centre tap at rank r of the centre's similarity order (topk_loss_kernel's order: descending,
+//                            stable, the centre excluded by index), unless that tap's annotation is 255;
+//   hist[case][bin(s)]    += 1 for the same taps when the centre's prediction equals its annotation, case = 0 (1a) pred same & gt same,
+//                            1 (1b) pred same & gt different, 2 (2b) both different, 3 (2a) pred different & gt same.
+// counters: hist[4][bins + 2] (slot `bins`: s < lo, slot bins + 1: s > hi or NaN), rank[K^2 - 1][2], n_centres, n_correct_centres.
+// One thread per pixel, grid-stride over the image's pixels; the block's counters live in LDS (32-bit, LDS atomics) and every non-zero one
+// is added to the 64-bit global counters once at the end.  A 32-bit block counter cannot wrap: a counter gets at most one count per
+// (pixel, tap), i.e. <= 48 * (pixels of the block), and the host refuses launches whose blocks would see 2^32 / 48 pixels (with 2048
+// blocks that is a similarity map of 1.8e11 pixels = 6.6 TB at K = 3, more than the device holds).
+constexpr int SPS_MAX_BINS = 256;
+constexpr int SPS_MAX_COUNTERS = 4 * (SPS_MAX_BINS + 2) + 2 * 48 + 2;
+
+// bin of lo <= v <= hi: #{edges <= v} - 1, v == hi into the last bin (np.histogram with explicit edges).  The guess from the mean bin
+// width is walked to the exact bin against the neighbouring edges, so the result is the definition's whatever the guess's rounding.
+__device__ __forceinline__ int sps_bin(float v, const float* __restrict__ e, int bins, float scale) {
+  const float t = (v - e[0]) * scale;
+  int b = t >= (float)bins ? bins - 1 : (t > 0.f ? (int)t : 0);
+  while (b > 0 && v < e[b]) --b;
+  while (b < bins - 1 && v >= e[b + 1]) ++b;
+  return b;
+}
+
+// grid: (blocks over H*W, N), about 2048 blocks in all (sps_blocks), 256 threads
+template <int K>
+__global__ __launch_bounds__(256) void sim_pair_stats_kernel(const float* __restrict__ sim, const unsigned char* __restrict__ pred,
+                                                             const unsigned char* __restrict__ gt, int H, int W, int Hp, int Wp,
+                                                             int Hg, int Wg, int dil, const float* __restrict__ edges, int bins,
+                                                             unsigned long long* __restrict__ counters) {
+  constexpr int R = K / 2, KK = K * K, CTR = KK / 2;
+  __shared__ unsigned int cnt[SPS_MAX_COUNTERS];
+  __shared__ float ed[SPS_MAX_BINS + 1];
+  const int hs = bins + 2, rank0 = 4 * hs, ncnt = rank0 + 2 * (KK - 1) + 2;
+  for (int i = threadIdx.x; i < ncnt; i += blockDim.x) cnt[i] = 0u;
+  for (int i = threadIdx.x; i <= bins; i += blockDim.x) ed[i] = edges[i];
+  __syncthreads();
+  const float lo = ed[0], hi = ed[bins], scale = (float)bins / (hi - lo);
+  const int n = blockIdx.y, HW = H * W, reach = R * dil;
+  const float sgy = (float)Hg / (float)H, sgx = (float)Wg / (float)W, spy = (float)Hp / (float)H, spx = (float)Wp / (float)W;
+  const unsigned char* g = gt + (i64)n * Hg * Wg;
+  const unsigned char* pr = pred + (i64)n * Hp * Wp;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const int y = p / W, x = p - y * W;
+    if (y < reach || y >= H - reach || x < reach || x >= W - reach) continue;      // a tap outside the map
+    const int gc = g[(i64)nearest_src(y, sgy, Hg) * Wg + nearest_src(x, sgx, Wg)];
+    if (gc == 255) continue;
+    const int pc = pr[(i64)nearest_src(y, spy, Hp) * Wp + nearest_src(x, spx, Wp)];
+    const bool correct = pc == gc;
+    atomicAdd(&cnt[ncnt - 2], 1u);
+    if (correct) atomicAdd(&cnt[ncnt - 1], 1u);
+    const i64 base = (i64)n * KK * HW + p;
+    float s[KK];                 // indexed by compile-time constants alone (the run-time tap's value is read again, an L1 hit)
+#pragma unroll
+    for (int k = 0; k < KK; ++k) s[k] = sim[base + (i64)k * HW];
+    for (int j = 0; j < KK; ++j) {
+      if (j == CTR) continue;
+      const int sy = y + (j / K - R) * dil, sx = x + (j % K - R) * dil;
+      const int gj = g[(i64)nearest_src(sy, sgy, Hg) * Wg + nearest_src(sx, sgx, Wg)];
+      if (gj == 255) continue;    // keeps its place in the order (it is in s[]), counts nowhere
+      const float sj = sim[base + (i64)j * HW];
+      int rank = 0;
+#pragma unroll
+      for (int i = 0; i < KK; ++i)
+        if (i != CTR) rank += (s[i] > sj || (s[i] == sj && i < j)) ? 1 : 0;
+      const bool gsame = gj == gc;
+      atomicAdd(&cnt[rank0 + 2 * rank + (gsame ? 0 : 1)], 1u);
+      if (!correct) continue;
+      const int pj = pr[(i64)nearest_src(sy, spy, Hp) * Wp + nearest_src(sx, spx, Wp)];
+      const int cs = pj == pc ? (gsame ? 0 : 1) : (gsame ? 3 : 2);
+      const int slot = sj < lo ? bins : (!(sj <= hi) ? bins + 1 : sps_bin(sj, ed, bins, scale));
+      atomicAdd(&cnt[cs * hs + slot], 1u);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncnt; i += blockDim.x) {
+    const unsigned int c = cnt[i];
+    if (c) atomicAdd(&counters[i], (unsigned long long)c);
+  }
+}
+
+// blocks per image of the pair statistics: about 2048 in all, so that a block sees enough pixels to amortise its counter flush
+inline int sps_blocks(i64 hw, int N) {
+  i64 g = (hw + 255) / 256;
+  const i64 cap = 2048 / N > 1 ? 2048 / N : 1;
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : (int)g;
+}
+
 inline int px_blocks(i64 n) {
   i64 g = (n + 255) / 256;
   if (g > 4096) g = 4096;
@@ -1128,6 +1218,26 @@ extern "C" int pfst_sim_loss_finalize(const double* acc, const unsigned long lon
                                       float* out, pfst_stream_t stream) {
   PFST_CHECK_ARG(acc && count && out && ksize_ok(ksize) && top_k >= 0 && top_k <= ksize * ksize - 1);
   hipLaunchKernelGGL(sim_loss_finalize_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, acc, count, ksize * ksize, top_k, w_pos, w_neg, out);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_sim_pair_stats_counters(int ksize, int bins) {
+  PFST_CHECK_ARG(ksize_ok(ksize) && bins >= 1 && bins <= SPS_MAX_BINS);
+  return 4 * (bins + 2) + 2 * (ksize * ksize - 1) + 2;
+}
+
+extern "C" int pfst_sim_pair_stats(const float* sim, const unsigned char* pred, const unsigned char* gt, int N, int H, int W, int Hp, int Wp,
+                                   int Hg, int Wg, int ksize, int dil, const float* edges, int bins, unsigned long long* counters,
+                                   pfst_stream_t stream) {
+  PFST_CHECK_ARG(sim && pred && gt && edges && counters && N > 0 && N <= 65535 && H > 0 && W > 0 && Hp > 0 && Wp > 0 && Hg > 0 && Wg > 0 &&
+                 dil >= 1 && ksize_ok(ksize));
+  PFST_CHECK_ARG(bins >= 1 && bins <= SPS_MAX_BINS && (i64)H * W <= 0x7fffffff && (reinterpret_cast<uintptr_t>(counters) & 7) == 0);
+  const int gx = sps_blocks((i64)H * W, N);
+  // pixels one block walks, times the 48 counts a pixel can add to one counter: below 2^32 (see the kernel's comment)
+  PFST_CHECK_ARG((((i64)H * W + gx - 1) / gx) * 48 < (1LL << 32));
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(sim_pair_stats_kernel<K_>, dim3(gx, N), dim3(256), 0, (hipStream_t)stream, sim, pred, gt, H, W,
+                                              Hp, Wp, Hg, Wg, dil, edges, bins, counters));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }

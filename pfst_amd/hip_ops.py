@@ -1299,6 +1299,30 @@ def cross_prob_bwd_(dlogits, prob, gP, dil, ds, unfold_grad=False, ksize=3):
     return dlogits
 
 
+def sim_pair_stats_counters(ksize, bins):
+    """length of the counter tensor of sim_pair_stats: hist[4][bins + 2], rank[ksize^2 - 1][2], n_centres, n_correct_centres"""
+    n = lib().pfst_sim_pair_stats_counters(int(ksize), int(bins))
+    if n < 0:
+        raise ValueError(f'sim_pair_stats: kernel size {ksize} (3 | 5 | 7) / bins {bins} (1 .. 256)')
+    return n
+
+
+def sim_pair_stats(sim, pred_u8, gt_u8, dil, ksize, edges, counters):
+    """pfst_sim_pair_stats: ADDS the pair statistics of sim [N, ksize^2, H, W] against pred_u8 [N, Hp, Wp] and gt_u8 [N, Hg, Wg] (255 =
+    ignore; both nearest-sampled to H x W) to `counters` (int64, sim_pair_stats_counters(ksize, len(edges) - 1) entries, layout in
+    include/pfst_hip.h); edges: float32 [bins + 1] on the device.  -> counters"""
+    _dense(sim), _dense(pred_u8, U8), _dense(gt_u8, U8), _dense(edges), _dense(counters, I64)
+    n, kk, h, w = sim.shape
+    bins = edges.numel() - 1
+    if kk != ksize * ksize or pred_u8.dim() != 3 or gt_u8.dim() != 3 or pred_u8.shape[0] != n or gt_u8.shape[0] != n:
+        raise ValueError(f'sim_pair_stats: sim {tuple(sim.shape)}, pred {tuple(pred_u8.shape)}, gt {tuple(gt_u8.shape)} for kernel size {ksize}')
+    if edges.dim() != 1 or counters.dim() != 1 or counters.numel() != sim_pair_stats_counters(ksize, bins):
+        raise ValueError(f'sim_pair_stats: {counters.numel()} counters for kernel size {ksize} and {bins} bins')
+    call('pfst_sim_pair_stats', sim.data_ptr(), pred_u8.data_ptr(), gt_u8.data_ptr(), n, h, w, pred_u8.shape[1], pred_u8.shape[2],
+         gt_u8.shape[1], gt_u8.shape[2], ksize, int(dil), edges.data_ptr(), bins, counters.data_ptr(), _stream())
+    return counters
+
+
 # ---------------------------------------------------------------- flat-arena optimiser steps
 def ema_update_(teacher_flat, student_flat, alpha):
     assert teacher_flat.numel() == student_flat.numel()

@@ -571,6 +571,17 @@ class EncoderDecoder(nn.Module):
         self._last_states = dict(feats=[v.data for v in x], seg_logits=logits.data)
         return lab8, logits.data
 
+    def eval_features(self, img):
+        """One whole-image forward as the test loop runs it (BatchNorm on running statistics, dropout off, no tape) that keeps what the
+        pseudo-feature statistics read (pfst_amd/statistics.py) -> dict(feats=[the four backbone maps], decoded_feats=the ASPP bottleneck
+        output (the head's return_features=True), seg_logits=the low-resolution logits), device tensors.  The logits are those of
+        `inference` on the same input, bit for bit (the same launches)."""
+        self.repack_weights(need_dgrad=False)
+        with bn_eval():
+            x = self.extract_feat(img.contiguous(), None)
+            logits, decoded = self.decode_head(x, return_features=True, tape=None, training=False)
+        return dict(feats=[v.data for v in x], decoded_feats=decoded.data, seg_logits=logits.data)
+
     def simple_test(self, img, img_meta=None, rescale=True):
         """-> (list of per-image label maps, list of per-image state dicts), the fork's contract (encoder_decoder.py:329-353; consumed as
         `result, state = model(return_loss=False, **data)` by apis/test.py:97).  The states hold the backbone features and the low-res
