@@ -538,6 +538,29 @@ int pfst_sgd_step(float* p, const float* g, float* buf, long long n, float lr, f
 /* out[0] = loss_weight*acc[0]/numel ; out[1] = 100*(acc[1]+eps)/(acc[2]+eps) ; out[2] = acc[3] (count of invalid labels) */
 int pfst_ce_finalize(const double* acc, double numel, float loss_weight, float* out, pfst_stream_t stream);
 
+/* ---- fused bilinear upsample + softmax + Dice loss (losses/dice_loss.py behind decode_head.py:249-283) ----
+ * p = softmax(up(logits)), t = one_hot(min(label, C-1)), valid = label != ignore_index (the LOSS's); per image n and class c
+ *   I = sum valid*t_c*p_c,  P = sum p_c^e,  T = sum t_c  (P, T over every pixel);  num = 2I + smooth, den = P + T + smooth,
+ *   loss = loss_weight/C * sum_{c != ignore_index} cw_c * mean_n (1 - num/den).
+ * form: 0 = generic kernels (any H x W, C <= 255), 4 / 8 = inter-cell block kernels (H == form*h, W == form*w, C <= 8, lse 8-byte and
+ * label 2-byte aligned).  Exactly one of lse_in (read: the CE term's) and lse_out[N][H][W] (written) is set.  Every workgroup STORES one row
+ * of partials, no atomics: slab[N][blocks][C][2] = (I, P), counts[N][blocks][C+3] = (T per class, #correct, #valid, #bad labels), the last
+ * three as pfst_ce_upsample_fwd counts them under head_ignore_index (bad: label >= C that is neither ignore index).
+ * blocks: form 0: ceil(H*W/1024); form 4: ceil((w+1)/16)*ceil((h+1)/32); form 8: ceil((w+1)/16)*ceil((h+1)/16). */
+int pfst_dice_upsample_fwd(const float* logits, int N, int C, int h, int w, const unsigned char* label, int H, int W,
+                           int ignore_index, int head_ignore_index, float exponent, int form, const float* lse_in, float* lse_out,
+                           double* slab, long long* counts, int blocks, pfst_stream_t stream);
+/* adds the rows in a fixed order: sums[N*C*3 + 3] = (I, P, T) per (n, c), then (#correct, #valid, #bad);
+ * coef[N][C][2] = (a, b) = (k*2/den, k*e*num/den^2), k = cw_c/(C*N), zeros for c == ignore_index; out[3] laid out as pfst_ce_finalize's */
+int pfst_dice_finalize(const double* slab, const long long* counts, int N, int C, int blocks, const float* class_weight,
+                       int ignore_index, double smooth, double exponent, double loss_weight, double* sums, float* coef, float* out,
+                       pfst_stream_t stream);
+/* dlogits (+)= scale * adjoint of the resize applied to p_c*(g_c - sum_k g_k p_k), g_c = -a*valid*t_c + b*p_c^(e-1); gather form, no
+ * atomics.  work[N][H][W] is needed by the generic form at C > 8 only. */
+int pfst_dice_upsample_bwd(const float* logits, int N, int C, int h, int w, const unsigned char* label, int H, int W,
+                           int ignore_index, float exponent, int form, const float* lse, const float* coef, float scale,
+                           float* work, float* dlogits, int accumulate, pfst_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,23 +8,10 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "common.h"
+#include "bilin.h"
 #include "../../include/pfst_hip.h"
 
 namespace {
-
-struct Bilin {
-  int y0, y1, x0, x1;
-  float ly0, ly1, lx0, lx1;
-};
-__device__ __forceinline__ Bilin make_bilin(int oy, int ox, float sh, float sw, int h, int w) {
-  Bilin b;
-  bilin_src(oy, sh, h, b.y0, b.y1, b.ly0, b.ly1);
-  bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-  return b;
-}
-__device__ __forceinline__ float interp(const float* __restrict__ p, int w, const Bilin& b) {
-  return bilin_blend(p[b.y0 * w + b.x0], p[b.y0 * w + b.x1], p[b.y1 * w + b.x0], p[b.y1 * w + b.x1], b.lx0, b.lx1, b.ly0, b.ly1);
-}
 
 // grid: (blocks over H*W, N).  One thread per full-resolution pixel.
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, int C, int h, int w,

@@ -1146,6 +1146,73 @@ def ce_finalize(acc, numel, loss_weight):
     return out
 
 
+def dice_form(logits, label_u8, lse=None, generic=False):
+    """which kernels a Dice term runs on: 4 / 8 = the inter-cell block kernels of that ratio (C <= 8, H == S h, W == S w, lse 8-byte and
+    label 2-byte aligned), 0 = the generic ones; generic=True forces 0 (tests compare the two forms on one shape).
+    -> (form, rows of partials per image)"""
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    for s, tile_rows in ((4, 32), (8, 16)):
+        if (not generic and c <= 8 and H == s * h and W == s * w and label_u8.data_ptr() % 2 == 0 and h < 65535 * 15
+                and (lse is None or lse.data_ptr() % 8 == 0)):
+            return s, ((w + 16) // 16) * ((h + tile_rows) // tile_rows)
+    return 0, (H * W + 1023) // 1024
+
+
+def dice_upsample_fwd(logits, label_u8, ignore_index=255, head_ignore_index=255, exponent=2.0, lse=None, generic=False):
+    """Per-workgroup partials of the Dice sums of softmax(up(logits)) and the head's accuracy counts; no atomics, a fixed order.
+    lse: the CE term's log-sum-exp of the same logits (then nothing is written per pixel), or None (formed here: the same bits).
+    -> (slab float64 [N, blocks, C, 2] = (I, P), counts int64 [N, blocks, C + 3] = (T per class, #correct, #valid, #bad), lse, form)"""
+    _dense(logits), _dense(label_u8, U8)
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    assert label_u8.numel() == n * H * W
+    if not float(exponent) >= 1.0:
+        raise ValueError(f'DiceLoss: exponent must be >= 1 (p^(e-1) at p -> 0 is not finite below), got {exponent}')
+    own = lse is None
+    if own:
+        lse = torch.empty(n, H, W, device=logits.device)
+    else:
+        assert _dense(lse).numel() == n * H * W
+    form, blocks = dice_form(logits, label_u8, lse, generic)
+    slab = torch.empty(n, blocks, c, 2, dtype=F64, device=logits.device)
+    counts = torch.empty(n, blocks, c + 3, dtype=I64, device=logits.device)
+    call('pfst_dice_upsample_fwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), H, W, int(ignore_index), int(head_ignore_index),
+         float(exponent), form, 0 if own else lse.data_ptr(), lse.data_ptr() if own else 0, slab.data_ptr(), counts.data_ptr(),
+         blocks, _stream())
+    return slab, counts, lse, form
+
+
+def dice_finalize(slab, counts, class_weight=None, ignore_index=255, smooth=1.0, exponent=2.0, loss_weight=1.0):
+    """adds the partials in a fixed order -> (out float32[3] = (loss, acc_seg %, #bad labels), coef float32 [N, C, 2] = the gradient's
+    (a, b) table, sums float64 [N*C*3 + 3] = (I, P, T) per (n, c), then (#correct, #valid, #bad))"""
+    n, blocks, c, _ = slab.shape
+    assert tuple(counts.shape) == (n, blocks, c + 3)
+    if class_weight is not None:
+        assert _dense(class_weight).numel() == c
+    sums = torch.empty(n * c * 3 + 3, dtype=F64, device=slab.device)
+    coef = torch.empty(n, c, 2, device=slab.device)
+    out = torch.empty(3, device=slab.device)
+    call('pfst_dice_finalize', slab.data_ptr(), counts.data_ptr(), n, c, blocks, _p(class_weight), int(ignore_index), float(smooth),
+         float(exponent), float(loss_weight), sums.data_ptr(), coef.data_ptr(), out.data_ptr(), _stream())
+    return out, coef, sums
+
+
+def dice_upsample_bwd(logits, label_u8, lse, coef, scale, ignore_index=255, exponent=2.0, out=None, accumulate=False, generic=False):
+    """d logits of the Dice term (gather form, no atomics); `scale` carries loss_weight and the step's gradient scale"""
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    if out is None:
+        assert not accumulate
+        out = torch.empty_like(logits)
+    assert tuple(coef.shape) == (n, c, 2) and _dense(lse).numel() == n * H * W
+    form, _ = dice_form(logits, label_u8, lse, generic)
+    work = torch.empty(n, H, W, device=logits.device) if form == 0 and c > 8 else None
+    call('pfst_dice_upsample_bwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), H, W, int(ignore_index), float(exponent), form,
+         lse.data_ptr(), _dense(coef).data_ptr(), float(scale), _p(work), _dense(out).data_ptr(), int(accumulate), _stream())
+    return out
+
+
 def pseudo_label(logits, size, threshold, want_i64=True, want_conf=False, want_prob=False):
     """-> (label int64 [N,H,W] | None, label uint8 [N,H,W], count uint64-as-int64 [1][, conf float [N,H,W]][, max prob float [N,H,W]])"""
     _dense(logits)

@@ -215,14 +215,17 @@ class CrossEntropyLoss(nn.Module):
             self._cw = torch.tensor(self.class_weight, dtype=torch.float32, device=dev)
         return self._cw
 
-    def fused(self, logits, label_u8, weight, tape, ignore_index=255, grad_scale=1.0):
+    def fused(self, logits, label_u8, weight, tape, ignore_index=255, grad_scale=1.0, share=None):
         """logits: Var [N,C,h,w] (low res); label_u8 [N,1,H,W] or [N,H,W]; weight [N,H,W] or None.
-        -> device tensor [loss, acc_seg]"""
+        share: a dict the terms of one head's loss list pass along -- the log-sum-exp map is left in it for a DiceLoss that follows.
+        -> device tensor [loss, acc_seg, #bad labels]"""
         ld = logits.data
         n = ld.shape[0]
         H, W = label_u8.shape[-2:]
         cw = self._cw_dev(ld.device)
         lse, acc = ops.ce_upsample_fwd(ld, label_u8, weight, cw, ignore_index)
+        if share is not None:
+            share['lse'] = lse
         out = ops.ce_finalize(acc, n * H * W, self.loss_weight)
         if tape is not None:
             scale = grad_scale * self.loss_weight / float(n * H * W)
@@ -235,6 +238,54 @@ class CrossEntropyLoss(nn.Module):
         return out
 
 
+@LOSSES.register_module()
+class DiceLoss(nn.Module):
+    """losses/dice_loss.py fused with the bilinear up-sampling of the logits (csrc/dice_loss.hip; the closed form: DESIGN.md section 8h).
+    The reference's quirks are kept: the head's `weight=` and `ignore_index=` are swallowed (a Dice term sees neither the pixel weights
+    nor the head's ignore_index, only its OWN), an ignored label is clamped to class C - 1 and counted in the denominator, a class index
+    equal to ignore_index is skipped while the divisor stays C, and `reduction` has no effect (dice_loss reduces a scalar).
+    exponent >= 1 only: p^(e-1) at p -> 0 is not finite below."""
+
+    def __init__(self, smooth=1, exponent=2, reduction='mean', class_weight=None, loss_weight=1.0, ignore_index=255,
+                 loss_name='loss_dice', **kwards):
+        super().__init__()
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError(f"DiceLoss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        if not float(exponent) >= 1.0:
+            raise ValueError(f'DiceLoss: exponent must be >= 1, got {exponent!r}')
+        self.smooth, self.exponent, self.reduction = smooth, exponent, reduction
+        self.class_weight = get_class_weight(class_weight)
+        self.loss_weight = loss_weight
+        self.ignore_index = 255 if ignore_index is None else ignore_index      # no label is None: uint8 label maps, 255 = "no class index"
+        self._loss_name = loss_name
+        self._cw = None
+
+    loss_name = CrossEntropyLoss.loss_name
+    _cw_dev = CrossEntropyLoss._cw_dev
+
+    def fused(self, logits, label_u8, weight, tape, ignore_index=255, grad_scale=1.0, share=None):
+        """the interface of CrossEntropyLoss.fused; `weight` is ignored and `ignore_index` (the head's) only selects the pixels of acc_seg.
+        -> device tensor [loss, acc_seg, #bad labels]"""
+        ld = logits.data
+        if self.class_weight is not None and len(self.class_weight) != ld.shape[1]:
+            raise ValueError(f'DiceLoss: class_weight has {len(self.class_weight)} entries for {ld.shape[1]} classes')
+        cw = self._cw_dev(ld.device)
+        ign, e = self.ignore_index, float(self.exponent)
+        slab, counts, lse, _ = ops.dice_upsample_fwd(ld, label_u8, ign, ignore_index, e, lse=None if share is None else share.get('lse'))
+        if share is not None:
+            share['lse'] = lse
+        out, coef, _ = ops.dice_finalize(slab, counts, cw, ign, self.smooth, e, self.loss_weight)
+        if tape is not None:
+            scale = grad_scale * self.loss_weight
+
+            def bwd():
+                buf, accf = logits.grad_target()
+                ops.dice_upsample_bwd(ld, label_u8, lse, coef, scale, ign, e, out=buf, accumulate=accf)
+            tape.record(bwd, dict(op='dice', x=logits, out=None, label=label_u8, class_weight=self.class_weight, loss_weight=scale,
+                                  ignore_index=ign, smooth=self.smooth, exponent=self.exponent))
+        return out
+
+
 class BaseDecodeHead(nn.Module):
     def __init__(self, in_channels, channels, *, num_classes, dropout_ratio=0.1, conv_cfg=None, norm_cfg=None,
                  act_cfg=dict(type='ReLU'), in_index=-1, input_transform=None,
@@ -244,12 +295,16 @@ class BaseDecodeHead(nn.Module):
         _check_norm(norm_cfg)
         if input_transform is not None or sampler is not None or align_corners or conv_cfg is not None:
             raise NotImplementedError('decode head options outside the PFST path')
-        if not isinstance(loss_decode, dict):
-            raise NotImplementedError('a single loss_decode dict is supported')
+        if not isinstance(loss_decode, (dict, list, tuple)):
+            raise TypeError(f'loss_decode must be a dict or a sequence of dicts, but got {type(loss_decode)}')
         self.in_channels, self.channels, self.num_classes = in_channels, channels, num_classes
         self.dropout_ratio, self.in_index, self.ignore_index = dropout_ratio, in_index, ignore_index
         self.align_corners = align_corners
-        self.loss_decode = build_loss(loss_decode)
+        # decode_head.py:84-92: one loss module, or a ModuleList of them in the order given
+        self.loss_decode = build_loss(loss_decode) if isinstance(loss_decode, dict) else nn.ModuleList([build_loss(l) for l in loss_decode])
+        for term in (self.loss_decode if isinstance(self.loss_decode, nn.ModuleList) else [self.loss_decode]):
+            if not hasattr(term, 'fused'):
+                raise NotImplementedError(f'{type(term).__name__} has no fused up-sampling form: it cannot be a loss_decode term')
         self.conv_seg = Conv2dP(channels, num_classes, 1, bias=True)
         nn.init.normal_(self.conv_seg.weight, 0, 0.01)
         self.dropout_enabled = True            # the teacher switches this off (pfgst.py:247-251)
@@ -286,10 +341,23 @@ class BaseDecodeHead(nn.Module):
         return conv_forward(feat, self.conv_seg, tape)
 
     def losses(self, seg_logit, seg_label_u8, seg_weight, tape, grad_scale=1.0):
-        out = self.loss_decode.fused(seg_logit, seg_label_u8, seg_weight, tape, self.ignore_index, grad_scale)
         # '_bad_labels': labels outside [0, C) other than ignore_index (F.cross_entropy raises on them); travels with the packed
         # scalars of the step and is checked on the host after the step's single read (uda.PFGST.forward_train), never logged
-        return {self.loss_decode.loss_name: out[0:1], 'acc_seg': out[1:2], '_bad_labels': out[2:3]}
+        if not isinstance(self.loss_decode, nn.ModuleList):
+            out = self.loss_decode.fused(seg_logit, seg_label_u8, seg_weight, tape, self.ignore_index, grad_scale)
+            return {self.loss_decode.loss_name: out[0:1], 'acc_seg': out[1:2], '_bad_labels': out[2:3]}
+        # decode_head.py:263-283: the terms in order, terms of one loss_name added; acc_seg once per head -- every term counts it from the
+        # same logits and labels under the head's ignore_index (the first one's is kept), every term's bad-label count is added
+        loss, share, first, bad = dict(), dict(), None, None
+        for term in self.loss_decode:
+            out = term.fused(seg_logit, seg_label_u8, seg_weight, tape, self.ignore_index, grad_scale, share=share)
+            name = term.loss_name
+            loss[name] = out[0:1] if name not in loss else loss[name] + out[0:1]
+            first = out if first is None else first
+            bad = out[2:3] if bad is None else bad + out[2:3]
+        loss['acc_seg'] = first[1:2]
+        loss['_bad_labels'] = bad
+        return loss
 
     def forward_train(self, inputs, img_metas, gt_semantic_seg, train_cfg, seg_weight=None, tape=None, grad_scale=1.0):
         seg_logits, feats = self.forward(inputs, return_features=True, tape=tape, training=True)
