@@ -954,6 +954,7 @@ extern "C" int pfst_dwconv3x3_multi_bwd(const float* x, long long x_bs, int ns, 
 extern "C" int pfst_dwconv3x3_wgrad(const float* x, long long x_bs, const float* dy, long long dy_bs, float* dw,
                                     int N, int C, int H, int W, int dil, pfst_stream_t stream) {
   PFST_CHECK_ARG(x && dy && dw && N > 0 && C > 0 && H > 0 && W > 0 && dil >= 1 && N <= 65535 && C <= 65535);
+  PFST_CHECK_ARG(x_bs >= (i64)C * H * W && dy_bs >= (i64)C * H * W);
   const int R = strip_rows(H, W, dil);
   const size_t lds = strip_lds(R, H, W, dil);
   PFST_CHECK_ARG(lds <= 150 * 1024);
