@@ -419,6 +419,27 @@ int pfst_pseudo_label(const float* logits, int N, int C, int h, int w, int H, in
                       long long* label_i64, unsigned char* label_u8, unsigned long long* count, float* conf_mask, float* max_prob,
                       pfst_stream_t stream);
 
+/* ---- offline pseudo-labels with class-wise entropy thresholds (core/hook/pseudo_labeling_hookv4.py:173-205, datasets/pipelines/loading.py:475-494;
+ * DESIGN.md 8i).  logits [N][C][h][w] are resized bilinearly (align_corners=False) to H x W per pixel, in registers (H == h: identity);
+ * p = exp(z - max) / sum.  C <= 255.
+ *   mode 0 (the hook): pred = the first class whose rounded p is maximal, entropy = -sum p log p (a term with p == 0 is 0)
+ *   mode 1 (the loader): pred = the first maximal logit, entropy = -sum p log(p + 1e-8)
+ * Entropies are >= +0, never -0.  ent [N][H][W] float and pred [N][H][W] uint8 may each be NULL (not both). */
+int pfst_entropy_upsample(const float* logits, int N, int C, int h, int w, int H, int W, int mode, float* ent, unsigned char* pred,
+                          pfst_stream_t stream);
+/* One level of an exact radix select over the mode-0 entropies per predicted class: ADDS, for every pixel, one count at
+ * hist[pred][(key >> shift) & ((1 << bits) - 1)], key = the fp32 bit pattern of the entropy (unsigned order = value order).  With prefix
+ * (unsigned 32-bit [C]; needs shift + bits < 32) only pixels with key >> (shift + bits) == prefix[pred] count.  hist: unsigned 64-bit
+ * [C][1 << bits], never cleared here; integer counters, so the result does not depend on launch, image or stream order.  1 <= bits <= 16;
+ * the counting is privatised in LDS where C << bits <= 12288 and goes through global atomics otherwise. */
+int pfst_entropy_class_hist(const float* logits, int N, int C, int h, int w, int H, int W, int shift, int bits, const unsigned int* prefix,
+                            unsigned long long* hist, pfst_stream_t stream);
+/* label [N][H][W] uint8 = mode-1 pred where the mode-1 entropy < thr[pred] (float [C]), else 255; with annotation_space = 1 instead pred + 1
+ * and 0 (files that LoadAnnotations(reduce_zero_label=True) reads back as pred / 255).  counts: unsigned 64-bit [C][2], ADDED to:
+ * (pixels predicted c, pixels kept as c). */
+int pfst_entropy_pseudo_label(const float* logits, int N, int C, int h, int w, int H, int W, const float* thr, int annotation_space,
+                              unsigned char* label, unsigned long long* counts, pfst_stream_t stream);
+
 /* ---- evaluation: intersect_and_union (rsiseg/core/evaluation/metrics.py:26-86).  hist[3*C] (+)= per-class
  * #intersect, #pred, #label over pixels whose label != ignore_index (caller zeroes hist once per evaluation) */
 int pfst_confusion_hist(const unsigned char* pred, const unsigned char* label, long long n, int C, int ignore_index,

@@ -44,12 +44,13 @@ def window_defaults(test_cfg, window=None, stride=None):
     return crop, step
 
 
-def init_segmentor(config, checkpoint=None, device='cuda:0', revise_checkpoint_key=False):
+def init_segmentor(config, checkpoint=None, device='cuda:0', revise_checkpoint_key=False, teacher=False):
     """config: a file name or a Config.  The checkpoint's `state_dict` is loaded as tools/test.py loads it: with `revise_checkpoint_key` the
     DDP `module.` and the UDA wrapper's `model.` prefixes are stripped first (a PFGST checkpoint needs it), and segmentor keys the checkpoint
-    does not have are an error.  The model carries `cfg`, `CLASSES` and `PALETTE` (the checkpoint's meta, else the ISPRS ones)."""
+    does not have are an error.  `teacher`: the EMA teacher of a PFGST checkpoint instead of its student (evaluation.teacher_checkpoint_keys).
+    The model carries `cfg`, `CLASSES` and `PALETTE` (the checkpoint's meta, else the ISPRS ones)."""
     from .data import ISPRS_CLASSES, ISPRS_PALETTE
-    from .evaluation import revise_checkpoint_keys
+    from .evaluation import revise_checkpoint_keys, teacher_checkpoint_keys
     from .registry import build_segmentor
     if isinstance(config, str):
         config = Config.fromfile(config)
@@ -62,7 +63,9 @@ def init_segmentor(config, checkpoint=None, device='cuda:0', revise_checkpoint_k
     if checkpoint is not None:
         ckpt = torch.load(checkpoint, map_location='cpu', weights_only=False)
         sd = ckpt.get('state_dict', ckpt)
-        if revise_checkpoint_key:
+        if teacher:
+            sd = teacher_checkpoint_keys(sd)
+        elif revise_checkpoint_key:
             sd = revise_checkpoint_keys(sd)
         missing = model.load_state_dict(sd, strict=False)
         own = [k for k in missing.missing_keys if not k.endswith('num_batches_tracked')]

@@ -77,6 +77,22 @@ def revise_checkpoint_keys(state_dict, revise_keys=((r'^module\.', ''), ('model.
     return out
 
 
+def teacher_checkpoint_keys(state_dict):
+    """A PFGST checkpoint's teacher as a segmentor state dict: the DDP `module.` prefix stripped, the student's `model.*` keys dropped,
+    `ema_model.` stripped from the teacher's.  The teacher is what labels the target during training, and its BatchNorm buffers are the
+    target domain's."""
+    import re
+    from collections import OrderedDict
+    out = OrderedDict()
+    for k, v in state_dict.items():
+        k = re.sub(r'^module\.', '', k)
+        if k.startswith('ema_model.'):
+            out[k[len('ema_model.'):]] = v
+    if not out:
+        raise ValueError('the checkpoint has no `ema_model.*` keys: it is not a PFGST checkpoint with a teacher')
+    return out
+
+
 AUG_TEST_RATIOS = [0.5, 0.75, 1.0, 1.25, 1.5, 1.75]        # tools/test.py:156-161 of the reference (`--aug-test`)
 
 

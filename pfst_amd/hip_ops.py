@@ -1233,6 +1233,60 @@ def pseudo_label(logits, size, threshold, want_i64=True, want_conf=False, want_p
     return res
 
 
+def _entropy_shape(name, logits, size):
+    _dense(_chk(logits, F32, 4))
+    n, c, h, w = logits.shape
+    H, W = (int(v) for v in size)
+    if not (n >= 1 and 1 <= c <= 255 and h >= 1 and w >= 1 and H >= 1 and W >= 1):
+        raise ValueError(f'{name}: logits {tuple(logits.shape)} (1 .. 255 classes) to size {(H, W)}')
+    return n, c, h, w, H, W
+
+
+def entropy_upsample(logits, size, mode=0, want_entropy=True, want_pred=True):
+    """pfst_entropy_upsample: logits [N, C, h, w] resized to `size` in registers -> (entropy float [N, H, W] | None, pred uint8 [N, H, W] |
+    None).  mode 0: the threshold pass (softmax arg-max, -sum p log p), mode 1: the label pass (logit arg-max, -sum p log(p + 1e-8))."""
+    n, c, h, w, H, W = _entropy_shape('entropy_upsample', logits, size)
+    if mode not in (0, 1) or not (want_entropy or want_pred):
+        raise ValueError(f'entropy_upsample: mode {mode} (0 | 1), and at least one output')
+    ent = torch.empty(n, H, W, device=logits.device) if want_entropy else None
+    pred = torch.empty(n, H, W, dtype=U8, device=logits.device) if want_pred else None
+    call('pfst_entropy_upsample', logits.data_ptr(), n, c, h, w, H, W, int(mode), _p(ent), _p(pred), _stream())
+    return ent, pred
+
+
+def entropy_class_hist(logits, size, shift, bits, hist, prefix=None):
+    """pfst_entropy_class_hist: ADDS one radix level of the per-class entropy keys of logits [N, C, h, w] at `size` to hist (int64 [C, 1 << bits]
+    on the device, unsigned counters): digit (key >> shift) & (2^bits - 1) of the pixels whose higher bits equal prefix[pred] (int32 [C], the
+    unsigned prefixes; None: every pixel).  -> hist"""
+    n, c, h, w, H, W = _entropy_shape('entropy_class_hist', logits, size)
+    shift, bits = int(shift), int(bits)
+    if not (shift >= 0 and 1 <= bits <= 16 and shift + bits <= 32) or (prefix is not None and shift + bits >= 32):
+        raise ValueError(f'entropy_class_hist: shift {shift}, bits {bits} (1 .. 16, shift + bits <= 32, < 32 with a prefix)')
+    if tuple(_dense(hist, I64).shape) != (c, 1 << bits):
+        raise ValueError(f'entropy_class_hist: hist {tuple(hist.shape)} for {c} classes and {bits} bits')
+    if prefix is not None and tuple(_dense(prefix, torch.int32).shape) != (c,):
+        raise ValueError(f'entropy_class_hist: prefix {tuple(prefix.shape)} for {c} classes')
+    call('pfst_entropy_class_hist', logits.data_ptr(), n, c, h, w, H, W, shift, bits, _p(prefix), hist.data_ptr(), _stream())
+    return hist
+
+
+def entropy_pseudo_label(logits, size, thr, annotation_space=False, counts=None):
+    """pfst_entropy_pseudo_label: -> (label uint8 [N, H, W], counts int64 [C, 2]); thr float [C] on the device.  The label is the logit
+    arg-max where the loader's entropy lies below thr[arg-max], else 255 (annotation_space: arg-max + 1, else 0); `counts` (a new zeroed
+    table unless given) += per class (pixels predicted, pixels kept)."""
+    n, c, h, w, H, W = _entropy_shape('entropy_pseudo_label', logits, size)
+    if tuple(_dense(thr).shape) != (c,):
+        raise ValueError(f'entropy_pseudo_label: thr {tuple(thr.shape)} for {c} classes')
+    if counts is None:
+        counts = torch.zeros(c, 2, dtype=I64, device=logits.device)
+    elif tuple(_dense(counts, I64).shape) != (c, 2):
+        raise ValueError(f'entropy_pseudo_label: counts {tuple(counts.shape)} for {c} classes')
+    label = torch.empty(n, H, W, dtype=U8, device=logits.device)
+    call('pfst_entropy_pseudo_label', logits.data_ptr(), n, c, h, w, H, W, thr.data_ptr(), int(bool(annotation_space)), label.data_ptr(),
+         counts.data_ptr(), _stream())
+    return label, counts
+
+
 def label_presence(label_u8):
     _dense(label_u8, U8)
     pres = torch.empty(256, dtype=torch.int32, device=label_u8.device)
