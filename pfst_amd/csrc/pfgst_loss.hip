@@ -671,7 +671,15 @@ __device__ __forceinline__ SrcMoments moments(const double* st) {
   SrcMoments m;
   m.n = st[0];
   m.mean = st[0] > 0 ? st[1] / st[0] : 0.0;
-  const double var = st[0] > 1 ? (st[2] - st[1] * st[1] / st[0]) / (st[0] - 1.0) : 0.0;
+  // One-pass sum of squared deviations: each of its two terms carries a rounding error of up to ~n 2^-53 of sum s^2, so a value below
+  // n 2^-51 sum s^2 cannot be told from noise and counts as 0.  Without this floor a constant set (std exactly 0 in the reference, its
+  // gradient 0 / 0) gave a std of 3.6e-9 (8794 pairs of 0.3f: tests/test_degenerate_batches_gpu.py).
+  // The price: a set whose std is below sqrt(n 2^-51) of its rms -- 2e-6 at 8794 pairs, 1e-5 at the 2e5 pairs of a 64 x 64 grid, where fp32
+  // resolves spreads down to 6e-8 -- reports std 0 and, by the rule for zero variance below, gets no std gradient, although that
+  // gradient (s - mean) / ((n - 1) std) is of ordinary size however small the spread.  Only a collapsed similarity map gets there; a
+  // variance that is exact down to fp32 resolution would need sums shifted by a pivot or a second pass over the pairs.
+  const double ss = st[0] > 1 ? st[2] - st[1] * st[1] / st[0] : 0.0;
+  const double var = ss > st[0] * 0x1p-51 * st[2] ? ss / (st[0] - 1.0) : 0.0;
   m.std = var > 0 ? sqrt(var) : 0.0;
   return m;
 }
