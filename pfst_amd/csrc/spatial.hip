@@ -262,6 +262,13 @@ __global__ void resize_bilinear_bwd_kernel(const float* __restrict__ dy, i64 dy_
   }
 }
 
+// one row of the x2 adjoints' four taps, in the arithmetic of resize_bilinear_bwd_kernel's row loop (a rounded product, then one fused
+// multiply-add per further tap in ascending column order; a zero-weight tap adds nothing, as the tap that loop skips): the three adjoint
+// kernels agree bit for bit, whichever the alignment of a view selects (tests/test_plane_views_gpu.py).  Pinned with intrinsics: left as
+// a * b + c * d + ... the compiler contracted the two x2 kernels' sums into differently grouped fmas
+__device__ __forceinline__ float bilin_row4(const float (&wx)[4], float v0, float v1, float v2, float v3) {
+  return __fmaf_rn(wx[3], v3, __fmaf_rn(wx[2], v2, __fmaf_rn(wx[1], v1, __fmul_rn(wx[0], v0))));
+}
 // exact 2x up-sampling (align_corners=False): output o = 2k reads inputs (k-1: .25, k: .75), o = 2k+1 reads (k: .75, k+1: .25),
 // clamped at the borders -- so input i receives {2i-1: .25, 2i: .75, 2i+1: .75, 2i+2: .25}, with the missing border tap's weight
 // folded onto the edge output (weight 1).  A separable 4x4 gather, one thread per input pixel.   grid: (blocks over Hi*Wi, C, N)
@@ -283,7 +290,7 @@ __global__ __launch_bounds__(256) void resize_bilinear2x_bwd_kernel(const float*
       const float* row = gp + (i64)oy * Wo + 2 * ix;
       const float2 mid = *reinterpret_cast<const float2*>(row);
       const float lft = row[ix > 0 ? -1 : 0], rgt = row[ix < Wi - 1 ? 2 : 1];
-      acc = fmaf(wy[a], wx[0] * lft + wx[1] * mid.x + wx[2] * mid.y + wx[3] * rgt, acc);
+      acc = __fmaf_rn(wy[a], bilin_row4(wx, lft, mid.x, mid.y, rgt), acc);
     }
     dp[i] = accumulate ? dp[i] + acc : acc;
   }
@@ -291,7 +298,8 @@ __global__ __launch_bounds__(256) void resize_bilinear2x_bwd_kernel(const float*
 
 // the same adjoint, a 2 x 2 block of input pixels per thread (Hi, Wi even, 16-byte aligned dy rows): the block's taps lie in 6 rows x 6
 // columns of dy -- one 16-byte load + two clamped scalars per row instead of (8-byte load + two scalars) x 4 rows per input pixel -- with the
-// taps and weights of resize_bilinear2x_bwd_kernel (a weight-0 tap multiplies whichever finite value sits in its register).
+// taps, weights and arithmetic (bilin_row4) of resize_bilinear2x_bwd_kernel (a weight-0 tap multiplies whichever finite value sits in its
+// register).
 // grid: (blocks over Hi*Wi/4, C, N)
 __global__ __launch_bounds__(256) void resize_bilinear2x_bwd_q_kernel(const float* __restrict__ dy, i64 dy_bs, float* __restrict__ dx,
                                                                       i64 dx_bs, int C, int Hi, int Wi, int accumulate) {
@@ -328,7 +336,7 @@ __global__ __launch_bounds__(256) void resize_bilinear2x_bwd_q_kernel(const floa
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
           const float* q = &v[2 * dyi + a][2 * dxi];
-          acc = fmaf(wy[a], wx[0] * q[0] + wx[1] * q[1] + wx[2] * q[2] + wx[3] * q[3], acc);
+          acc = __fmaf_rn(wy[a], bilin_row4(wx, q[0], q[1], q[2], q[3]), acc);
         }
         o[dyi][dxi] = acc;
       }

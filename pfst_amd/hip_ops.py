@@ -764,12 +764,14 @@ def bn_backward_dual(dy, mask, a, b):
     """the BatchNorm backward of TWO layers that receive the same gated gradient g = (mask bit ? dy : 0) -- bn3 and the downsample branch's BN of
     a stage's first Bottleneck -- in one reduction and one apply pass (pfst_bn_backward_dual).  a / b: dicts x (pre-BN tensor), mean, invstd,
     gamma, dgamma, dbeta, amax (slot group or None); a may carry partials / slots (its sums from the launch that wrote dy).  Returns
-    (dxa, dxb), or None when the entry point does not take the case (deterministic mode, unaligned planes): the caller runs the layers one by one"""
+    (dxa, dxb), or None when the entry point does not take the case (deterministic mode, unaligned planes, planes that are no multiple of 256
+    elements): the caller runs the layers one by one"""
     n, c, h, w = a['x'].shape
     assert dy.shape == a['x'].shape == b['x'].shape
-    assert mask.dtype == torch.int64 and mask.numel() == n * c * h * w // 64 and (h * w) % 256 == 0
-    if is_deterministic() or any(_bs(t) % 4 or t.data_ptr() % 16 for t in (dy, a["x"], b["x"])):
+    # the conditions under which pfst_bn_backward_dual answers PFST_ERR_UNSUPPORTED, repeated here (dxa / dxb are allocated below)
+    if is_deterministic() or (h * w) % 256 != 0 or any(_bs(t) % 4 or t.data_ptr() % 16 for t in (dy, a["x"], b["x"])):
         return None
+    assert mask.dtype == torch.int64 and mask.numel() == n * c * h * w // 64
     dxa, dxb = torch.empty(n, c, h, w, device=dy.device), torch.empty(n, c, h, w, device=dy.device)
     ws = torch.empty(4 * c, dtype=torch.float64, device=dy.device)
     call('pfst_bn_backward_dual', dy.data_ptr(), _bs(dy), mask.data_ptr(),

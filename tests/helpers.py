@@ -74,3 +74,37 @@ def assert_live_target_side(log, ex=None, min_frac=0.15):
     if ex is not None:
         frac = float(ex['mask'].float().mean())
         assert frac >= min_frac, f'valid target region is {frac:.3f} of the grid'
+
+
+# ---- canary buffers of the kernel-level GPU tests (depthwise, BatchNorm and plane kernels on views)
+DEV = 'cuda'
+SENT = -7777.0
+
+
+class Guard:
+    """an NCHW view with dense planes inside a SENT-filled flat buffer: `front` / `back` whole channels either side of the view in every
+    image (back = 3 by default: a plane kernel that ran a whole group of four channels past C - 1 would still land on canaries), `odd` extra
+    floats per image (an odd batch stride), `lead` floats in front of everything (lead = 1: planes start at 16k + 4 bytes)"""
+
+    def __init__(self, shape, front=1, back=3, lead=0, odd=0):
+        n, c, h, w = shape
+        self.bs = (front + c + back) * h * w + odd
+        self.off = lead + front * h * w
+        self.flat = torch.full((lead + n * self.bs + 64,), SENT, device=DEV)
+        assert self.flat.data_ptr() % 16 == 0
+        self.view = self.flat.as_strided(shape, (self.bs, h * w, w, 1), self.off)
+
+    def put(self, t):
+        self.view.copy_(t)
+        return self.view
+
+    def intact(self, what=''):
+        m = torch.ones(self.flat.numel(), dtype=torch.bool, device=DEV)
+        m.as_strided(self.view.shape, self.view.stride(), self.off).fill_(False)
+        bad = (self.flat[m] != SENT).nonzero().flatten()
+        assert bad.numel() == 0, f'{what}: {bad.numel()} floats outside the view were written, the first at flat index {int(bad[0])}'
+
+
+def out_view(shape, **kw):
+    gd = Guard(shape, **kw)
+    return gd, gd.view

@@ -56,12 +56,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import SENT, Guard, out_view
 from test_hip_ops import g, ops  # noqa: F401  (ops: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
-SENT = -7777.0
 FWD, WGRAD, STAT = 1e-5, 1e-4, 2e-5            # inherited from test_hip_ops.test_depthwise
 SUMS = 64 * 2.0 ** -24                         # partial sums against the kernel's own output (docstring)
 LDS = 64 * 1024                                # dwconv.hip DW_LDS_BYTES
@@ -135,35 +135,6 @@ def det_mode(ops, on=True):
         yield
     finally:
         ops.set_deterministic(before)
-
-
-class Guard:
-    """an NCHW view with dense planes inside a SENT-filled flat buffer: `front` / `back` whole channels either side of the view in every
-    image (back = 3 by default: a plane kernel that ran a whole group of four channels past C - 1 would still land on canaries), `odd` extra
-    floats per image (an odd batch stride), `lead` floats in front of everything (lead = 1: planes start at 16k + 4 bytes)"""
-
-    def __init__(self, shape, front=1, back=3, lead=0, odd=0):
-        n, c, h, w = shape
-        self.bs = (front + c + back) * h * w + odd
-        self.off = lead + front * h * w
-        self.flat = torch.full((lead + n * self.bs + 64,), SENT, device=DEV)
-        assert self.flat.data_ptr() % 16 == 0
-        self.view = self.flat.as_strided(shape, (self.bs, h * w, w, 1), self.off)
-
-    def put(self, t):
-        self.view.copy_(t)
-        return self.view
-
-    def intact(self, what=''):
-        m = torch.ones(self.flat.numel(), dtype=torch.bool, device=DEV)
-        m.as_strided(self.view.shape, self.view.stride(), self.off).fill_(False)
-        bad = (self.flat[m] != SENT).nonzero().flatten()
-        assert bad.numel() == 0, f'{what}: {bad.numel()} floats outside the view were written, the first at flat index {int(bad[0])}'
-
-
-def out_view(shape, **kw):
-    gd = Guard(shape, **kw)
-    return gd, gd.view
 
 
 class DwGuard:

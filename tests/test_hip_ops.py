@@ -670,8 +670,8 @@ def test_bilinear_resize(ops, hi, wi, ho, wo):
     dx2 = ops.resize_bilinear_bwd(dy.to(DEV), (hi, wi), out=dx.clone(), accumulate=True)
     assert_close(dx2, 2 * x.grad, 1e-5, 'resize bwd accumulate')
     if ho == 2 * hi and wo == 2 * wi and hi % 2 == 0 and wi % 2 == 0:
-        # the 2 x 2-block adjoint against the one-pixel kernel (reached through an 8-byte aligned view): the same taps and weights, the
-        # compiler contracts the two expressions into differently grouped fmas
+        # the 2 x 2-block adjoint against the one-pixel kernel (reached through an 8-byte aligned view): the same taps and weights (and,
+        # since both rows go through bilin_row4, the same bits: tests/test_plane_views_gpu.py asserts torch.equal across all three adjoints)
         pad = torch.zeros(2, 5 * ho * wo + 2, device=DEV)
         pad[:, 2:] = dy.to(DEV).reshape(2, -1)
         dx1 = ops.resize_bilinear_bwd(pad[:, 2:].reshape(2, 5, ho, wo), (hi, wi))       # 8-byte aligned images: the one-pixel kernel
