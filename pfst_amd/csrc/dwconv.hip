@@ -11,6 +11,8 @@
 // The data gradient is the same stencil with mirrored taps; the weight gradient reuses the staging and reduces
 // 9 partial sums per block (wavefront shuffles, one atomic per tap per block).
 #include <stdlib.h>
+#include <initializer_list>
+#include <type_traits>
 #include "common.h"
 #include "../../include/pfst_hip.h"
 
@@ -175,6 +177,86 @@ __device__ __forceinline__ void block_minmax(float& lo, float& hi, float* scratc
   }
 }
 
+// One tap of an output quad: k * v added into the quad (the stencil, forward or data gradient), and a . v, summed pairwise (the tap's share of
+// a weight gradient).  Every kernel of this file forms its sums with exactly these two expressions.
+__device__ __forceinline__ void tap_fma4(float k, const float4& v, float4& acc) {
+  acc.x = fmaf(k, v.x, acc.x); acc.y = fmaf(k, v.y, acc.y); acc.z = fmaf(k, v.z, acc.z); acc.w = fmaf(k, v.w, acc.w);
+}
+__device__ __forceinline__ float tap_dot4(const float4& a, const float4& v) { return (a.x * v.x + a.y * v.y) + (a.z * v.z + a.w * v.w); }
+
+// The nine taps of the output quad at row yy, columns 4 c4 .. 4 c4 + 3, read from a staged tile whose first row is plane row `lo` (s.lo of a
+// strip, 0 of a whole plane): f(t, v) receives tap t = 3 ty + tx and the four inputs under it, zeros outside the plane's columns; tap rows
+// outside the plane are skipped.  MODE 1, 2, 3 as for dwconv3x3_kernel below.  (f and v by value: handed on by reference, the same arithmetic
+// costs the kernels with a weight gradient two more registers.)
+template <int MODE, class F>
+__device__ __forceinline__ void quad_taps(const float* __restrict__ tile, int lo, int yy, int c4, int H, int W, int dil, F f) {
+#pragma unroll
+  for (int ty = 0; ty < 3; ++ty) {
+    const int sy = yy + (ty - 1) * dil;
+    if (sy < 0 || sy >= H) continue;
+    const float* row = tile + (sy - lo) * W;
+    float4 tv[3];
+    if (MODE == 3) row_taps_d1(row, c4, W, tv[0], tv[1], tv[2]);
+#pragma unroll
+    for (int tx = 0; tx < 3; ++tx) f(ty * 3 + tx, MODE == 3 ? tv[tx] : row4<MODE == 1>(row, c4 * 4 + (tx - 1) * dil, W));
+  }
+}
+
+// the scalar form (MODE 0, any W): f(t, v) for the taps of output (yy, col) that fall inside the plane
+template <class F>
+__device__ __forceinline__ void scalar_taps(const float* __restrict__ tile, int lo, int yy, int col, int H, int W, int dil, F f) {
+#pragma unroll
+  for (int ty = 0; ty < 3; ++ty) {
+    const int sy = yy + (ty - 1) * dil;
+    if (sy < 0 || sy >= H) continue;
+    const float* row = tile + (sy - lo) * W;
+#pragma unroll
+    for (int tx = 0; tx < 3; ++tx) {
+      const int sx = col + (tx - 1) * dil;
+      if (sx >= 0 && sx < W) f(ty * 3 + tx, row[sx]);
+    }
+  }
+}
+
+// Fused BatchNorm statistics of the outputs a thread writes: their sum, sum of squares and extrema (predicted max |relu(bn(y))|, bn.hip).
+// The kernels are HBM-bound, the arithmetic is free; it saves the separate bn_stats read of the depthwise output.
+struct StatAcc {
+  float s = 0.f, q = 0.f, lo = __builtin_inff(), hi = -__builtin_inff();
+  __device__ __forceinline__ void add(const float4& a) {
+    s += (a.x + a.y) + (a.z + a.w);
+    q = fmaf(a.x, a.x, fmaf(a.y, a.y, fmaf(a.z, a.z, fmaf(a.w, a.w, q))));
+    lo = fminf(fminf(lo, fminf(a.x, a.y)), fminf(a.z, a.w));
+    hi = fmaxf(fmaxf(hi, fmaxf(a.x, a.y)), fmaxf(a.z, a.w));
+  }
+  __device__ __forceinline__ void add(float a) {
+    s += a;
+    q = fmaf(a, a, q);
+    lo = fminf(lo, a);
+    hi = fmaxf(hi, a);
+  }
+  // the workgroup's partial sums for pfst_bn_finalize_partials: stats[c][slot][2] of [C][T][2], and with minmax its (minimum, maximum) in a
+  // second [C][T][2] behind the sums.  Every thread of the workgroup calls it (barriers inside); red: >= 40 doubles of LDS.
+  __device__ __forceinline__ void write_partials(float* __restrict__ stats, int C, i64 T, int c, i64 slot, int minmax, double* red) {
+    double bs = (double)s, bq = (double)q;
+    block_sum2_d<true>(bs, bq, red);
+    float2* dst = reinterpret_cast<float2*>(stats) + ((i64)c * T + slot);
+    if (threadIdx.x == 0) *dst = make_float2((float)bs, (float)bq);
+    if (minmax) {
+      block_minmax(lo, hi, reinterpret_cast<float*>(red));
+      if (threadIdx.x == 0) dst[(i64)C * T] = make_float2(lo, hi);
+    }
+  }
+};
+
+// One plane's (or strip's) quads into registers through a buffer resource: thread t of NT holds quads t, t + NT, ..., all QPT 16-byte loads in
+// flight at once; a quad past `bytes` reads as zeros instead of needing a branch around the load.
+template <int QPT, int NT>
+__device__ __forceinline__ void fetch_quads(float4 (&r)[QPT], const float* __restrict__ base, int bytes) {
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
+#pragma unroll
+  for (int u = 0; u < QPT; ++u) r[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * ((int)threadIdx.x + u * NT), 0, 0));
+}
+
 // MODE 0: scalar (any W); MODE 1: float4 outputs, dilation % 4 == 0 (ds_read_b128 taps); MODE 2: float4 outputs, any dilation;
 // MODE 3: float4 outputs, dilation 1 (row_taps_d1)
 // WG (backward only, flip = 1: x = dY, y = dX): the same pass also forms the WEIGHT gradient.  With v_t = dY[p + off(t)] the nine
@@ -196,10 +278,10 @@ __global__ __launch_bounds__(512) void dwconv3x3_kernel(const float* __restrict_
   // normalised as they are loaded.  The normalised tensor is never materialised (its only consumer is this depthwise layer).
   extern __shared__ float tile[];
   __shared__ double red[40];                       // (also the 8 x 9 floats of block_add9)
-  float st_s = 0.f, st_q = 0.f;                    // fused BatchNorm statistics of this block's outputs (stats != NULL)
-  float st_lo = __builtin_inff(), st_hi = -__builtin_inff();      // stats_minmax: and their extrema (predicted max |relu(bn(y))|, bn.hip)
+  StatAcc st;                                      // of this block's outputs (written when stats != NULL)
   const int c = blockIdx.y, n = blockIdx.z;
   const Strip s = make_strip(blockIdx.x, R, H, dil);
+  const i64 T = (i64)gridDim.x * gridDim.z, slot = (i64)n * gridDim.x + blockIdx.x;      // of the statistics partials: one slot per (image, strip)
   const float* xp = x + (i64)n * x_bs + (i64)c * H * W;
   float* yp = y + (i64)n * y_bs + (i64)c * H * W;
   const float* fxp = WG ? fx + (i64)n * fx_bs + (i64)c * H * W : nullptr;
@@ -229,28 +311,14 @@ __global__ __launch_bounds__(512) void dwconv3x3_kernel(const float* __restrict_
         xq = *(reinterpret_cast<const float4*>(fxp + (i64)yy * W) + c4);
         if (bnl) xq = bn_on_load4(xq, bsc, bsh);
       }
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int sy = yy + (ty - 1) * dil;
-        if (sy < 0 || sy >= H) continue;
-        const float* row = tile + (sy - s.lo) * W;
-        float4 tv[3];
-        if (MODE == 3) row_taps_d1(row, c4, W, tv[0], tv[1], tv[2]);
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const float4 v = MODE == 3 ? tv[tx] : row4<MODE == 1>(row, c4 * 4 + (tx - 1) * dil, W);
-          const float k = wt[ty * 3 + tx];
-          acc.x = fmaf(k, v.x, acc.x); acc.y = fmaf(k, v.y, acc.y); acc.z = fmaf(k, v.z, acc.z); acc.w = fmaf(k, v.w, acc.w);
-          if (WG) accw[8 - (ty * 3 + tx)] += (xq.x * v.x + xq.y * v.y) + (xq.z * v.z + xq.w * v.w);
-        }
-      }
+      quad_taps<MODE>(tile, s.lo, yy, c4, H, W, dil, [&](int t, float4 v) {
+        tap_fma4(wt[t], v, acc);
+        if (WG) accw[8 - t] += tap_dot4(xq, v);
+      });
       float4* out = reinterpret_cast<float4*>(yp + (i64)yy * W) + c4;
       if (accumulate) { const float4 o = *out; acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w; }
       *out = acc;
-      st_s += (acc.x + acc.y) + (acc.z + acc.w);
-      st_q = fmaf(acc.x, acc.x, fmaf(acc.y, acc.y, fmaf(acc.z, acc.z, fmaf(acc.w, acc.w, st_q))));
-      st_lo = fminf(fminf(st_lo, fminf(acc.x, acc.y)), fminf(acc.z, acc.w));
-      st_hi = fmaxf(fmaxf(st_hi, fmaxf(acc.x, acc.y)), fmaxf(acc.z, acc.w));
+      st.add(acc);
     }
   } else {
     const int total = (s.y1 - s.y0) * W;
@@ -258,47 +326,18 @@ __global__ __launch_bounds__(512) void dwconv3x3_kernel(const float* __restrict_
       const int r = i / W, col = i - r * W;
       const int yy = s.y0 + r;
       float acc = 0.f;
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int sy = yy + (ty - 1) * dil;
-        if (sy < 0 || sy >= H) continue;
-        const float* row = tile + (sy - s.lo) * W;
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const int sx = col + (tx - 1) * dil;
-          if (sx >= 0 && sx < W) {
-            acc = fmaf(wt[ty * 3 + tx], row[sx], acc);
-            if (WG) accw[8 - (ty * 3 + tx)] = fmaf(bnl ? bn_on_load(fxp[(i64)yy * W + col], bsc, bsh) : fxp[(i64)yy * W + col], row[sx], accw[8 - (ty * 3 + tx)]);
-          }
-        }
-      }
+      scalar_taps(tile, s.lo, yy, col, H, W, dil, [&](int t, float v) {
+        acc = fmaf(wt[t], v, acc);
+        if (WG) accw[8 - t] = fmaf(bnl ? bn_on_load(fxp[(i64)yy * W + col], bsc, bsh) : fxp[(i64)yy * W + col], v, accw[8 - t]);
+      });
       const i64 o = (i64)yy * W + col;
       acc = accumulate ? yp[o] + acc : acc;
       yp[o] = acc;
-      st_s += acc;
-      st_q = fmaf(acc, acc, st_q);
-      st_lo = fminf(st_lo, acc);
-      st_hi = fmaxf(st_hi, acc);
+      st.add(acc);
     }
   }
-  // per-(channel, strip, image) partial sums for pfst_bn_finalize_partials: stats[c][n * gridDim.x + strip][2]  (the kernel is
-  // HBM-bound, the arithmetic is free; saves the separate bn_stats read of the depthwise output)
-  if (stats) {
-    double bs = (double)st_s, bq = (double)st_q;
-    block_sum2_d<true>(bs, bq, red);
-    if (threadIdx.x == 0) {
-      const i64 T = (i64)gridDim.x * gridDim.z;
-      float2* dst = reinterpret_cast<float2*>(stats) + ((i64)c * T + (i64)n * gridDim.x + blockIdx.x);
-      *dst = make_float2((float)bs, (float)bq);
-    }
-    if (stats_minmax) {                              // [C][T][2] behind the sums
-      block_minmax(st_lo, st_hi, reinterpret_cast<float*>(red));
-      if (threadIdx.x == 0) {
-        const i64 T = (i64)gridDim.x * gridDim.z;
-        reinterpret_cast<float2*>(stats)[(i64)gridDim.y * T + (i64)c * T + (i64)n * gridDim.x + blockIdx.x] = make_float2(st_lo, st_hi);
-      }
-    }
-  }
+  // per-(channel, strip, image) partials: stats[c][n * gridDim.x + strip][2]
+  if (stats) st.write_partials(stats, C, T, c, slot, stats_minmax, red);
   if (WG) block_add9(accw, dw_dst(dw, c, det_T, blockIdx.z * gridDim.x + blockIdx.x), reinterpret_cast<float*>(red));
 }
 
@@ -317,12 +356,7 @@ __global__ __launch_bounds__(512) void dwconv3x3_plane_kernel(const float* __res
   const int n = blockIdx.z, c0 = blockIdx.y * cpb, c1 = min(C, c0 + cpb);
   const int HW = H * W, n4 = HW >> 2, W4 = W >> 2, tid = threadIdx.x;
   float4 r[8];                                     // host: n4 <= 8 * 512
-  auto fetch = [&](int c) {
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (i64)n * x_bs + (i64)c * HW), 0, HW * 4, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) r[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (tid + u * 512), 0, 0));
-  };
+  auto fetch = [&](int c) { fetch_quads<8, 512>(r, x + (i64)n * x_bs + (i64)c * HW, HW * 4); };
   fetch(c0);
   for (int c = c0; c < c1; ++c) {
     float4* t4 = reinterpret_cast<float4*>(tile);
@@ -335,56 +369,29 @@ __global__ __launch_bounds__(512) void dwconv3x3_plane_kernel(const float* __res
 #pragma unroll
     for (int t = 0; t < 9; ++t) wt[t] = w[c * 9 + (flip ? 8 - t : t)];
     float* yp = y + (i64)n * y_bs + (i64)c * HW;
-    float st_s = 0.f, st_q = 0.f;
-    float st_lo = __builtin_inff(), st_hi = -__builtin_inff();
+    StatAcc st;
     float accw[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) accw[t] = 0.f;
     float4 xr[8];                                  // WG: the forward input's quads this thread's outputs pair with, all in flight at once
-    if (WG) {
-      const __amdgpu_buffer_rsrc_t xs =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(fx + (i64)n * fx_bs + (i64)c * HW), 0, HW * 4, 0x00020000);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) xr[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xs, 16 * (tid + u * 512), 0, 0));
-    }
+    if (WG) fetch_quads<8, 512>(xr, fx + (i64)n * fx_bs + (i64)c * HW, HW * 4);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = tid + u * 512;
       if (i >= n4) break;
       const int yy = i / W4, c4 = i - yy * W4;
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int sy = yy + (ty - 1) * dil;
-        if (sy < 0 || sy >= H) continue;
-        const float* row = tile + sy * W;
-        float4 tv[3];
-        if (MODE == 3) row_taps_d1(row, c4, W, tv[0], tv[1], tv[2]);
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const float4 v = MODE == 3 ? tv[tx] : row4<MODE == 1>(row, c4 * 4 + (tx - 1) * dil, W);
-          const float k = wt[ty * 3 + tx];
-          acc.x = fmaf(k, v.x, acc.x); acc.y = fmaf(k, v.y, acc.y); acc.z = fmaf(k, v.z, acc.z); acc.w = fmaf(k, v.w, acc.w);
-          if (WG) accw[8 - (ty * 3 + tx)] += (xr[u].x * v.x + xr[u].y * v.y) + (xr[u].z * v.z + xr[u].w * v.w);
-        }
-      }
+      const float4 xq = WG ? xr[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+      quad_taps<MODE>(tile, 0, yy, c4, H, W, dil, [&](int t, float4 v) {
+        tap_fma4(wt[t], v, acc);
+        if (WG) accw[8 - t] += tap_dot4(xq, v);
+      });
       float4* out = reinterpret_cast<float4*>(yp) + i;
       if (accumulate) { const float4 o = *out; acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w; }
       *out = acc;
-      st_s += (acc.x + acc.y) + (acc.z + acc.w);
-      st_q = fmaf(acc.x, acc.x, fmaf(acc.y, acc.y, fmaf(acc.z, acc.z, fmaf(acc.w, acc.w, st_q))));
-      st_lo = fminf(fminf(st_lo, fminf(acc.x, acc.y)), fminf(acc.z, acc.w));
-      st_hi = fmaxf(fmaxf(st_hi, fmaxf(acc.x, acc.y)), fmaxf(acc.z, acc.w));
+      st.add(acc);
     }
-    if (stats) {                                   // stats[c][n][2]: one strip per plane (pfst_dwconv_stats_slots == 1)
-      double bs = (double)st_s, bq = (double)st_q;
-      block_sum2_d<true>(bs, bq, red);
-      if (tid == 0) reinterpret_cast<float2*>(stats)[(i64)c * gridDim.z + n] = make_float2((float)bs, (float)bq);
-      if (stats_minmax) {                          // [C][N][2] behind the sums
-        block_minmax(st_lo, st_hi, reinterpret_cast<float*>(red));
-        if (tid == 0) reinterpret_cast<float2*>(stats)[(i64)C * gridDim.z + (i64)c * gridDim.z + n] = make_float2(st_lo, st_hi);
-      }
-    }
+    if (stats) st.write_partials(stats, C, gridDim.z, c, n, stats_minmax, red);          // stats[c][n][2]: one strip per plane (pfst_dwconv_stats_slots == 1)
     if (WG) block_add9(accw, dw_dst(dw, c, det_T, blockIdx.z), reinterpret_cast<float*>(red));
     __syncthreads();                               // every tap of this plane has been read: the tile may be overwritten
   }
@@ -395,100 +402,46 @@ template <bool VEC, bool ALIGNED, bool D1 = false>
 __global__ __launch_bounds__(512) void dwconv3x3_wgrad_kernel(const float* __restrict__ x, i64 x_bs, const float* __restrict__ dy,
                                                               i64 dy_bs, float* __restrict__ dw, int C, int H, int W, int dil, int R, int det_T = 0) {
   extern __shared__ float tile[];
-  __shared__ float red[8][9];
+  __shared__ float red[8 * 9];                     // block_add9
+  constexpr int MODE = D1 ? 3 : (ALIGNED ? 1 : 2);
   const int c = blockIdx.y, n = blockIdx.z;
   const Strip s = make_strip(blockIdx.x, R, H, dil);
   const float* xp = x + (i64)n * x_bs + (i64)c * H * W;
   const float* gp = dy + (i64)n * dy_bs + (i64)c * H * W;
+  float* dst = dw_dst(dw, c, det_T, blockIdx.z * gridDim.x + blockIdx.x);          // (read up here, in uniform code)
   // the strip's output gradients: up to eight 16-byte loads per thread in flight beside the staging copy (a strip of at most 64 KB is
-  // exactly one batch; larger strips take further batches inside the loop)
-  const int W4v = W >> 2, totalv = (s.y1 - s.y0) * W4v;
+  // exactly one batch; larger strips take further quads from memory behind it)
+  const int W4 = W >> 2, total4 = (s.y1 - s.y0) * W4;
+  const float* gs = gp + (i64)s.y0 * W;            // the strip's rows are contiguous: quad i of the strip is gs[4 i ..]
   float4 gq[8];
-  if (VEC) {
-    const __amdgpu_buffer_rsrc_t grs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gp + (i64)s.y0 * W), 0, totalv * 16, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      gq[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(grs, 16 * (threadIdx.x + u * 512), 0, 0));
-  }
+  if (VEC) fetch_quads<8, 512>(gq, gs, total4 * 16);
   stage_rows(xp, tile, s.lo, s.hi, W);
   __syncthreads();
   float acc[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = 0.f;
   if (VEC) {
-    const int W4 = W >> 2;
-    const int total = (s.y1 - s.y0) * W4;
+    auto quad = [&](int i, const float4 g) {
+      const int r = i / W4, c4 = i - r * W4;
+      quad_taps<MODE>(tile, s.lo, s.y0 + r, c4, H, W, dil, [&](int t, float4 v) { acc[t] += tap_dot4(g, v); });
+    };
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = threadIdx.x + u * 512;
-      if (i >= total) break;
-      const int r = i / W4, c4 = i - r * W4;
-      const int yy = s.y0 + r;
-      const float4 g = gq[u];
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int sy = yy + (ty - 1) * dil;
-        if (sy < 0 || sy >= H) continue;
-        const float* row = tile + (sy - s.lo) * W;
-        float4 tv[3];
-        if (D1) row_taps_d1(row, c4, W, tv[0], tv[1], tv[2]);
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const float4 v = D1 ? tv[tx] : row4<ALIGNED>(row, c4 * 4 + (tx - 1) * dil, W);
-          acc[ty * 3 + tx] += (g.x * v.x + g.y * v.y) + (g.z * v.z + g.w * v.w);
-        }
-      }
+      if (i >= total4) break;
+      quad(i, gq[u]);
     }
-    for (int i = threadIdx.x + 8 * 512; i < total; i += blockDim.x) {
-      const int r = i / W4, c4 = i - r * W4;
-      const int yy = s.y0 + r;
-      const float4 g = *(reinterpret_cast<const float4*>(gp + (i64)yy * W) + c4);
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int sy = yy + (ty - 1) * dil;
-        if (sy < 0 || sy >= H) continue;
-        const float* row = tile + (sy - s.lo) * W;
-        float4 tv[3];
-        if (D1) row_taps_d1(row, c4, W, tv[0], tv[1], tv[2]);
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const float4 v = D1 ? tv[tx] : row4<ALIGNED>(row, c4 * 4 + (tx - 1) * dil, W);
-          acc[ty * 3 + tx] += (g.x * v.x + g.y * v.y) + (g.z * v.z + g.w * v.w);
-        }
-      }
-    }
+    for (int i = threadIdx.x + 8 * 512; i < total4; i += blockDim.x) quad(i, reinterpret_cast<const float4*>(gs)[i]);
   } else {
     const int total = (s.y1 - s.y0) * W;
     for (int i = threadIdx.x; i < total; i += blockDim.x) {
       const int r = i / W, col = i - r * W;
       const int yy = s.y0 + r;
       const float g = gp[(i64)yy * W + col];
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int sy = yy + (ty - 1) * dil;
-        if (sy < 0 || sy >= H) continue;
-        const float* row = tile + (sy - s.lo) * W;
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const int sx = col + (tx - 1) * dil;
-          if (sx >= 0 && sx < W) acc[ty * 3 + tx] = fmaf(g, row[sx], acc[ty * 3 + tx]);
-        }
-      }
+      scalar_taps(tile, s.lo, yy, col, H, W, dil, [&](int t, float v) { acc[t] = fmaf(g, v, acc[t]); });
     }
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const float v = wave_sum(acc[t]);
-    if (lane == 0) red[wid][t] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    float v = 0.f;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) v += red[k][threadIdx.x];
-    atomicAdd(&dw_dst(dw, c, det_T, blockIdx.z * gridDim.x + blockIdx.x)[threadIdx.x], v);
-  }
+  block_add9(acc, dst, red);
 }
 
 // ---- the three atrous depthwise branches of the ASPP head in one pass (sep_aspp_head.py:63-77: dilations 12 / 24 / 36 on the SAME 2048-channel
@@ -519,12 +472,7 @@ __global__ __launch_bounds__(512) void dwconv3x3_multi_fwd_kernel(const float* _
   const int n = blockIdx.z, c0 = blockIdx.y * cpb, c1 = min(C, c0 + cpb);
   const int HW = H * W, n4 = HW >> 2, W4 = W >> 2, tid = threadIdx.x;
   float4 r[8];
-  auto fetch = [&](int c) {
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (i64)n * x_bs + (i64)c * HW), 0, HW * 4, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) r[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (tid + u * 512), 0, 0));
-  };
+  auto fetch = [&](int c) { fetch_quads<8, 512>(r, x + (i64)n * x_bs + (i64)c * HW, HW * 4); };
   fetch(c0);
   for (int c = c0; c < c1; ++c) {
     float4* t4 = reinterpret_cast<float4*>(tile);
@@ -548,38 +496,15 @@ __global__ __launch_bounds__(512) void dwconv3x3_multi_fwd_kernel(const float* _
 #pragma unroll
       for (int t = 0; t < 9; ++t) wt[t] = S.w[si][c * 9 + t];
       float* yp = S.y[si] + (i64)n * S.bs[si] + (i64)c * HW;
-      float st_s = 0.f, st_q = 0.f;
-      float st_lo = __builtin_inff(), st_hi = -__builtin_inff();
+      StatAcc st;
       for (int i = tid; i < n4; i += 512) {
         const int yy = i / W4, c4 = i - yy * W4;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int ty = 0; ty < 3; ++ty) {
-          const int sy = yy + (ty - 1) * dil;
-          if (sy < 0 || sy >= H) continue;
-          const float* row = tile + sy * W;
-#pragma unroll
-          for (int tx = 0; tx < 3; ++tx) {
-            const float4 v = row4<true>(row, c4 * 4 + (tx - 1) * dil, W);
-            const float k = wt[ty * 3 + tx];
-            acc.x = fmaf(k, v.x, acc.x); acc.y = fmaf(k, v.y, acc.y); acc.z = fmaf(k, v.z, acc.z); acc.w = fmaf(k, v.w, acc.w);
-          }
-        }
+        quad_taps<1>(tile, 0, yy, c4, H, W, dil, [&](int t, float4 v) { tap_fma4(wt[t], v, acc); });
         reinterpret_cast<float4*>(yp)[i] = acc;
-        st_s += (acc.x + acc.y) + (acc.z + acc.w);
-        st_q = fmaf(acc.x, acc.x, fmaf(acc.y, acc.y, fmaf(acc.z, acc.z, fmaf(acc.w, acc.w, st_q))));
-        st_lo = fminf(fminf(st_lo, fminf(acc.x, acc.y)), fminf(acc.z, acc.w));
-        st_hi = fmaxf(fmaxf(st_hi, fmaxf(acc.x, acc.y)), fmaxf(acc.z, acc.w));
+        st.add(acc);
       }
-      if (S.stats[si]) {                           // same partial layout as dwconv3x3_plane_kernel: stats[c][n][2]
-        double bs = (double)st_s, bq = (double)st_q;
-        block_sum2_d<true>(bs, bq, red);
-        if (tid == 0) reinterpret_cast<float2*>(S.stats[si])[(i64)c * gridDim.z + n] = make_float2((float)bs, (float)bq);
-        if (S.stats_minmax) {                      // [C][N][2] behind the sums
-          block_minmax(st_lo, st_hi, reinterpret_cast<float*>(red));
-          if (tid == 0) reinterpret_cast<float2*>(S.stats[si])[(i64)C * gridDim.z + (i64)c * gridDim.z + n] = make_float2(st_lo, st_hi);
-        }
-      }
+      if (S.stats[si]) st.write_partials(S.stats[si], C, gridDim.z, c, n, S.stats_minmax, red);          // the partial layout of dwconv3x3_plane_kernel: stats[c][n][2]
     }
     __syncthreads();                               // every tap of this plane has been read: the tile may be overwritten
   }
@@ -602,27 +527,18 @@ __global__ __launch_bounds__(NT) void dwconv3x3_multi_bwd_kernel(const float* __
   float4* const x4 = t4 + n4;
   float4 r[QPT], p[QPT];
   auto fetch = [&](int c, int si) {                // the gradient plane (BNB: and the pre-normalisation plane) of branch si, channel c -> registers
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(S.dy[si] + (i64)n * S.bs[si] + (i64)c * HW), 0, HW * 4, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < QPT; ++u) r[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (tid + u * NT), 0, 0));
-    if (BNB) {
-      const __amdgpu_buffer_rsrc_t ps =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(S.pre[si] + (i64)n * S.bs[si] + (i64)c * HW), 0, HW * 4, 0x00020000);
-#pragma unroll
-      for (int u = 0; u < QPT; ++u) p[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ps, 16 * (tid + u * NT), 0, 0));
-    }
+    fetch_quads<QPT, NT>(r, S.dy[si] + (i64)n * S.bs[si] + (i64)c * HW, HW * 4);
+    if (BNB) fetch_quads<QPT, NT>(p, S.pre[si] + (i64)n * S.bs[si] + (i64)c * HW, HW * 4);
   };
   fetch(c0, 0);
   for (int c = c0; c < c1; ++c) {
     float4 dxa[QPT];
     {                                              // the forward input's plane: each thread keeps its own quads in LDS (read back per branch)
-      const __amdgpu_buffer_rsrc_t xs =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (i64)n * x_bs + (i64)c * HW), 0, HW * 4, 0x00020000);
+      float4 xv[QPT];
+      fetch_quads<QPT, NT>(xv, x + (i64)n * x_bs + (i64)c * HW, HW * 4);
 #pragma unroll
       for (int u = 0; u < QPT; ++u) {
-        const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xs, 16 * (tid + u * NT), 0, 0));
-        if (tid + u * NT < n4) x4[tid + u * NT] = v;
+        if (tid + u * NT < n4) x4[tid + u * NT] = xv[u];
         dxa[u] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
@@ -651,19 +567,10 @@ __global__ __launch_bounds__(NT) void dwconv3x3_multi_bwd_kernel(const float* __
         if (i >= n4) break;
         const int yy = i / W4, c4 = i - yy * W4;
         const float4 xq = x4[i];
-#pragma unroll
-        for (int ty = 0; ty < 3; ++ty) {
-          const int sy = yy + (ty - 1) * dil;
-          if (sy < 0 || sy >= H) continue;
-          const float* row = tile + sy * W;
-#pragma unroll
-          for (int tx = 0; tx < 3; ++tx) {
-            const float4 v = row4<true>(row, c4 * 4 + (tx - 1) * dil, W);
-            const float k = wt[ty * 3 + tx];
-            dxa[u].x = fmaf(k, v.x, dxa[u].x); dxa[u].y = fmaf(k, v.y, dxa[u].y); dxa[u].z = fmaf(k, v.z, dxa[u].z); dxa[u].w = fmaf(k, v.w, dxa[u].w);
-            accw[8 - (ty * 3 + tx)] += (xq.x * v.x + xq.y * v.y) + (xq.z * v.z + xq.w * v.w);
-          }
-        }
+        quad_taps<1>(tile, 0, yy, c4, H, W, dil, [&](int t, float4 v) {
+          tap_fma4(wt[t], v, dxa[u]);              // (across the branches: dxa is not reset between them)
+          accw[8 - t] += tap_dot4(xq, v);
+        });
       }
       block_add9(accw, dw_dst(S.dw[si], c, det_T, blockIdx.z), reinterpret_cast<float*>(red));
       __syncthreads();                             // every tap of this gradient plane has been read: the tile may be overwritten
@@ -696,6 +603,86 @@ inline size_t strip_lds(int R, int H, int W, int dil) {
   return (size_t)rows * W * sizeof(float);
 }
 
+// float4 routes: W % 4 == 0, every operand of the call 16-byte aligned (a NULL one counts as aligned) and every batch stride a multiple of
+// four floats.  Each caller lists the operands its kernel reads or writes as quads.
+inline bool dw_vec(int H, int W, std::initializer_list<const void*> ptrs, std::initializer_list<i64> strides) {
+  uintptr_t p = 0;
+  i64 s = 0;
+  for (const void* q : ptrs) p |= (uintptr_t)q;
+  for (i64 b : strides) s |= b;
+  return (W % 4 == 0) && (p % 16 == 0) && (s % 4 == 0) && (((i64)H * W) % 4 == 0);
+}
+
+// the kernels' MODE (see dwconv3x3_kernel); d1 = false: dilation 1 through the general MODE 2 instead of row_taps_d1
+inline int dw_mode(bool vec, int dil, bool d1 = true) { return !vec ? 0 : (dil % 4 == 0 ? 1 : (dil == 1 && d1 ? 3 : 2)); }
+
+constexpr int DW_CPB = 4;                          // channels per workgroup of the whole-plane kernels
+
+// the whole-plane kernel instead of the strip kernel (which alone carries the normalise-on-load and BatchNorm-backward variants: `folded`)
+inline bool dw_plane_route(int mode, int R, int H, int W, bool folded) { return mode != 0 && R == H && (i64)H * W <= 8 * 512 * 4 && !folded; }
+
+// Launch one kernel instantiation, named here and nowhere else: its first launch raises its dynamic-LDS limit to the 150 KiB the argument
+// checks allow.  (KERNEL in parentheses when its template arguments hold a comma.)
+#define DW_LAUNCH(KERNEL, grid, threads, lds, st, ...)                                                                                   \
+  do {                                                                                                                                   \
+    static const hipError_t lds_limit_ =                                                                                                 \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);               \
+    (void)lds_limit_;                                                                                                                    \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, st, __VA_ARGS__);                                                               \
+  } while (0)
+
+// a run-time MODE (0 .. 3) or branch count (1 .. 3) as a template argument: f(std::integral_constant<int, V>{})
+template <class F>
+void dw_for_mode(int mode, F f) {
+  switch (mode) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 0>{});
+  }
+}
+template <class F>
+void dw_for_branches(int ns, F f) {
+  switch (ns) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+  }
+}
+
+// The strip or the whole-plane kernel of one MODE, without (forward, data gradient) or with the weight gradient (WG): the one place that
+// spells out the two kernels' argument lists.  fx .. det_T: WG only; bnl: strip kernel only.
+template <bool WG>
+void dw_launch_conv(int mode, bool plane, int R, size_t lds, hipStream_t st, const float* x, i64 x_bs, const float* w, float* y, i64 y_bs, int N, int C,
+                    int H, int W, int dil, int flip, int accumulate, float* stats, int stats_minmax, const float4* bnl, const float* fx = nullptr,
+                    i64 fx_bs = 0, float* dw = nullptr, const float* bnpre = nullptr, i64 bnpre_bs = 0, const pfst_bn_bwd_rec_t* bnrec = nullptr,
+                    int det_T = 0) {
+  dw_for_mode(mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if constexpr (MODE != 0) {
+      if (plane) {
+        DW_LAUNCH((dwconv3x3_plane_kernel<MODE, WG>), dim3(1, cdiv(C, DW_CPB), N), 512, lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, DW_CPB, flip,
+                  accumulate, stats, fx, fx_bs, dw, det_T, stats_minmax);
+        return;
+      }
+    }
+    DW_LAUNCH((dwconv3x3_kernel<MODE, WG>), dim3(cdiv(H, R), C, N), 512, lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, R, flip, accumulate, stats, fx,
+              fx_bs, dw, bnl, bnpre, bnpre_bs, bnrec, det_T, stats_minmax);
+  });
+}
+
+// Deterministic mode (see dw_dst): nb consecutive zeroed blocks of [C][det_T][9] slots in the scratch -> the first block, or NULL when there
+// is no scratch or it could not be cleared; afterwards dw_det_reduce adds one block's slots in index order into its weight gradient.
+float* dw_det_slots(int C, int det_T, int nb, hipStream_t st) {
+  const size_t bytes = (size_t)C * det_T * 9 * nb * sizeof(float);
+  float* part = static_cast<float*>(pfst_det_scratch(bytes, st));
+  if (part && hipMemsetAsync(part, 0, bytes, st) != hipSuccess) return nullptr;
+  return part;
+}
+void dw_det_reduce(const float* part, float* dw, int C, int det_T, hipStream_t st) {
+  hipLaunchKernelGGL(dw_det_reduce_kernel, dim3(C), dim3(64), 0, st, part, dw, C, det_T);
+}
+
 }  // namespace
 
 extern "C" int pfst_dwconv_stats_slots(int H, int W, int dil) {
@@ -714,53 +701,9 @@ extern "C" int pfst_dwconv3x3(const float* x, long long x_bs, const float* w, fl
   const int R = strip_rows(H, W, dil);
   const size_t lds = strip_lds(R, H, W, dil);
   PFST_CHECK_ARG(lds <= 150 * 1024);
-  static bool set = false;
-  if (!set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    set = true;
-  }
-  const bool vec = (W % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) % 16 == 0) && (x_bs % 4 == 0) && (y_bs % 4 == 0) &&
-                   (((i64)H * W) % 4 == 0);
-  const int mode = !vec ? 0 : (dil % 4 == 0 ? 1 : (dil == 1 ? 3 : 2));
-  dim3 grid(cdiv(H, R), C, N);
-  hipStream_t st = (hipStream_t)stream;
-  constexpr int cpb = 4;            // channels per workgroup of the plane kernel
-  if (mode != 0 && R == H && (i64)H * W <= 8 * 512 * 4 && cpb > 0 && !bnl) {      // (the strip kernel carries the normalise-on-load variant)
-    static bool set2 = false;
-    if (!set2) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_plane_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_plane_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_plane_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      set2 = true;
-    }
-    dim3 gp(1, cdiv(C, cpb), N);
-    if (mode == 1)
-      hipLaunchKernelGGL(dwconv3x3_plane_kernel<1>, gp, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, cpb, flip, accumulate, stats,
-                         (const float*)nullptr, (i64)0, (float*)nullptr, 0, stats_minmax);
-    else if (mode == 3)
-      hipLaunchKernelGGL(dwconv3x3_plane_kernel<3>, gp, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, cpb, flip, accumulate, stats,
-                         (const float*)nullptr, (i64)0, (float*)nullptr, 0, stats_minmax);
-    else
-      hipLaunchKernelGGL(dwconv3x3_plane_kernel<2>, gp, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, cpb, flip, accumulate, stats,
-                         (const float*)nullptr, (i64)0, (float*)nullptr, 0, stats_minmax);
-    PFST_CHECK_LAUNCH();
-    return PFST_OK;
-  }
-  if (mode == 1)
-    hipLaunchKernelGGL(dwconv3x3_kernel<1>, grid, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, R, flip, accumulate, stats, (const float*)nullptr, (i64)0, (float*)nullptr, bnl,
-                       (const float*)nullptr, (i64)0, (const pfst_bn_bwd_rec_t*)nullptr, 0, stats_minmax);
-  else if (mode == 2)
-    hipLaunchKernelGGL(dwconv3x3_kernel<2>, grid, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, R, flip, accumulate, stats, (const float*)nullptr, (i64)0, (float*)nullptr, bnl,
-                       (const float*)nullptr, (i64)0, (const pfst_bn_bwd_rec_t*)nullptr, 0, stats_minmax);
-  else if (mode == 3)
-    hipLaunchKernelGGL(dwconv3x3_kernel<3>, grid, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, R, flip, accumulate, stats, (const float*)nullptr, (i64)0, (float*)nullptr, bnl,
-                       (const float*)nullptr, (i64)0, (const pfst_bn_bwd_rec_t*)nullptr, 0, stats_minmax);
-  else
-    hipLaunchKernelGGL(dwconv3x3_kernel<0>, grid, dim3(512), lds, st, x, x_bs, w, y, y_bs, C, H, W, dil, R, flip, accumulate, stats, (const float*)nullptr, (i64)0, (float*)nullptr, bnl,
-                       (const float*)nullptr, (i64)0, (const pfst_bn_bwd_rec_t*)nullptr, 0, stats_minmax);
+  const int mode = dw_mode(dw_vec(H, W, {x, y}, {x_bs, y_bs}), dil);
+  dw_launch_conv<false>(mode, dw_plane_route(mode, R, H, W, bnl != nullptr), R, lds, (hipStream_t)stream, x, x_bs, w, y, y_bs, N, C, H, W, dil, flip,
+                        accumulate, stats, stats_minmax, bnl);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
@@ -777,55 +720,21 @@ extern "C" int pfst_dwconv3x3_bwd(const float* dy, long long dy_bs, const float*
   const int R = strip_rows(H, W, dil);
   const size_t lds = strip_lds(R, H, W, dil);
   PFST_CHECK_ARG(lds <= 150 * 1024);
-  static bool set = false;
-  if (!set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_plane_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_plane_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_plane_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    set = true;
-  }
-  const bool vec = (W % 4 == 0) && (((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)x) % 16 == 0) && (dy_bs % 4 == 0) && (dx_bs % 4 == 0) &&
-                   (x_bs % 4 == 0) && (((i64)H * W) % 4 == 0) && (!bn_pre || (((uintptr_t)bn_pre % 16 == 0) && bn_pre_bs % 4 == 0));
+  const bool vec = dw_vec(H, W, {dy, dx, x, bn_pre}, {dy_bs, dx_bs, x_bs, bn_pre ? bn_pre_bs : 0});
 #ifdef PFST_DIAG_DW_MODE2
-  const int mode = !vec ? 0 : (dil % 4 == 0 ? 1 : 2);
+  const int mode = dw_mode(vec, dil, false);
 #else
-  const int mode = !vec ? 0 : (dil % 4 == 0 ? 1 : (dil == 1 ? 3 : 2));
+  const int mode = dw_mode(vec, dil);
 #endif
-  dim3 grid(cdiv(H, R), C, N);
   hipStream_t st = (hipStream_t)stream;
-  constexpr int cpb = 4;
-  float* const none = nullptr;
-  const bool plane = mode != 0 && R == H && (i64)H * W <= 8 * 512 * 4 && cpb > 0 && !bnl && !bn_rec;
+  const bool plane = dw_plane_route(mode, R, H, W, bnl || bn_rec);
   // deterministic mode: per-workgroup slots of a zeroed scratch + an ordered reduction instead of the workgroups' atomic adds into dw
-  const int det_T = pfst_deterministic() ? (plane ? N : (int)grid.x * N) : 0;
+  const int det_T = pfst_deterministic() ? (plane ? N : cdiv(H, R) * N) : 0;
   float* dwk = dw;
-  if (det_T) {
-    const size_t bytes = (size_t)C * det_T * 9 * sizeof(float);
-    dwk = static_cast<float*>(pfst_det_scratch(bytes, st));
-    PFST_CHECK_DET(dwk != nullptr);
-    if (hipMemsetAsync(dwk, 0, bytes, st) != hipSuccess) return PFST_ERR_LAUNCH;
-  }
-  if (plane) {
-    dim3 gp(1, cdiv(C, cpb), N);
-    if (mode == 1)
-      hipLaunchKernelGGL((dwconv3x3_plane_kernel<1, true>), gp, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, cpb, 1, accumulate, none, x, (i64)x_bs, dwk, det_T);
-    else if (mode == 3)
-      hipLaunchKernelGGL((dwconv3x3_plane_kernel<3, true>), gp, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, cpb, 1, accumulate, none, x, (i64)x_bs, dwk, det_T);
-    else
-      hipLaunchKernelGGL((dwconv3x3_plane_kernel<2, true>), gp, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, cpb, 1, accumulate, none, x, (i64)x_bs, dwk, det_T);
-  } else if (mode == 1)
-    hipLaunchKernelGGL((dwconv3x3_kernel<1, true>), grid, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, R, 1, accumulate, none, x, (i64)x_bs, dwk, bnl, bn_pre, (i64)bn_pre_bs, bn_rec, det_T);
-  else if (mode == 2)
-    hipLaunchKernelGGL((dwconv3x3_kernel<2, true>), grid, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, R, 1, accumulate, none, x, (i64)x_bs, dwk, bnl, bn_pre, (i64)bn_pre_bs, bn_rec, det_T);
-  else if (mode == 3)
-    hipLaunchKernelGGL((dwconv3x3_kernel<3, true>), grid, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, R, 1, accumulate, none, x, (i64)x_bs, dwk, bnl, bn_pre, (i64)bn_pre_bs, bn_rec, det_T);
-  else
-    hipLaunchKernelGGL((dwconv3x3_kernel<0, true>), grid, dim3(512), lds, st, dy, dy_bs, w, dx, dx_bs, C, H, W, dil, R, 1, accumulate, none, x, (i64)x_bs, dwk, bnl, bn_pre, (i64)bn_pre_bs, bn_rec, det_T);
-  if (det_T) hipLaunchKernelGGL(dw_det_reduce_kernel, dim3(C), dim3(64), 0, st, dwk, dw, C, det_T);
+  if (det_T) PFST_CHECK_DET((dwk = dw_det_slots(C, det_T, 1, st)) != nullptr);
+  dw_launch_conv<true>(mode, plane, R, lds, st, dy, dy_bs, w, dx, dx_bs, N, C, H, W, dil, 1, accumulate, nullptr, 0, bnl, x, x_bs, dwk, bn_pre,
+                       bn_pre_bs, bn_rec, det_T);
+  if (det_T) dw_det_reduce(dwk, dw, C, det_T, st);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
@@ -875,20 +784,10 @@ extern "C" int pfst_dwconv3x3_multi_fwd(const float* x, long long x_bs, int ns, 
   S.pool = plane_mean;
   S.pool_scale = 1.0f / (float)(H * W);
   S.stats_minmax = stats_minmax;
-  static bool set = false;
-  if (!set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_multi_fwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_multi_fwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_multi_fwd_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    set = true;
-  }
-  const int cpb = 4;
   const size_t lds = (size_t)H * W * sizeof(float);
-  dim3 gp(1, cdiv(C, cpb), N);
+  dim3 gp(1, cdiv(C, DW_CPB), N);
   hipStream_t st = (hipStream_t)stream;
-  if (ns == 1) hipLaunchKernelGGL(dwconv3x3_multi_fwd_kernel<1>, gp, dim3(512), lds, st, x, (i64)x_bs, S, C, H, W, cpb);
-  else if (ns == 2) hipLaunchKernelGGL(dwconv3x3_multi_fwd_kernel<2>, gp, dim3(512), lds, st, x, (i64)x_bs, S, C, H, W, cpb);
-  else hipLaunchKernelGGL(dwconv3x3_multi_fwd_kernel<3>, gp, dim3(512), lds, st, x, (i64)x_bs, S, C, H, W, cpb);
+  dw_for_branches(ns, [&](auto K) { DW_LAUNCH(dwconv3x3_multi_fwd_kernel<decltype(K)::value>, gp, 512, lds, st, x, (i64)x_bs, S, C, H, W, DW_CPB); });
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
@@ -913,40 +812,25 @@ extern "C" int pfst_dwconv3x3_multi_bwd(const float* x, long long x_bs, int ns, 
       S.pre[i] = bn_pre[k];
       S.rec[i] = bn_rec[k];
     }
-  static bool set = false;
-  if (!set) {
-#define PFST_DW_MULTI_ATTR(NS_, B_) \
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_multi_bwd_kernel<NS_, B_, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)
-    PFST_DW_MULTI_ATTR(1, false); PFST_DW_MULTI_ATTR(2, false); PFST_DW_MULTI_ATTR(3, false);
-    PFST_DW_MULTI_ATTR(1, true); PFST_DW_MULTI_ATTR(2, true); PFST_DW_MULTI_ATTR(3, true);
-#undef PFST_DW_MULTI_ATTR
-    set = true;
-  }
-  const int cpb = 4;
   const size_t lds = 2 * (size_t)H * W * sizeof(float);          // gradient plane + forward-input plane
-  dim3 gp(1, cdiv(C, cpb), N);
+  dim3 gp(1, cdiv(C, DW_CPB), N);
   hipStream_t st = (hipStream_t)stream;
-  // deterministic mode (see pfst_dwconv3x3_bwd): every branch's weight gradient through [C][N][9] slots of the scratch
+  // deterministic mode (see pfst_dwconv3x3_bwd): every branch's weight gradient through its own block of [C][N][9] slots
   const int det_T = pfst_deterministic() ? N : 0;
   float* real_dw[3] = {S.dw[0], S.dw[1], S.dw[2]};
   if (det_T) {
-    const size_t per = (size_t)C * det_T * 9, bytes = per * ns * sizeof(float);
-    float* part = static_cast<float*>(pfst_det_scratch(bytes, st));
+    float* part = dw_det_slots(C, det_T, ns, st);
     PFST_CHECK_DET(part != nullptr);
-    if (hipMemsetAsync(part, 0, bytes, st) != hipSuccess) return PFST_ERR_LAUNCH;
-    for (int i = 0; i < 3; ++i) S.dw[i] = part + (size_t)(i < ns ? i : 0) * per;
+    for (int i = 0; i < 3; ++i) S.dw[i] = part + (size_t)(i < ns ? i : 0) * C * det_T * 9;
   }
   // 1024 threads: 2.33 ms per launch against 2.50 ms with 512 (profiles/r04_dw_multi_microbench.txt)
-#define PFST_DW_MULTI_LAUNCH(NS_, B_) \
-  hipLaunchKernelGGL((dwconv3x3_multi_bwd_kernel<NS_, B_, 1024>), gp, dim3(1024), lds, st, x, (i64)x_bs, S, dx, (i64)dx_bs, accumulate, C, H, W, cpb, det_T)
-  if (bnb) {
-    if (ns == 1) { PFST_DW_MULTI_LAUNCH(1, true); } else if (ns == 2) { PFST_DW_MULTI_LAUNCH(2, true); } else { PFST_DW_MULTI_LAUNCH(3, true); }
-  } else {
-    if (ns == 1) { PFST_DW_MULTI_LAUNCH(1, false); } else if (ns == 2) { PFST_DW_MULTI_LAUNCH(2, false); } else { PFST_DW_MULTI_LAUNCH(3, false); }
-  }
-#undef PFST_DW_MULTI_LAUNCH
+  dw_for_branches(ns, [&](auto K) {
+    constexpr int NS = decltype(K)::value;
+    if (bnb) DW_LAUNCH((dwconv3x3_multi_bwd_kernel<NS, true, 1024>), gp, 1024, lds, st, x, (i64)x_bs, S, dx, (i64)dx_bs, accumulate, C, H, W, DW_CPB, det_T);
+    else DW_LAUNCH((dwconv3x3_multi_bwd_kernel<NS, false, 1024>), gp, 1024, lds, st, x, (i64)x_bs, S, dx, (i64)dx_bs, accumulate, C, H, W, DW_CPB, det_T);
+  });
   if (det_T)
-    for (int i = 0; i < ns; ++i) hipLaunchKernelGGL(dw_det_reduce_kernel, dim3(C), dim3(64), 0, st, S.dw[i], real_dw[i], C, det_T);
+    for (int i = 0; i < ns; ++i) dw_det_reduce(S.dw[i], real_dw[i], C, det_T, st);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
@@ -958,35 +842,17 @@ extern "C" int pfst_dwconv3x3_wgrad(const float* x, long long x_bs, const float*
   const int R = strip_rows(H, W, dil);
   const size_t lds = strip_lds(R, H, W, dil);
   PFST_CHECK_ARG(lds <= 150 * 1024);
-  static bool set = false;
-  if (!set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_wgrad_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_wgrad_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_wgrad_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv3x3_wgrad_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    set = true;
-  }
-  const bool vec = (W % 4 == 0) && (((uintptr_t)x | (uintptr_t)dy) % 16 == 0) && (x_bs % 4 == 0) && (dy_bs % 4 == 0) &&
-                   (((i64)H * W) % 4 == 0);
+  const int mode = dw_mode(dw_vec(H, W, {x, dy}, {x_bs, dy_bs}), dil);
   dim3 grid(cdiv(H, R), C, N);
   hipStream_t st = (hipStream_t)stream;
   const int det_T = pfst_deterministic() ? (int)grid.x * N : 0;        // deterministic mode: see pfst_dwconv3x3_bwd
   float* dwk = dw;
-  if (det_T) {
-    const size_t bytes = (size_t)C * det_T * 9 * sizeof(float);
-    dwk = static_cast<float*>(pfst_det_scratch(bytes, st));
-    PFST_CHECK_DET(dwk != nullptr);
-    if (hipMemsetAsync(dwk, 0, bytes, st) != hipSuccess) return PFST_ERR_LAUNCH;
-  }
-  if (vec && dil % 4 == 0)
-    hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, true>), grid, dim3(512), lds, st, x, x_bs, dy, dy_bs, dwk, C, H, W, dil, R, det_T);
-  else if (vec && dil == 1)
-    hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, false, true>), grid, dim3(512), lds, st, x, x_bs, dy, dy_bs, dwk, C, H, W, dil, R, det_T);
-  else if (vec)
-    hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, false>), grid, dim3(512), lds, st, x, x_bs, dy, dy_bs, dwk, C, H, W, dil, R, det_T);
-  else
-    hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<false, false>), grid, dim3(512), lds, st, x, x_bs, dy, dy_bs, dwk, C, H, W, dil, R, det_T);
-  if (det_T) hipLaunchKernelGGL(dw_det_reduce_kernel, dim3(C), dim3(64), 0, st, dwk, dw, C, det_T);
+  if (det_T) PFST_CHECK_DET((dwk = dw_det_slots(C, det_T, 1, st)) != nullptr);
+  dw_for_mode(mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    DW_LAUNCH((dwconv3x3_wgrad_kernel<MODE != 0, MODE == 1, MODE == 3>), grid, 512, lds, st, x, x_bs, dy, dy_bs, dwk, C, H, W, dil, R, det_T);
+  });
+  if (det_T) dw_det_reduce(dwk, dw, C, det_T, st);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }

@@ -9,7 +9,7 @@ bn_finalize_partials.  Unlike there, every bound but the last is applied PER CHA
 max |ref|), so that a wrong tail channel cannot hide behind a larger one; mean and invstd against the vector's maximum.  The inputs carry
 offsets (x = randn + 1, w = randn + 0.25) so that at C == 1 the "vector's maximum" of the mean is not a sum that cancels to nothing; each
 case asserts max |mean| > 0.1 before it uses the bound.  The partial sums themselves are held to the kernel's own output in fp64 within
-64 * 2^-24 * sum |y| (resp. sum y^2): a thread adds at most 34 values in fp32 before the block reduction in fp64 and the final rounding.
+64 * 2^-24 * sum |y| (resp. sum y^2): a thread adds at most 36 values in fp32 (35 rounding steps) before the block reduction in fp64 and the final rounding.
 Fused options keep the bit-identity the suite already proves them by (torch.equal): bnl against the tensor bn_apply writes, bnb against
 bn_backward writing dL/dpre first, the fused backward's dx against the data-gradient kernel, multi-branch outputs / partials against
 per-branch launches.
@@ -655,7 +655,11 @@ C_CASES = [(16, 40, 512, 'strip1', 40, 33),    # 64 KiB / (4 W) - 2 dil = 0 -> o
            (16, 40, 510, 'strip0', 40, 33),    # the same clamp on the scalar kernel
            (1, 136, 128, 'strip3', 2, 128),    # control
            # 16 - 72 rows -> one row per strip, and the 73-row halo is clipped to the 20-row plane: 80 KiB staged, NOT refused (see the refusal test)
-           (36, 20, 1024, 'strip1', 20, 20)]
+           (36, 20, 1024, 'strip1', 20, 20),
+           # a two-row plane above 64 KiB -> one row per strip, two rows staged: 4100 quads per strip, more than the 8 x 512 the weight-gradient
+           # kernel keeps in registers, so its second loop (quads from memory) runs -- reachable only with W > 16384
+           (1, 2, 16400, 'strip3', 2, 2),
+           (4, 2, 16400, 'strip1', 2, 2)]
 
 
 @pytest.mark.parametrize('dil,H,W,route,strips,staged', C_CASES)

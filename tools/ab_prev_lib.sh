@@ -8,5 +8,6 @@ for L in prev new prev new; do
   python bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-alt-math 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d['hbm_kernels']
-print('$L', round(d['value'],3), round(d['ms_per_step'],2), {k:(h[k]['ms_per_step'], h[k]['frac_of_8TBps']) for k in ('pfst_bn_apply','pfst_bn_backward','pfst_dwconv3x3_wgrad')})"
+keys=('pfst_bn_apply','pfst_bn_backward','pfst_dwconv3x3','pfst_dwconv3x3_bwd','pfst_dwconv3x3_multi_fwd','pfst_dwconv3x3_multi_bwd','pfst_dwconv3x3_wgrad')
+print('$L', round(d['value'],3), round(d['ms_per_step'],2), {k:(h[k]['ms_per_step'], h[k]['frac_of_8TBps']) for k in keys if k in h})" || exit 1
 done
