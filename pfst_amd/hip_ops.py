@@ -551,7 +551,9 @@ def wino_conv(x, u, cout, dil, out=None, accumulate=False, keep_v=False, want_st
     keep_v: the transformed input goes to a tensor of its own and is returned as (out, V) for the weight gradient
     (288 GB of HBM: keeping it resident beats re-transforming the input in backward).
     bnl: coef [C, 4] of the conv -> BN -> ReLU layer feeding this one: x is that layer's PRE-normalisation output, normalised by the input
-    transform as it loads (x_amax then = the predicted max of the normalised tensor, bn_finalize_partials(predict_amax=...))"""
+    transform as it loads (x_amax then = the predicted max of the normalised tensor, bn_finalize_partials(predict_amax=...)).
+    bnb = (pre, coef, relu): `pre` needs 16-byte aligned planes and a batch stride in whole float4s (a channel slice of an aligned buffer
+    with HW % 4 == 0); pfst_wino_output refuses any other, before it writes `out`"""
     n, c, h, w = x.shape
     assert bnl is None or (tuple(bnl.shape) == (c, 4) and (u_amax is None or x_amax is not None))
     m, nx = _wino_m(m)

@@ -84,13 +84,15 @@ SENT = -7777.0
 class Guard:
     """an NCHW view with dense planes inside a SENT-filled flat buffer: `front` / `back` whole channels either side of the view in every
     image (back = 3 by default: a plane kernel that ran a whole group of four channels past C - 1 would still land on canaries), `odd` extra
-    floats per image (an odd batch stride), `lead` floats in front of everything (lead = 1: planes start at 16k + 4 bytes)"""
+    floats per image (an odd batch stride), `lead` floats in front of everything (lead = 1: planes start at 16k + 4 bytes); `fill`: the
+    canary value, compared bit for bit (NaN: what a read outside the view multiplies into its result)"""
 
-    def __init__(self, shape, front=1, back=3, lead=0, odd=0):
+    def __init__(self, shape, front=1, back=3, lead=0, odd=0, fill=SENT):
         n, c, h, w = shape
         self.bs = (front + c + back) * h * w + odd
         self.off = lead + front * h * w
-        self.flat = torch.full((lead + n * self.bs + 64,), SENT, device=DEV)
+        self.fill = torch.full((1,), fill, device=DEV).view(torch.int32)
+        self.flat = torch.full((lead + n * self.bs + 64,), fill, device=DEV)
         assert self.flat.data_ptr() % 16 == 0
         self.view = self.flat.as_strided(shape, (self.bs, h * w, w, 1), self.off)
 
@@ -101,10 +103,34 @@ class Guard:
     def intact(self, what=''):
         m = torch.ones(self.flat.numel(), dtype=torch.bool, device=DEV)
         m.as_strided(self.view.shape, self.view.stride(), self.off).fill_(False)
-        bad = (self.flat[m] != SENT).nonzero().flatten()
+        bad = (self.flat.view(torch.int32)[m] != self.fill).nonzero().flatten()
         assert bad.numel() == 0, f'{what}: {bad.numel()} floats outside the view were written, the first at flat index {int(bad[0])}'
 
 
 def out_view(shape, **kw):
     gd = Guard(shape, **kw)
     return gd, gd.view
+
+
+# ---- per-channel bounds of the kernel-level GPU tests and the worst ratio each group measured
+WORST = {}
+
+
+def note(group, kind, ratio):
+    WORST[group, kind] = max(WORST.get((group, kind), 0.0), ratio)
+
+
+def report(group):
+    print(f'worst ratio to the bound, group {group}:', {k[1]: f'{v:.3g}' for k, v in sorted(WORST.items()) if k[0] == group})
+
+
+def chan_close(got, ref, bound, group, kind, cdim=1, what='', scale=None):
+    """max |got - ref| over each channel against bound * that channel's max |ref| (scale: a per-channel magnitude that replaces max |ref|
+    where the reference is a sum that cancels to zero by construction; the caller says why)"""
+    got, ref = got.detach().double().cpu(), ref.double()
+    dims = [d for d in range(ref.dim()) if d != cdim]
+    err, scale = (got - ref).abs().amax(dims), ref.abs().amax(dims) if scale is None else scale
+    assert float(scale.min()) > 0.0
+    ratio = float((err / (bound * scale)).max())
+    note(group, kind, ratio)
+    assert ratio < 1.0, f'{what or kind}: {ratio:.3g} x the bound {bound} (per channel: {(err / scale).tolist()})'

@@ -56,7 +56,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import SENT, Guard, out_view
+from helpers import SENT, Guard, chan_close, note, out_view, report
 from test_hip_ops import g, ops  # noqa: F401  (ops: the module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -65,7 +65,6 @@ DEV = 'cuda'
 FWD, WGRAD, STAT = 1e-5, 1e-4, 2e-5            # inherited from test_hip_ops.test_depthwise
 SUMS = 64 * 2.0 ** -24                         # partial sums against the kernel's own output (docstring)
 LDS = 64 * 1024                                # dwconv.hip DW_LDS_BYTES
-WORST = {}
 
 
 def cdiv(a, b):
@@ -99,26 +98,6 @@ def folded(route):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the checks
-def note(group, kind, ratio):
-    WORST[group, kind] = max(WORST.get((group, kind), 0.0), ratio)
-
-
-def report(group):
-    print(f'worst ratio to the bound, group {group}:', {k[1]: f'{v:.3g}' for k, v in sorted(WORST.items()) if k[0] == group})
-
-
-def chan_close(got, ref, bound, group, kind, cdim=1, what='', scale=None):
-    """max |got - ref| over each channel against bound * that channel's max |ref| (scale: a per-channel magnitude that replaces max |ref|
-    where the reference is a sum that cancels to zero by construction; the caller says why)"""
-    got, ref = got.detach().double().cpu(), ref.double()
-    dims = [d for d in range(ref.dim()) if d != cdim]
-    err, scale = (got - ref).abs().amax(dims), ref.abs().amax(dims) if scale is None else scale
-    assert float(scale.min()) > 0.0
-    ratio = float((err / (bound * scale)).max())
-    note(group, kind, ratio)
-    assert ratio < 1.0, f'{what or kind}: {ratio:.3g} x the bound {bound} (per channel: {(err / scale).tolist()})'
-
-
 def vec_close(got, ref, bound, group, kind):
     got, ref = got.detach().double().cpu(), ref.double()
     ratio = float((got - ref).abs().max() / (bound * ref.abs().max()))
