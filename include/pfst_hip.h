@@ -440,6 +440,24 @@ int pfst_entropy_class_hist(const float* logits, int N, int C, int h, int w, int
 int pfst_entropy_pseudo_label(const float* logits, int N, int C, int h, int w, int H, int W, const float* thr, int annotation_space,
                               unsigned char* label, unsigned long long* counts, pfst_stream_t stream);
 
+/* ---- OHEMPixelSampler (core/seg/sampler/ohem_pixel_sampler.py): the 0/1 pixel-weight map of online hard example mining from
+ * logits [N][C][h][w], resized bilinearly (align_corners=False) to H x W per pixel in registers, and label [N][H][W].  A pixel is valid where
+ * its label is neither ignore_index nor outside [0, C).  The whole sequence (key pass, three histogram levels of an exact radix select whose
+ * digits are chosen on the device, weight pass) is enqueued on `stream` from device pointers only; nothing is read on the host.
+ *   has_thresh = 1: key = the softmax probability of the label, exp(z_y - max) / sum; s = the valid keys in ascending order,
+ *                   k = min(batch_kept, n_valid - 1), threshold = max(s[k], thresh); weight = 1 where valid and key < threshold.
+ *                   Where at least k + 1 keys are <= thresh the threshold is thresh and the select's passes return at once.
+ *   has_thresh = 0: key = coef[y] * max(lse - z_y, 0), coef float [C] >= 0 (the sum over the head's CE terms of loss_weight * class_weight);
+ *                   the k = min(batch_kept, n_valid) valid pixels of largest key get weight 1: every key above the cut value, and of the
+ *                   pixels equal to it the first in raster order (n, y, x) until exactly k are kept.
+ * weight [N][H][W] float, 16-byte aligned, holds the keys (-1 at pixels that are not valid) between the passes and the 0 / 1 map at the end.
+ * info: 4 x 64-bit = (bit pattern of the fp32 threshold / cut value, n_valid, n_kept, k).  keys_out [N][H][W] (or NULL) receives a copy of the
+ * key map, for tests and diagnosis.  workspace: pfst_ohem_workspace_bytes bytes, 8-byte aligned, any contents. */
+int pfst_ohem_workspace_bytes(int N, int H, int W, long long* bytes);
+int pfst_ohem_sample(const float* logits, int N, int C, int h, int w, const unsigned char* label, int H, int W, int ignore_index,
+                     int has_thresh, float thresh, long long batch_kept, const float* coef, void* workspace, float* weight, long long* info,
+                     float* keys_out, pfst_stream_t stream);
+
 /* ---- evaluation: intersect_and_union (rsiseg/core/evaluation/metrics.py:26-86).  hist[3*C] (+)= per-class
  * #intersect, #pred, #label over pixels whose label != ignore_index (caller zeroes hist once per evaluation) */
 int pfst_confusion_hist(const unsigned char* pred, const unsigned char* label, long long n, int C, int ignore_index,

@@ -1291,6 +1291,45 @@ def entropy_pseudo_label(logits, size, thr, annotation_space=False, counts=None)
     return label, counts
 
 
+_ohem_ws_bytes = None
+
+
+def ohem_sample(logits, label_u8, ignore_index=255, thresh=None, batch_kept=100000, coef=None, want_keys=False):
+    """pfst_ohem_sample: OHEMPixelSampler's 0 / 1 weight map [N, H, W] of logits [N, C, h, w] under label_u8 [N, 1, H, W] or [N, H, W], every
+    launch on the current stream and nothing read on the host.  thresh (a float): weight 1 where the label's softmax probability lies below
+    max(s[k], fp32(thresh)), s the ascending sort over the valid pixels and k = min(batch_kept, n_valid - 1).  thresh None: the
+    min(batch_kept, n_valid) valid pixels of largest coef[label] * nll (coef float [C] on the device, >= 0), ties at the cut kept in raster order.
+    -> (weight, info int64 [4] = (bit pattern of the fp32 threshold / cut value, n_valid, n_kept, k)[, keys float [N, H, W]: the map the
+    select ran on, -1 where the pixel is not valid])"""
+    global _ohem_ws_bytes
+    _dense(_chk(logits, F32, 4)), _dense(label_u8, U8)
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    if label_u8.numel() != n * H * W or not 1 <= c <= 255:
+        raise ValueError(f'ohem_sample: logits {tuple(logits.shape)} (1 .. 255 classes) with labels {tuple(label_u8.shape)}')
+    batch_kept = int(batch_kept)
+    if batch_kept < 0:
+        raise ValueError(f'ohem_sample: batch_kept {batch_kept}')
+    if thresh is None:
+        if coef is None or tuple(_dense(coef).shape) != (c,):
+            raise ValueError(f'ohem_sample: without a threshold the per-class loss coefficients are needed, float [{c}]')
+    elif thresh != thresh:
+        raise ValueError('ohem_sample: thresh is NaN')
+    dev = logits.device
+    if _ohem_ws_bytes is None:
+        nbytes = ctypes.c_longlong(0)
+        call('pfst_ohem_workspace_bytes', n, H, W, ctypes.addressof(nbytes))
+        _ohem_ws_bytes = nbytes.value
+    ws = torch.empty(_ohem_ws_bytes // 8, dtype=I64, device=dev)
+    weight = torch.empty(n, H, W, device=dev)
+    info = torch.empty(4, dtype=I64, device=dev)
+    keys = torch.empty(n, H, W, device=dev) if want_keys else None
+    call('pfst_ohem_sample', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), H, W, int(ignore_index), int(thresh is not None),
+         0.0 if thresh is None else float(thresh), batch_kept, _p(None if thresh is not None else coef), ws.data_ptr(), weight.data_ptr(),
+         info.data_ptr(), _p(keys), _stream())
+    return (weight, info, keys) if want_keys else (weight, info)
+
+
 def label_presence(label_u8):
     _dense(label_u8, U8)
     pres = torch.empty(256, dtype=torch.int32, device=label_u8.device)

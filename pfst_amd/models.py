@@ -17,7 +17,8 @@ from . import layers as layers_mod
 from .engine import Var
 from .layers import (BatchNorm2dP, Conv2dP, ConvModule, DepthwiseSeparableConvModule, WeightBatch, bn_eval, conv_bn_act,
                      conv_forward, dwsep_branches)
-from .registry import BACKBONES, HEADS, LOSSES, SEGMENTORS, add_prefix, build_backbone, build_head, build_loss
+from .registry import (BACKBONES, HEADS, LOSSES, PIXEL_SAMPLERS, SEGMENTORS, add_prefix, build_backbone, build_head, build_loss,
+                       build_pixel_sampler)
 
 
 # False: the decode head's Dropout2d as a scaling pass of its own (the fold on / off test); default: folded into sep_bottleneck[1]'s normalisation
@@ -286,6 +287,51 @@ class DiceLoss(nn.Module):
         return out
 
 
+@PIXEL_SAMPLERS.register_module()
+class OHEMPixelSampler:
+    """core/seg/sampler/ohem_pixel_sampler.py on the device (csrc/ohem.hip): the 0 / 1 map of the hard pixels, from the
+    LOW-resolution logits -- the resize is fused, the reference's full-resolution softmax and global sort are an exact radix select whose
+    digits are chosen on the device, and the host reads nothing.  With `thresh` a valid pixel is kept where the softmax probability of its
+    label lies below max(s[k], fp32(thresh)), s the ascending sort of those probabilities, k = min(min_kept * N, n_valid - 1); without, the
+    min(min_kept * N, n_valid) valid pixels of largest unreduced loss are kept (ties at the cut: in raster order, the same from run to run).
+    A label outside [0, C) other than the head's ignore_index is not valid here (the head still reports it after the step).
+    context: the decode head (its ignore_index and loss terms); the terms must be CrossEntropyLoss -- a term that ignores pixel weights has no
+    use for the map and no per-pixel loss to rank by."""
+
+    def __init__(self, context, thresh=None, min_kept=100000):
+        assert min_kept > 1
+        self.context = context
+        self.thresh = None if thresh is None else float(thresh)
+        self.min_kept = int(min_kept)
+        self.last_info = None          # device int64 [4] of the last call: (threshold / cut bits, n_valid, n_kept, k); never read in the step
+        self._coef = None
+        terms = context.loss_decode if isinstance(context.loss_decode, nn.ModuleList) else [context.loss_decode]
+        coef = [0.0] * context.num_classes
+        for term in terms:
+            if not isinstance(term, CrossEntropyLoss):
+                raise NotImplementedError(f'OHEMPixelSampler: the loss term {type(term).__name__} ({term.loss_name}) takes no pixel weights and '
+                                          'has no per-pixel loss; a sampled head needs CrossEntropyLoss terms only')
+            cw = term.class_weight if term.class_weight is not None else [1.0] * context.num_classes
+            if len(cw) != context.num_classes:
+                raise ValueError(f'OHEMPixelSampler: {term.loss_name} has {len(cw)} class weights for {context.num_classes} classes')
+            if not term.loss_weight >= 0 or not all(float(v) >= 0 for v in cw):
+                raise ValueError(f'OHEMPixelSampler: {term.loss_name} has a negative loss_weight or class weight; the per-pixel loss must be >= 0')
+            coef = [a + float(term.loss_weight) * float(v) for a, v in zip(coef, cw)]
+        self.coef = coef               # per class: sum over the terms of loss_weight * class_weight (cross_entropy_loss.py:45-50, 273)
+
+    def _coef_dev(self, dev):
+        if self._coef is None or self._coef.device != dev:
+            self._coef = torch.tensor(self.coef, dtype=torch.float32, device=dev)
+        return self._coef
+
+    def sample(self, seg_logit, seg_label_u8):
+        """seg_logit: the low-resolution logits [N, C, h, w] (tensor or Var); seg_label_u8 [N, 1, H, W] or [N, H, W] -> weight [N, H, W]"""
+        ld = seg_logit.data if isinstance(seg_logit, Var) else seg_logit
+        coef = self._coef_dev(ld.device) if self.thresh is None else None
+        weight, self.last_info = ops.ohem_sample(ld, seg_label_u8, self.context.ignore_index, self.thresh, self.min_kept * ld.shape[0], coef)
+        return weight
+
+
 class BaseDecodeHead(nn.Module):
     def __init__(self, in_channels, channels, *, num_classes, dropout_ratio=0.1, conv_cfg=None, norm_cfg=None,
                  act_cfg=dict(type='ReLU'), in_index=-1, input_transform=None,
@@ -293,7 +339,7 @@ class BaseDecodeHead(nn.Module):
                  sampler=None, align_corners=False, init_cfg=None):
         super().__init__()
         _check_norm(norm_cfg)
-        if input_transform is not None or sampler is not None or align_corners or conv_cfg is not None:
+        if input_transform is not None or align_corners or conv_cfg is not None:
             raise NotImplementedError('decode head options outside the PFST path')
         if not isinstance(loss_decode, (dict, list, tuple)):
             raise TypeError(f'loss_decode must be a dict or a sequence of dicts, but got {type(loss_decode)}')
@@ -305,6 +351,8 @@ class BaseDecodeHead(nn.Module):
         for term in (self.loss_decode if isinstance(self.loss_decode, nn.ModuleList) else [self.loss_decode]):
             if not hasattr(term, 'fused'):
                 raise NotImplementedError(f'{type(term).__name__} has no fused up-sampling form: it cannot be a loss_decode term')
+        # decode_head.py:93-96.  A plain attribute: the sampler is no module and holds the head as its context
+        self.sampler = build_pixel_sampler(sampler, context=self) if sampler is not None else None
         self.conv_seg = Conv2dP(channels, num_classes, 1, bias=True)
         nn.init.normal_(self.conv_seg.weight, 0, 0.01)
         self.dropout_enabled = True            # the teacher switches this off (pfgst.py:247-251)
@@ -343,6 +391,9 @@ class BaseDecodeHead(nn.Module):
     def losses(self, seg_logit, seg_label_u8, seg_weight, tape, grad_scale=1.0):
         # '_bad_labels': labels outside [0, C) other than ignore_index (F.cross_entropy raises on them); travels with the packed
         # scalars of the step and is checked on the host after the step's single read (uda.PFGST.forward_train), never logged
+        if self.sampler is not None:
+            # decode_head.py:258-259: the sampler's map REPLACES the weights the caller passed (PFGST's pseudo-label confidence included)
+            seg_weight = self.sampler.sample(seg_logit, seg_label_u8)
         if not isinstance(self.loss_decode, nn.ModuleList):
             out = self.loss_decode.fused(seg_logit, seg_label_u8, seg_weight, tape, self.ignore_index, grad_scale)
             return {self.loss_decode.loss_name: out[0:1], 'acc_seg': out[1:2], '_bad_labels': out[2:3]}

@@ -57,6 +57,7 @@ def _register_builtin_types():
 
 MODELS = Registry('models')
 BACKBONES = NECKS = HEADS = LOSSES = SEGMENTORS = DISCRIMINATORS = UDA = MODELS
+PIXEL_SAMPLERS = Registry('pixel sampler')          # rsiseg/core/seg/builder.py:4: a registry of its own
 
 
 def build_backbone(cfg):
@@ -69,6 +70,11 @@ def build_head(cfg):
 
 def build_loss(cfg):
     return LOSSES.build(cfg)
+
+
+def build_pixel_sampler(cfg, **default_args):
+    """rsiseg/core/seg/builder.py:7-9; a decode head passes context=self"""
+    return PIXEL_SAMPLERS.build(cfg, default_args)
 
 
 def _check_cfgs(model_cfg, train_cfg, test_cfg):
