@@ -139,9 +139,19 @@ class Tape:
 
 class ParamArena:
     """All parameters of one network in ONE contiguous fp32 device buffer (+ an equally laid out
-    gradient buffer).  EMA, AdamW and the RCCL all-reduce each act on the flat buffer once."""
+    gradient buffer).  EMA, AdamW and the RCCL all-reduce each act on the flat buffer once.
+
+    The flat launches step the SLOTS, the modules read `p.data`: the two must be the same storage when a step starts.  `sync(model)`, called
+    by the steps' ensure_* functions before their first launch, keeps that true:
+      * a parameter whose `.data` no longer points at its slot (`p.data = other`: an evaluation hook swapping EMA values in, a loaded
+        tensor) is RE-ADOPTED -- its current values are copied into the slot and `.data` is rebound to the slot's view.  The optimizer's
+        flat state (momentum, AdamW moments, step count) is kept, as torch keeps the state of a parameter whose `.data` was swapped;
+      * a module whose Parameter OBJECT was replaced (`load_state_dict(assign=True)`, `setattr`, a new sub-module) cannot be stepped: the
+        arena, the cached gradient views and the optimizer hold the old object.  sync raises a RuntimeError naming the parameter, before
+        anything is launched."""
 
     def __init__(self, named_params, device, with_grad=True):
+        self._slots = self._owners = self._tree_version = None
         self.names, self.offsets, self.shapes = [], {}, {}
         off = 0
         for name, p in named_params:
@@ -159,6 +169,50 @@ class ParamArena:
             if with_grad:
                 p.grad = self.view(self.grad, name)
             p._pfst_arena = self
+        base = self.data.data_ptr()
+        self._slots = [(name, p, base + 4 * self.offsets[name]) for name, p in named_params]      # (cached: no view is built to compare)
+
+    def check_objects(self, model):
+        """every parameter of `model` is the object recorded here, and nothing else: else RuntimeError naming the first that is not"""
+        version = model.module_tree_version() if hasattr(model, 'module_tree_version') else None
+        if self._owners is None or version is None or version != self._tree_version:
+            # first call, or a sub-module changed hands: walk the module tree once and compare it with the arena's own list
+            now = list(model.named_parameters())
+            mine = {id(p): name for name, p, _ in self._slots}
+            for name, p in now:
+                if id(p) not in mine:
+                    raise RuntimeError(f"parameter '{name}' is not the Parameter object this model's ParamArena and optimizer were built "
+                                       'with (load_state_dict(assign=True), setattr or a replaced sub-module): they would go on stepping the '
+                                       'old object.  Assign values with `p.data = ...` / `p.copy_(...)`, or rebuild the optimizer and the arena')
+            if len(now) != len(self._slots):
+                gone = sorted(set(mine.values()) - {mine[id(p)] for _, p in now})
+                raise RuntimeError(f"parameter '{gone[0]}' of this model's ParamArena is no longer a parameter of the model")
+            names = {id(p): name for name, p in now}
+            self._owners = [(m._parameters, k, p, names[id(p)]) for m in model.modules() for k, p in m._parameters.items() if p is not None]
+            self._tree_version = version
+            return
+        for params, k, p, name in self._owners:
+            if params.get(k) is not p:
+                raise RuntimeError(f"parameter '{name}' is not the Parameter object this model's ParamArena and optimizer were built with "
+                                   '(load_state_dict(assign=True), setattr): they would go on stepping the old object.  Assign values with '
+                                   '`p.data = ...` / `p.copy_(...)`, or rebuild the optimizer and the arena')
+
+    def sync(self, model):
+        """before a step's first launch (class docstring): raise for a replaced Parameter object, re-adopt every parameter whose `.data` was
+        rebound.  Address compares against cached integers while nothing moved: no view, no launch."""
+        self.check_objects(model)
+        self.readopt()
+
+    def readopt(self):
+        """every parameter whose `.data` left its slot: values into the slot, `.data` back onto the slot's view"""
+        for name, p, ptr in self._slots:
+            if p.data_ptr() != ptr:
+                v = self.view(self.data, name)
+                if tuple(p.shape) != self.shapes[name] or p.dtype != v.dtype:
+                    raise RuntimeError(f"parameter '{name}' was rebound to a {tuple(p.shape)} {p.dtype} tensor; its ParamArena slot is "
+                                       f'{self.shapes[name]} {v.dtype}')
+                v.copy_(p.data)
+                p.data = v
 
     def view(self, flat, name):
         o = self.offsets[name]

@@ -69,14 +69,22 @@ _h2d_const = {}
 def h2d_small(t_cpu, dev, tag):
     """a small per-step host tensor (augmentation parameters, class choices) to the device WITHOUT the stream synchronisation a pageable
     copy implies (`.to(dev)` of pageable memory makes the host wait for everything queued on the stream -- the host then starts the next
-    pass with no lead over the device): staged through a pinned buffer cached per (tag, shape, dtype), copied asynchronously.  A buffer is
-    reused one step later at the earliest; the step's blocking read of its log values lies in between"""
-    key = (tag, tuple(t_cpu.shape), t_cpu.dtype)
-    st = _h2d_stage.get(key)
-    if st is None:
-        st = _h2d_stage[key] = torch.empty(t_cpu.shape, dtype=t_cpu.dtype, pin_memory=True)
+    pass with no lead over the device): staged through a pinned buffer cached per (tag, shape, dtype, device), copied asynchronously.  An event
+    recorded behind each copy guards the buffer: the next call with the same key rewrites it only once that copy has run.  In the train step
+    a buffer is reused one step later at the earliest, with the step's blocking read of its log values in between -- the event has long
+    completed, the query returns at once and nothing waits; only a caller that reuses a key while its stream is still busy blocks, for that
+    one copy"""
+    key = (tag, tuple(t_cpu.shape), t_cpu.dtype, str(dev))
+    ent = _h2d_stage.get(key)
+    if ent is None:
+        ent = _h2d_stage[key] = (torch.empty(t_cpu.shape, dtype=t_cpu.dtype, pin_memory=True), torch.cuda.Event())
+    st, evt = ent
+    if not evt.query():                  # (an event never recorded counts as complete)
+        evt.synchronize()
     st.copy_(t_cpu)
-    return st.to(dev, non_blocking=True)
+    out = st.to(dev, non_blocking=True)
+    evt.record(torch.cuda.current_stream(dev))
+    return out
 
 
 def const_tensor(values, dev, dtype=F32):

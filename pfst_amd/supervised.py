@@ -37,11 +37,17 @@ def step_state(model):
 
 
 def ensure_arena(model, device):
+    """the model's parameter arena on `device`, built on the first step, and -- on every step, before its first launch -- in step with the
+    model (ParamArena.sync): a parameter whose `.data` was rebound since the last step (an evaluation hook that swapped other values in) is
+    re-adopted, i.e. its current values are copied into its slot and `.data` is rebound to the slot, the optimizer's flat state kept; a
+    Parameter OBJECT that was replaced (load_state_dict(assign=True), setattr) raises a RuntimeError naming it, since the optimizer holds
+    the old one"""
     st = step_state(model)
     if st.arena is None or st.arena.data.device != device:
         model.to(device)
         st.arena = ParamArena(list(model.named_parameters()), device, with_grad=True)
         st.grad_ptrs = None
+    st.arena.sync(model)
     return st.arena
 
 

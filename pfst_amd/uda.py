@@ -268,16 +268,24 @@ class PFGST(UDADecorator):
         return get_module(self.ema_model)
 
     def _ensure_arenas(self, device):
-        a = self._student_arena
-        if a is not None and a.data.device == device:
-            return
+        """the student's and the teacher's parameter arenas on `device`, built on the first step, and -- on every step, before its first
+        launch -- in step with the two models (engine.ParamArena): a student or teacher parameter whose `.data` was rebound since the last
+        step (EMA values swapped in for an evaluation, a loaded tensor) is re-adopted, i.e. its current values are copied into its slot and
+        `.data` is rebound to the slot, the optimizer's flat state kept; a Parameter OBJECT that was replaced (load_state_dict(assign=True),
+        setattr) raises a RuntimeError naming it, since the optimizer and the EMA launch hold the old one"""
         model, ema = self.get_model(), self.get_ema_model()
-        model.to(device), ema.to(device)
-        for aux in (self.aux_losses if self.apply_aux else []):
-            aux.to(device)
-        self._student_arena = ParamArena(list(model.named_parameters()), device, with_grad=True)
-        self._teacher_arena = ParamArena(list(ema.named_parameters()), device, with_grad=False)
-        assert self._student_arena.numel == self._teacher_arena.numel
+        a = self._student_arena
+        if a is None or a.data.device != device:
+            model.to(device), ema.to(device)
+            for aux in (self.aux_losses if self.apply_aux else []):
+                aux.to(device)
+            self._student_arena = ParamArena(list(model.named_parameters()), device, with_grad=True)
+            self._teacher_arena = ParamArena(list(ema.named_parameters()), device, with_grad=False)
+            assert self._student_arena.numel == self._teacher_arena.numel
+        self._student_arena.check_objects(model)          # both checks in front of the first copy: an error leaves nothing launched
+        self._teacher_arena.check_objects(ema)
+        self._student_arena.readopt()
+        self._teacher_arena.readopt()
 
     @property
     def student_arena(self):
