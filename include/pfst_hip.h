@@ -600,6 +600,27 @@ int pfst_dice_upsample_bwd(const float* logits, int N, int C, int h, int w, cons
                            int ignore_index, float exponent, int form, const float* lse, const float* coef, float scale,
                            float* work, float* dlogits, int accumulate, pfst_stream_t stream);
 
+/* ---- fused bilinear upsample + per-(pixel, class) logistic losses: FocalLoss (losses/focal_loss.py:13-68) and CrossEntropyLoss(use_sigmoid)
+ * (cross_entropy_loss.py:68-156) behind decode_head.py:249-283 ----
+ * x = up(logits), t = [label == c], y = t ? -x : x, q = sigmoid(y), b = softplus(y), k = coef[c][t ? 0 : 1] (coef[C][2] = (k_pos, k_neg)):
+ *   l = k q^gamma b, summed with pix_weight (NULL: 1) over the pixels with label != ignore_index and label < C; no softmax across classes.
+ * form: 0 = generic kernels (any H x W, C <= 255), 4 / 8 = inter-cell block kernels (H == form*h, W == form*w, C <= 8, pix_weight 8-byte and
+ * label 2-byte aligned).  Every workgroup STORES one row of partials, no atomics: slab[N][blocks][C] = the class's weighted loss sum,
+ * counts[N][blocks][3] = (#correct, #valid, #bad labels) as pfst_ce_upsample_fwd counts them.  gamma >= 0 (NaN: -1).
+ * blocks: form 0: ceil(H*W/1024); form 4: ceil((w+1)/16)*ceil((h+1)/32); form 8: ceil((w+1)/16)*ceil((h+1)/16). */
+int pfst_sigloss_upsample_fwd(const float* logits, int N, int C, int h, int w, const unsigned char* label, const float* pix_weight,
+                              int H, int W, int ignore_index, const float* coef, float gamma, int form, double* slab,
+                              long long* counts, int blocks, pfst_stream_t stream);
+/* adds the rows in a fixed order: sums[N*C + 3] = the loss sum per (n, c), then (#correct, #valid, #bad);
+ * out[3] = (loss_weight / divisor * sum, acc_seg %, #bad) laid out as pfst_ce_finalize's */
+int pfst_sigloss_finalize(const double* slab, const long long* counts, int N, int C, int blocks, double divisor, double loss_weight,
+                          double* sums, float* out, pfst_stream_t stream);
+/* dlogits (+)= scale * adjoint of the resize applied to pix_weight * valid * dl/dx, dl/dx = (t ? -1 : 1) k q^gamma (q + gamma (1 - q) b);
+ * gather form, no atomics, no full-resolution buffer at any C */
+int pfst_sigloss_upsample_bwd(const float* logits, int N, int C, int h, int w, const unsigned char* label, const float* pix_weight,
+                              int H, int W, int ignore_index, const float* coef, float gamma, int form, float scale, float* dlogits,
+                              int accumulate, pfst_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1225,6 +1225,70 @@ def dice_upsample_bwd(logits, label_u8, lse, coef, scale, ignore_index=255, expo
     return out
 
 
+def sigloss_form(logits, label_u8, pix_weight=None, generic=False):
+    """which kernels a sigmoid loss term (FocalLoss, CrossEntropyLoss(use_sigmoid)) runs on, by dice_form's rules: 4 / 8 = the inter-cell
+    block kernels of that ratio (C <= 8, H == S h, W == S w, pixel weights 8-byte and label 2-byte aligned), 0 = the generic ones;
+    generic=True forces 0.  -> (form, rows of partials per image)"""
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    for s, tile_rows in ((4, 32), (8, 16)):
+        if (not generic and c <= 8 and H == s * h and W == s * w and label_u8.data_ptr() % 2 == 0 and h < 65535 * 15
+                and (pix_weight is None or pix_weight.data_ptr() % 8 == 0)):
+            return s, ((w + 16) // 16) * ((h + tile_rows) // tile_rows)
+    return 0, (H * W + 1023) // 1024
+
+
+def _sigloss_args(logits, label_u8, pix_weight, coef):
+    _dense(logits), _dense(label_u8, U8)
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    assert label_u8.numel() == n * H * W
+    if pix_weight is not None:
+        assert _dense(pix_weight).numel() == n * H * W
+    if tuple(_dense(coef).shape) != (c, 2):
+        raise ValueError(f'sigmoid loss: the (k_pos, k_neg) table must be float [{c}, 2], got {tuple(coef.shape)}')
+    return n, c, h, w, H, W
+
+
+def sigloss_upsample_fwd(logits, label_u8, coef, gamma=0.0, pix_weight=None, ignore_index=255, generic=False):
+    """Per-workgroup partials of sum w_px valid k q^gamma b over sigmoid(up(logits)) and the head's accuracy counts; no atomics, a fixed order.
+    coef float [C, 2] = (k_pos, k_neg) per class.
+    -> (slab float64 [N, blocks, C], counts int64 [N, blocks, 3] = (#correct, #valid, #bad), form)"""
+    n, c, h, w, H, W = _sigloss_args(logits, label_u8, pix_weight, coef)
+    if not float(gamma) >= 0.0:
+        raise ValueError(f'sigmoid loss: gamma must be >= 0, got {gamma}')
+    form, blocks = sigloss_form(logits, label_u8, pix_weight, generic)
+    slab = torch.empty(n, blocks, c, dtype=F64, device=logits.device)
+    counts = torch.empty(n, blocks, 3, dtype=I64, device=logits.device)
+    call('pfst_sigloss_upsample_fwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), _p(pix_weight), H, W, int(ignore_index),
+         coef.data_ptr(), float(gamma), form, slab.data_ptr(), counts.data_ptr(), blocks, _stream())
+    return slab, counts, form
+
+
+def sigloss_finalize(slab, counts, divisor, loss_weight=1.0):
+    """adds the partials in a fixed order -> (out float32[3] = (loss_weight / divisor * sum, acc_seg %, #bad labels),
+    sums float64 [N*C + 3] = the loss sum per (n, c), then (#correct, #valid, #bad))"""
+    n, blocks, c = slab.shape
+    assert tuple(counts.shape) == (n, blocks, 3)
+    sums = torch.empty(n * c + 3, dtype=F64, device=slab.device)
+    out = torch.empty(3, device=slab.device)
+    call('pfst_sigloss_finalize', slab.data_ptr(), counts.data_ptr(), n, c, blocks, float(divisor), float(loss_weight), sums.data_ptr(),
+         out.data_ptr(), _stream())
+    return out, sums
+
+
+def sigloss_upsample_bwd(logits, label_u8, coef, scale, gamma=0.0, pix_weight=None, ignore_index=255, out=None, accumulate=False, generic=False):
+    """d logits of a sigmoid loss term (gather form, no atomics); `scale` carries loss_weight / divisor and the step's gradient scale"""
+    n, c, h, w, H, W = _sigloss_args(logits, label_u8, pix_weight, coef)
+    if out is None:
+        assert not accumulate
+        out = torch.empty_like(logits)
+    form, _ = sigloss_form(logits, label_u8, pix_weight, generic)
+    call('pfst_sigloss_upsample_bwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), _p(pix_weight), H, W, int(ignore_index),
+         coef.data_ptr(), float(gamma), form, float(scale), _dense(out).data_ptr(), int(accumulate), _stream())
+    return out
+
+
 def pseudo_label(logits, size, threshold, want_i64=True, want_conf=False, want_prob=False):
     """-> (label int64 [N,H,W] | None, label uint8 [N,H,W], count uint64-as-int64 [1][, conf float [N,H,W]][, max prob float [N,H,W]])"""
     _dense(logits)

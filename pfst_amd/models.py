@@ -193,17 +193,21 @@ def get_class_weight(class_weight):
 @LOSSES.register_module()
 class CrossEntropyLoss(nn.Module):
     """Softmax CE with pixel weights, optional class weights, ignore_index, mean over ALL pixels
-    (avg_non_ignore=False), fused with the bilinear up-sampling of the logits and the accuracy."""
+    (avg_non_ignore=False), fused with the bilinear up-sampling of the logits and the accuracy.
+    use_sigmoid=True: cross_entropy_loss.py:68-156 -- one-hot labels and binary_cross_entropy_with_logits per (pixel, class), class_weight as
+    its pos_weight (the positive term only), mean over all N C H W elements; csrc/sigmoid_loss.hip, DESIGN.md section 8k."""
 
     def __init__(self, use_sigmoid=False, use_mask=False, reduction='mean', class_weight=None, loss_weight=1.0,
                  loss_name='loss_ce', avg_non_ignore=False):
         super().__init__()
-        if use_sigmoid or use_mask or reduction != 'mean' or avg_non_ignore:
-            raise NotImplementedError('pfst_amd CrossEntropyLoss: softmax CE, reduction=mean, avg_non_ignore=False only')
+        if use_mask or reduction != 'mean' or avg_non_ignore:
+            raise NotImplementedError('pfst_amd CrossEntropyLoss: softmax or sigmoid CE, reduction=mean, avg_non_ignore=False, use_mask=False only')
+        self.use_sigmoid = bool(use_sigmoid)
         self.class_weight = get_class_weight(class_weight)
         self.loss_weight = loss_weight
         self._loss_name = loss_name
         self._cw = None
+        self._coef = None
 
     @property
     def loss_name(self):
@@ -216,10 +220,22 @@ class CrossEntropyLoss(nn.Module):
             self._cw = torch.tensor(self.class_weight, dtype=torch.float32, device=dev)
         return self._cw
 
+    def sigmoid_coef(self, num_classes):
+        """the (k_pos, k_neg) rows of the sigmoid form: pos_weight on the positive term, 1 on the negative"""
+        if num_classes < 2:
+            raise NotImplementedError('CrossEntropyLoss(use_sigmoid=True): one-channel (binary) logits are not built, num_classes >= 2 only')
+        cw = self.class_weight if self.class_weight is not None else [1.0] * num_classes
+        if len(cw) != num_classes:
+            raise ValueError(f'CrossEntropyLoss(use_sigmoid=True): class_weight has {len(cw)} entries for {num_classes} classes')
+        return [[float(v), 1.0] for v in cw]
+
     def fused(self, logits, label_u8, weight, tape, ignore_index=255, grad_scale=1.0, share=None):
         """logits: Var [N,C,h,w] (low res); label_u8 [N,1,H,W] or [N,H,W]; weight [N,H,W] or None.
         share: a dict the terms of one head's loss list pass along -- the log-sum-exp map is left in it for a DiceLoss that follows.
         -> device tensor [loss, acc_seg, #bad labels]"""
+        if self.use_sigmoid:
+            return _sigmoid_fused(self, 'bce', self.sigmoid_coef(logits.data.shape[1]), 0.0, 'mean', logits, label_u8, weight, tape,
+                                  ignore_index, grad_scale)
         ld = logits.data
         n = ld.shape[0]
         H, W = label_u8.shape[-2:]
@@ -237,6 +253,78 @@ class CrossEntropyLoss(nn.Module):
             tape.record(bwd, dict(op='ce', x=logits, out=None, label=label_u8, weight=weight, class_weight=self.class_weight,
                                   loss_weight=grad_scale * self.loss_weight, ignore_index=ignore_index))
         return out
+
+
+def _sigmoid_fused(term, op, coef_rows, gamma, reduction, logits, label_u8, weight, tape, ignore_index, grad_scale):
+    """the shared body of the sigmoid terms (FocalLoss, CrossEntropyLoss(use_sigmoid)): forward partials, the ordered sum, the tape record.
+    Neither reads or writes share['lse'].  The divisor is known on the host: N C H W for 'mean' and for 'none' (the reference returns the
+    [N,C,H,W] map there and _parse_losses takes its mean), 1 for 'sum'."""
+    ld = logits.data
+    n, c = ld.shape[:2]
+    H, W = label_u8.shape[-2:]
+    if term._coef is None or term._coef.device != ld.device or term._coef.shape[0] != c:
+        term._coef = torch.tensor(coef_rows, dtype=torch.float32, device=ld.device)
+    coef = term._coef
+    divisor = 1.0 if reduction == 'sum' else float(n * c * H * W)
+    slab, counts, _ = ops.sigloss_upsample_fwd(ld, label_u8, coef, gamma, weight, ignore_index)
+    out, _ = ops.sigloss_finalize(slab, counts, divisor, term.loss_weight)
+    if tape is not None:
+        scale = grad_scale * term.loss_weight / divisor
+
+        def bwd():
+            buf, accf = logits.grad_target()
+            ops.sigloss_upsample_bwd(ld, label_u8, coef, scale, gamma, weight, ignore_index, out=buf, accumulate=accf)
+        tape.record(bwd, dict(op=op, x=logits, out=None, label=label_u8, weight=weight, coef=coef_rows, gamma=gamma, reduction=reduction,
+                              loss_weight=grad_scale * term.loss_weight, ignore_index=ignore_index))
+    return out
+
+
+@LOSSES.register_module()
+class FocalLoss(nn.Module):
+    """losses/focal_loss.py (its py_sigmoid_focal_loss branch) fused with the bilinear up-sampling of the logits (csrc/sigmoid_loss.hip; the
+    closed form: DESIGN.md section 8k): per (pixel, class) alpha_t (1 - p_t)^gamma BCE(x, t), times the class weight, the pixel weight and
+    the validity of the label under the HEAD's ignore_index; no softmax across classes.  alpha: a float, or a list of C floats indexing the
+    class axis."""
+
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.5, reduction='mean', class_weight=None, loss_weight=1.0, loss_name='loss_focal'):
+        super().__init__()
+        if use_sigmoid is not True:
+            raise NotImplementedError('FocalLoss: only sigmoid focal loss is supported (use_sigmoid=True), as in the reference')
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError(f"FocalLoss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not float(gamma) >= 0.0:
+            raise ValueError(f'FocalLoss: gamma must be a number >= 0, got {gamma!r}')
+        alphas = list(alpha) if isinstance(alpha, (list, tuple)) else [alpha]
+        if not alphas or any(isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) <= 1.0 for a in alphas):
+            raise ValueError(f'FocalLoss: alpha (a float or a list of floats) must lie in [0, 1], got {alpha!r}')
+        if class_weight is not None and not isinstance(class_weight, (list, tuple)):
+            raise TypeError('FocalLoss: class_weight must be None or a list')
+        self.use_sigmoid, self.gamma, self.reduction = use_sigmoid, gamma, reduction
+        self.alpha = list(alpha) if isinstance(alpha, (list, tuple)) else alpha
+        self.class_weight = None if class_weight is None else list(class_weight)
+        self.loss_weight = loss_weight
+        self._loss_name = loss_name
+        self._coef = None
+
+    loss_name = CrossEntropyLoss.loss_name
+
+    def coef_rows(self, num_classes):
+        """(k_pos, k_neg) = class_weight_c * (alpha_c, 1 - alpha_c) per class"""
+        c = num_classes
+        if c < 2:
+            raise NotImplementedError('FocalLoss: one-channel (binary) logits are not built, num_classes >= 2 only')
+        alpha = self.alpha if isinstance(self.alpha, list) else [self.alpha] * c
+        if len(alpha) != c:
+            raise ValueError(f'FocalLoss: alpha has {len(alpha)} entries for {c} classes')
+        cw = self.class_weight if self.class_weight is not None else [1.0] * c
+        if len(cw) != c:
+            raise ValueError(f'FocalLoss: class_weight has {len(cw)} entries for {c} classes')
+        return [[float(w) * float(a), float(w) * (1.0 - float(a))] for w, a in zip(cw, alpha)]
+
+    def fused(self, logits, label_u8, weight, tape, ignore_index=255, grad_scale=1.0, share=None):
+        """the interface of CrossEntropyLoss.fused -> device tensor [loss, acc_seg, #bad labels]"""
+        return _sigmoid_fused(self, 'focal', self.coef_rows(logits.data.shape[1]), float(self.gamma), self.reduction, logits, label_u8, weight,
+                              tape, ignore_index, grad_scale)
 
 
 @LOSSES.register_module()
@@ -311,6 +399,10 @@ class OHEMPixelSampler:
             if not isinstance(term, CrossEntropyLoss):
                 raise NotImplementedError(f'OHEMPixelSampler: the loss term {type(term).__name__} ({term.loss_name}) takes no pixel weights and '
                                           'has no per-pixel loss; a sampled head needs CrossEntropyLoss terms only')
+            if term.use_sigmoid and self.thresh is None:
+                # the reference ranks the term's unreduced loss there, which is an [N,C,H,W] map for the sigmoid form, and fails
+                raise NotImplementedError(f'OHEMPixelSampler: without thresh the pixels are ranked by the unreduced loss, which {term.loss_name} '
+                                          '(use_sigmoid=True) has per (pixel, class) only; give thresh')
             cw = term.class_weight if term.class_weight is not None else [1.0] * context.num_classes
             if len(cw) != context.num_classes:
                 raise ValueError(f'OHEMPixelSampler: {term.loss_name} has {len(cw)} class weights for {context.num_classes} classes')

@@ -2,9 +2,10 @@
 """The supervised step with CrossEntropyLoss heads beside the same step with [CrossEntropyLoss, DiceLoss] in both heads, in ONE process on one
 box at the flagship workload's size (b = 8 x 1024^2 unless --batch / --size): blocks of steps of the two alternate as in
 tools/supervised_step_bench.py (every block starts and ends with a device synchronise, every step is timed by the host clock), the median
-per kind over all blocks is printed as one JSON line.
+per kind over all blocks is printed as one JSON line.  --terms chooses what the second step lists after its CE term: any of dice, focal (the
+FocalLoss defaults) and bce (CrossEntropyLoss(use_sigmoid=True)), comma-separated, in that order -- `--terms focal` is the cost of a Focal term.
 
-    python tools/dice_step_bench.py [--steps 24] [--blocks 4] [--warmup 3] [--batch 8] [--size 1024]"""
+    python tools/dice_step_bench.py [--steps 24] [--blocks 4] [--warmup 3] [--batch 8] [--size 1024] [--terms dice]"""
 import argparse
 import copy
 import json
@@ -26,7 +27,14 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=None)
     ap.add_argument('--size', type=int, default=None)
+    ap.add_argument('--terms', default='dice', help='the terms listed after CE in the second step: dice, focal, bce (comma-separated)')
     args = ap.parse_args()
+    extra = {'dice': lambda lw: dict(type='DiceLoss', loss_weight=lw), 'focal': lambda lw: dict(type='FocalLoss', loss_weight=lw),
+             'bce': lambda lw: dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=lw, loss_name='loss_bce')}
+    terms = [t.strip() for t in args.terms.split(',') if t.strip()]
+    if not terms or any(t not in extra for t in terms):
+        ap.error(f'--terms takes a comma-separated list of {sorted(extra)}, got {args.terms!r}')
+    listed = 'ce_' + '_'.join(terms)
     import numpy as np
     import torch
     import pfst_amd  # noqa: F401
@@ -39,11 +47,11 @@ def main():
     batch = {k: v for k, v in synth_batch(b, size, w['num_classes'], w['in_channels'], seed=1234, device='cuda').items() if not k.startswith('target_')}
     random.seed(0); np.random.seed(0); torch.manual_seed(0); torch.cuda.manual_seed_all(0)
     kinds = {}
-    for kind in ('ce', 'ce_dice'):
+    for kind in ('ce', listed):
         mcfg = copy.deepcopy(cfg['model'])
-        if kind == 'ce_dice':
+        if kind == listed:
             for head, lw in (('decode_head', 3.0), ('auxiliary_head', 1.2)):
-                mcfg[head]['loss_decode'] = [dict(mcfg[head]['loss_decode']), dict(type='DiceLoss', loss_weight=lw)]
+                mcfg[head]['loss_decode'] = [dict(mcfg[head]['loss_decode'])] + [extra[t](lw) for t in terms]
         model = build_segmentor(mcfg)
         fill_state_dict(model.state_dict(), 0)
         model.cuda()
@@ -72,7 +80,7 @@ def main():
     res = dict(batch=b, size=size, steps_per_kind=len(times['ce']), blocks=args.blocks)
     for kind, v in times.items():
         res[kind] = dict(median_ms=round(statistics.median(v), 2), min_ms=round(min(v), 2), max_ms=round(max(v), 2))
-    res['dice_adds_ms'] = round(res['ce_dice']['median_ms'] - res['ce']['median_ms'], 2)
+    res['_'.join(terms) + '_adds_ms'] = round(res[listed]['median_ms'] - res['ce']['median_ms'], 2)
     print(json.dumps(res))
 
 
