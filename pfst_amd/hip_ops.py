@@ -1133,6 +1133,8 @@ def ce_upsample_fwd(logits, label_u8, pix_weight=None, class_weight=None, ignore
     assert label_u8.numel() == n * H * W
     if pix_weight is not None:
         assert _dense(pix_weight).numel() == n * H * W
+    if class_weight is not None:
+        assert _dense(class_weight).numel() == c
     lse = torch.empty(n, H, W, device=logits.device)
     acc = torch.zeros(4, dtype=F64, device=logits.device)
     call('pfst_ce_upsample_fwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), _p(pix_weight), _p(class_weight), H, W,
@@ -1141,11 +1143,18 @@ def ce_upsample_fwd(logits, label_u8, pix_weight=None, class_weight=None, ignore
 
 
 def ce_upsample_bwd(logits, label_u8, lse, scale, pix_weight=None, class_weight=None, ignore_index=255, out=None, accumulate=False):
+    _dense(logits), _dense(label_u8, U8)                       # as ce_upsample_fwd: a view would be read as if it were dense
     n, c, h, w = logits.shape
     H, W = label_u8.shape[-2:]
+    assert label_u8.numel() == n * H * W and lse.numel() == n * H * W
+    if pix_weight is not None:
+        assert _dense(pix_weight).numel() == n * H * W
+    if class_weight is not None:
+        assert _dense(class_weight).numel() == c
     if out is None:
         assert not accumulate
         out = torch.empty_like(logits)
+    assert out.shape == logits.shape
     call('pfst_ce_upsample_bwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), _p(pix_weight), _p(class_weight), H, W,
          ignore_index, _dense(lse).data_ptr(), float(scale), _dense(out).data_ptr(), int(accumulate), _stream())
     return out
