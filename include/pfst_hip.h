@@ -329,6 +329,28 @@ int pfst_broadcast_hw(const float* v, float* y, long long y_bs, int N, int C, in
 /* y_amax (both): NULL, or the slot group (1024 floats, zeroed) that receives max |y| of what the launch writes (f16x3 scale, csrc/amax.h) */
 /* v[n][c] = sum_hw dy[n][c][hw]  (adjoint of the 1x1 -> HxW bilinear broadcast) */
 int pfst_reduce_hw(const float* dy, long long dy_bs, float* v, int N, int C, int HW, pfst_stream_t stream);
+/* ---- plane <-> pyramid of small grids (csrc/pyramid.hip): PSPHead's pooling pyramid (psp_head.py:9-50) both ways.
+ * K <= PFST_PYR_MAX_SCALES grids of s_k x s_k cells, 1 <= s_k <= PFST_PYR_MAX_SCALE (`scales`, `chan_off`: HOST arrays of K ints; the grid
+ * pointers: HOST arrays of K device pointers, grid k dense [N][C][s_k][s_k]).  S1 = sum_k s_k.  Tables (DEVICE, built by the host once per
+ * (H, W, scales), pfst_amd.hip_ops.pyramid_operator): op_h [S1][H] / op_w [S1][W] the dense per-axis operator D, row off1[k] + i = cell
+ * row / column i of scale k; span_* [S1][2] the [begin, end) of each row's non-zeros; tspan_h [K][H][2] / tspan_w [K][W][2] the
+ * [begin, end) of the cells of scale k whose operator row is non-zero at that pixel row / column.  No atomics, fixed summation order. */
+#define PFST_PYR_MAX_SCALES 6
+#define PFST_PYR_MAX_SCALE 8
+/* outs[k][n][c] = Dh_k . X . Dw_k^T.  shared != 0: X = x[n][chan_off[0] + c] for every scale, read once (AdaptiveAvgPool2d(s_k) of one tensor);
+ * shared == 0: X = x[n][chan_off[k] + c] (the adjoint of the resize into the concat slices).  x: dense planes, batch stride x_bs. */
+int pfst_pyramid_reduce(const float* x, long long x_bs, int N, int C, int H, int W, int K, const int* scales, const int* chan_off, int shared,
+                        const float* op_h, const float* op_w, const int* span_h, const int* span_w, float* const* outs, pfst_stream_t stream);
+/* sliced == 0: y[n][c] = (accumulate ? y : 0) + (add ? add[n][c] : 0) + sum_k Dh_k^T . G_k . Dw_k (the adjoint of the pooling, written once);
+ * sliced != 0: y[n][chan_off[k] + c] = (accumulate ? y : 0) + Dh_k^T . G_k . Dw_k for every k (the bilinear resize of each grid into its slice
+ * of the concat; add must be NULL).  y_amax: NULL, or the slot group that receives max |y| of what is written (not with accumulate). */
+int pfst_pyramid_expand(const float* const* grids, int N, int C, int H, int W, int K, const int* scales, const int* chan_off, int sliced, float* y,
+                        long long y_bs, const float* add, long long add_bs, int accumulate, const float* op_h, const float* op_w,
+                        const int* tspan_h, const int* tspan_w, float* y_amax, pfst_stream_t stream);
+/* y[n][0:CHW] = (accumulate ? y : 0) + x[n][0:CHW] between two dense-plane views (the identity slice of a concat buffer and its adjoint);
+ * y_amax as above */
+int pfst_copy_planes(const float* x, long long x_bs, float* y, long long y_bs, int N, long long CHW, int accumulate, float* y_amax,
+                     pfst_stream_t stream);
 /* F.interpolate(mode='nearest') by an integer factor on [NC][h][w] maps and its adjoint (pfgst_loss.py:57-58) */
 int pfst_upsample_nearest(const float* x, float* y, int NC, int h, int w, int factor, pfst_stream_t stream);
 int pfst_upsample_nearest_bwd(const float* dy, float* dx, int NC, int h, int w, int factor, pfst_stream_t stream);

@@ -875,6 +875,150 @@ def broadcast_hw(v, out, scale=1.0, accumulate=False, amax=None):
     return out
 
 
+# ---------------------------------------------------------------- plane <-> pyramid of small grids (csrc/pyramid.hip)
+PYR_MAX_SCALES, PYR_MAX_SCALE = 6, 8          # PFST_PYR_MAX_SCALES / PFST_PYR_MAX_SCALE
+_pyramid_tables = {}
+
+
+def check_pool_scales(scales):
+    """the scales the pyramid kernels take: one to six grids of 1 .. 8 cells per side"""
+    scales = tuple(int(s) for s in scales)
+    if not 1 <= len(scales) <= PYR_MAX_SCALES or any(not 1 <= s <= PYR_MAX_SCALE for s in scales):
+        raise NotImplementedError(f'pyramid kernels: 1 to {PYR_MAX_SCALES} scales of 1 .. {PYR_MAX_SCALE} cells per side, got {scales}')
+    return scales
+
+
+def pyramid_operator(kind, n, scales):
+    """The per-axis operator of the pyramid kernels for an axis of `n` pixels, on the host in fp64 (no device needed):
+    -> (D [sum(scales), n], span int32 [sum(scales), 2], tspan int32 [len(scales), n, 2]).  Rows off1[k] .. off1[k] + s_k of D belong to scale k.
+    kind 'pool':     row i of scale s is 1 / (b - a) on [a, b) = [floor(i n / s), ceil((i + 1) n / s)): nn.AdaptiveAvgPool2d(s) is Dh X Dw^T;
+    kind 'bilinear': D = A^T, A [n, s] the bilinear resize from s to n cells (align_corners=False, torch's
+                     area_pixel_compute_source_index: src = max(0, s / n (dst + 0.5) - 0.5)): F.interpolate is Dh^T G Dw.
+    span: the [begin, end) of each row's non-zeros; tspan[k, p]: the [begin, end) of the cells of scale k that pixel p touches."""
+    import numpy as np
+    scales = check_pool_scales(scales)
+    if kind not in ('pool', 'bilinear'):
+        raise ValueError(kind)
+    rows = []
+    for s in scales:
+        d = np.zeros((s, n), np.float64)
+        if kind == 'pool':
+            for i in range(s):
+                a, b = (i * n) // s, -((-(i + 1) * n) // s)
+                d[i, a:b] = 1.0 / (b - a)
+        else:
+            src = np.maximum(0.0, (s / n) * (np.arange(n, dtype=np.float64) + 0.5) - 0.5)
+            i0 = np.minimum(src.astype(np.int64), s - 1)
+            i1 = i0 + (i0 < s - 1)
+            l1 = src - i0
+            np.add.at(d, (i0, np.arange(n)), 1.0 - l1)
+            np.add.at(d, (i1, np.arange(n)), l1)
+        rows.append(d)
+    dense = np.concatenate(rows, 0)
+
+    def spans(m):            # per row of m: [first non-zero, last non-zero + 1); the non-zeros of a row are one run, possibly with exact zeros inside
+        nz = m != 0
+        some = nz.any(1)                      # (a grid finer than the plane it is resized to has cells that no pixel reads: an empty span)
+        lo = np.where(some, nz.argmax(1), 0)
+        hi = np.where(some, m.shape[1] - nz[:, ::-1].argmax(1), 0)
+        return np.stack([lo, hi], 1).astype(np.int32)
+    span = spans(dense)
+    tspan = np.stack([spans(d.T) for d in rows], 0)
+    return dense, span, tspan
+
+
+def _pyramid_dev_tables(kind, h, w, scales, dev):
+    key = (kind, h, w, scales, str(dev))
+    t = _pyramid_tables.get(key)
+    if t is None:
+        import numpy as np
+        if len(_pyramid_tables) >= 64:
+            _pyramid_tables.clear()
+        t = []
+        for axis, n in (('h', h), ('w', w)):
+            dense, span, tspan = pyramid_operator(kind, n, scales)
+            for name, arr in (('op', dense.astype(np.float32)), ('span', span), ('tspan', tspan)):
+                t.append(h2d_small(torch.from_numpy(np.ascontiguousarray(arr)), dev, ('pyramid', name, axis)))
+        t = _pyramid_tables[key] = tuple(t)           # (op_h, span_h, tspan_h, op_w, span_w, tspan_w)
+    return t
+
+
+def _pyr_ints(vals):
+    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+
+
+def _pyramid_reduce(kind, x, c, scales, chan_off, shared, out=None):
+    scales = check_pool_scales(scales)
+    n, _, h, w = x.shape
+    bs = _bs(x)
+    op_h, span_h, _, op_w, span_w, _ = _pyramid_dev_tables(kind, h, w, scales, x.device)
+    cells = n * c * sum(s * s for s in scales)
+    flat = torch.empty(cells, device=x.device) if out is None else _dense(out)
+    if flat.dim() != 1 or flat.numel() != cells:
+        raise ValueError(f'out must be a flat tensor of {cells} floats, got {tuple(flat.shape)}')
+    outs, o = [], 0
+    for s in scales:
+        outs.append(flat[o:o + n * c * s * s].view(n, c, s, s))
+        o += n * c * s * s
+    call('pfst_pyramid_reduce', x.data_ptr(), bs, n, c, h, w, len(scales), _pyr_ints(scales), _pyr_ints(chan_off), int(shared), op_h.data_ptr(),
+         op_w.data_ptr(), span_h.data_ptr(), span_w.data_ptr(), _ptr_array(outs), _stream())
+    return outs
+
+
+def _pyramid_expand(kind, grids, scales, chan_off, sliced, out, c, add, accumulate, amax):
+    scales = check_pool_scales(scales)
+    n, _, h, w = out.shape
+    if len(grids) != len(scales) or any(tuple(g.shape) != (n, c, s, s) for g, s in zip(grids, scales)):
+        raise ValueError(f'pyramid grids {[tuple(g.shape) for g in grids]} for scales {scales}, N = {n}, C = {c}')
+    _, _, tspan_h, _, _, tspan_w = t = _pyramid_dev_tables(kind, h, w, scales, out.device)
+    call('pfst_pyramid_expand', _ptr_array([_dense(g) for g in grids]), n, c, h, w, len(scales), _pyr_ints(scales), _pyr_ints(chan_off), int(sliced),
+         out.data_ptr(), _bs(out), _p(add), 0 if add is None else _bs(add), int(accumulate), t[0].data_ptr(), t[3].data_ptr(), tspan_h.data_ptr(),
+         tspan_w.data_ptr(), _p(amax), _stream())
+    return out
+
+
+def pyramid_pool(x, scales, out=None):
+    """[F.adaptive_avg_pool2d(x, s) for s in scales] in ONE launch that reads x once: -> list of dense [N, C, s, s] (views of one allocation,
+    or of the flat tensor `out` of N C sum(s^2) floats).  x may be a channel slice of a wider NCHW buffer."""
+    return _pyramid_reduce('pool', x, x.shape[1], scales, [0] * len(scales), True, out)
+
+
+def pyramid_pool_bwd(grads, scales, out, accumulate=False, add=None):
+    """the adjoint of pyramid_pool, all scales in one pass: out = (accumulate ? out : 0) + (add if given) + sum_k pool_k^T(grads[k]).
+    `add`: a tensor shaped like out (a slice of a concat gradient: the identity branch beside the pyramid) -- dL/dx is written once"""
+    if add is not None and tuple(add.shape) != tuple(out.shape):
+        raise ValueError(f'add {tuple(add.shape)} for out {tuple(out.shape)}')
+    return _pyramid_expand('pool', grads, scales, [0] * len(scales), False, out, out.shape[1], add, accumulate, None)
+
+
+def pyramid_upsample(grids, scales, out, amax=None):
+    """out[:, k C:(k + 1) C] = F.interpolate(grids[k], out.shape[2:], mode='bilinear', align_corners=False) for every k in one launch; out: a
+    [N, K C, H, W] dense-plane view (the pyramid's slices of the concat buffer).  amax: the slot group that receives max |out|"""
+    c = grids[0].shape[1]
+    if out.shape[1] != c * len(grids):
+        raise ValueError(f'{len(grids)} grids of {c} channels into {out.shape[1]} channels')
+    return _pyramid_expand('bilinear', grids, scales, [k * c for k in range(len(grids))], True, out, c, None, False, amax)
+
+
+def pyramid_upsample_bwd(dy, scales, out=None):
+    """the adjoint of pyramid_upsample: dy [N, K C, H, W] (dense planes) -> list of dense [N, C, s, s] (out: as for pyramid_pool), one launch"""
+    k = len(scales)
+    if dy.shape[1] % k:
+        raise ValueError(f'{dy.shape[1]} channels for {k} scales')
+    c = dy.shape[1] // k
+    return _pyramid_reduce('bilinear', dy, c, scales, [i * c for i in range(k)], False, out)
+
+
+def copy_planes(x, out, accumulate=False, amax=None):
+    """out[...] = (accumulate ? out : 0) + x between two dense-plane NCHW views of equal shape (a tensor into its slice of a concat buffer); amax: the slot group that
+    receives max |x|"""
+    if tuple(x.shape) != tuple(out.shape):
+        raise ValueError(f'copy_planes: {tuple(x.shape)} into {tuple(out.shape)}')
+    n, c, h, w = x.shape
+    call('pfst_copy_planes', x.data_ptr(), _bs(x), out.data_ptr(), _bs(out), n, c * h * w, int(accumulate), _p(amax), _stream())
+    return out
+
+
 def upsample_nearest(x, factor):
     _dense(x)
     n, c, h, w = x.shape

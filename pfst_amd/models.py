@@ -610,18 +610,163 @@ class DepthwiseSeparableASPPHead(BaseDecodeHead):
         tape.record(*bwd_pool)
 
 
+def _concat_var(x, channels, tape):
+    """an empty [N, channels, H, W] concat buffer over x's grid; under f16x3 with the slot group every writer of it publishes max |.| into"""
+    n, _, h, w = x.data.shape
+    cat = Var(torch.empty(n, channels, h, w, device=x.data.device), tape is not None)
+    if layers_mod.CONV_MATH == 'f16x3':
+        cat.amax = ops.amax_slots(x.data.device)
+    return cat
+
+
+def _identity_into(x, cat, c0, tape):
+    """x copied into channels [c0, c0 + C) of the concat `cat` (the reference's torch.cat([x, ...])); backward adds that slice of the
+    concat's gradient to dL/dx.  Recorded AFTER the layers that read x, so that in backward it runs before their data gradients and the
+    first of them still completes dL/dx"""
+    c1 = c0 + x.data.shape[1]
+    ops.copy_planes(x.data, cat.data[:, c0:c1], amax=cat.amax)
+    if tape is not None and x.requires_grad:
+        def bwd():
+            buf, acc = x.grad_target()
+            ops.copy_planes(cat.grad[:, c0:c1], buf, accumulate=acc)
+        tape.record(bwd)
+
+
+@HEADS.register_module()
+class ASPPHead(BaseDecodeHead):
+    """aspp_head.py (DeepLabV3): the image-pool branch and dense atrous branches -> concat -> 3x3 bottleneck -> cls_seg.  The concat, its shared
+    maximum and the deferred normalisation of its writers are those of DepthwiseSeparableASPPHead (a dense 3x3 branch on the Winograd path
+    writes its slice normalised: layers.norm_plan)"""
+
+    def __init__(self, dilations=(1, 6, 12, 18), **kwargs):
+        super().__init__(**kwargs)
+        assert isinstance(dilations, (list, tuple)) and all(isinstance(d, int) and d >= 1 for d in dilations)
+        self.dilations = tuple(dilations)
+        ci, ch = self.in_channels, self.channels
+        self.image_pool = nn.Sequential(nn.Identity(), ConvModule(ci, ch, 1))
+        self.aspp_modules = nn.ModuleList([ConvModule(ci, ch, 1 if d == 1 else 3, padding=0 if d == 1 else d, dilation=d) for d in dilations])
+        self.bottleneck = ConvModule((len(dilations) + 1) * ch, ch, 3, padding=1)
+
+    def forward(self, inputs, return_features=False, tape=None, training=True):
+        x = inputs[self.in_index]
+        n, _, h, w = x.data.shape
+        ch, nb = self.channels, len(self.dilations) + 1
+        cat = _concat_var(x, nb * ch, tape)
+        sl = layers_mod.folds_into_concat(self.bottleneck.conv, h, w, tape is not None)
+        if sl:
+            cat.coef_table = torch.empty(nb * ch, 4, device=x.data.device)
+            cat.coef_table[:ch] = layers_mod.identity_coef_row(x.data.device)
+        # the branches first, the image pool after them: in backward the pool's broadcast lands in dL/dx before the first branch's data
+        # gradient, which completes it (the order of DepthwiseSeparableASPPHead)
+        for i, m in enumerate(self.aspp_modules):
+            m(x, tape, out=cat.slice((i + 1) * ch, (i + 2) * ch), defer=sl)
+        pooled = Var(ops.global_avgpool(x.data), tape is not None)
+        pa = self.image_pool[1](pooled, tape)
+        ops.broadcast_hw(pa.data, cat.data[:, 0:ch], amax=cat.amax)
+        if tape is not None:
+            hw = float(h * w)
+
+            def bwd_pool():
+                pa._grad = ops.reduce_hw(cat.grad[:, 0:ch])
+
+            def bwd_gap():
+                buf, acc = x.grad_target()
+                if not acc:
+                    ops.fill_(buf, 0.0)
+                ops.broadcast_hw(pooled.grad, buf, 1.0 / hw, True)
+                pooled.free_grad()
+            DepthwiseSeparableASPPHead._reorder_pool(tape, (bwd_gap, dict(op='gap', name='decode_head.gap', x=x, out=pooled)),
+                                                     (bwd_pool, dict(op='broadcast', name='decode_head.image_pool.up', x=pa, out=cat.slice(0, ch))))
+        if sl:
+            cat.lazy = (cat.data, cat.coef_table, None)
+        feats = self.bottleneck(cat, tape)
+        # (the returned features are the PRE-dropout input of cls_seg, aspp_head.py:118-126: Dropout2d stays a pass of its own)
+        logits = self.cls_seg(feats, tape, training)
+        return (logits, feats) if return_features else logits
+
+
+@HEADS.register_module()
+class PSPHead(BaseDecodeHead):
+    """psp_head.py (PSPNet): [x, resize(ConvModule(AdaptiveAvgPool2d(s)(x))) for s in pool_scales] -> 3x3 bottleneck -> cls_seg.  The pyramid
+    is four launches of csrc/pyramid.hip whatever the number of scales: every pooled grid from one read of x, every
+    resize into its slice of the concat, and their adjoints; the 1x1 conv -> BN(train, over N s^2 samples) -> ReLU on the small grids are the
+    library's layers.  x is copied into its slice.  Returns the bottleneck output as the decoded features (a superset of the reference's
+    forward, which has no return_features: `use_decoded_feats` needs them)."""
+
+    def __init__(self, pool_scales=(1, 2, 3, 6), **kwargs):
+        super().__init__(**kwargs)
+        assert isinstance(pool_scales, (list, tuple))
+        self.pool_scales = ops.check_pool_scales(pool_scales)          # NotImplementedError beyond six scales of 1 .. 8
+        ci, ch = self.in_channels, self.channels
+        self.psp_modules = nn.ModuleList([nn.Sequential(nn.Identity(), ConvModule(ci, ch, 1)) for _ in self.pool_scales])
+        self.bottleneck = ConvModule(ci + len(self.pool_scales) * ch, ch, 3, padding=1)
+
+    def forward(self, inputs, return_features=False, tape=None, training=True):
+        x = inputs[self.in_index]
+        ci, ch, scales = self.in_channels, self.channels, self.pool_scales
+        cat = _concat_var(x, ci + len(scales) * ch, tape)
+        x.claim_first_use()              # dL/dx is completed by the pyramid's adjoint below, which fuses nothing
+        ops.copy_planes(x.data, cat.data[:, 0:ci], amax=cat.amax)
+        pooled = [Var(p, tape is not None) for p in ops.pyramid_pool(x.data, scales)]
+        if tape is not None:
+            # recorded before the small layers, so it runs after them: dL/dx = the identity slice's gradient + the adjoint of every pooling,
+            # written once
+            def bwd_pool():
+                buf, acc = x.grad_target()
+                ops.pyramid_pool_bwd([p.grad for p in pooled], scales, buf, accumulate=acc, add=cat.grad[:, 0:ci])
+                for p in pooled:
+                    p.free_grad()
+            tape.record(bwd_pool)
+        outs = [self.psp_modules[k][1](pooled[k], tape) for k in range(len(scales))]
+        ops.pyramid_upsample([o.data for o in outs], scales, cat.data[:, ci:], amax=cat.amax)
+        if tape is not None:
+            def bwd_up():
+                for o, g in zip(outs, ops.pyramid_upsample_bwd(cat.grad[:, ci:], scales)):
+                    o._grad = g
+            tape.record(bwd_up)
+        feats = self.bottleneck(cat, tape)
+        logits = self.cls_seg(feats, tape, training)
+        return (logits, feats) if return_features else logits
+
+
 @HEADS.register_module()
 class FCNHead(BaseDecodeHead):
+    """fcn_head.py: num_convs conv -> BN -> ReLU layers (kernel 1 or 3, any dilation), optionally conv_cat over [x, feats]"""
+
     def __init__(self, num_convs=2, kernel_size=3, concat_input=True, dilation=1, **kwargs):
         super().__init__(**kwargs)
-        if num_convs != 1 or concat_input or kernel_size != 3:
-            raise NotImplementedError('FCNHead: the PFST auxiliary head (num_convs=1, concat_input=False) only')
-        self.convs = nn.Sequential(ConvModule(self.in_channels, self.channels, 3, padding=dilation, dilation=dilation))
+        if not (isinstance(num_convs, int) and num_convs >= 0 and isinstance(dilation, int) and dilation > 0):
+            raise ValueError(f'FCNHead: num_convs >= 0 and dilation >= 1, got {num_convs!r}, {dilation!r}')
+        if kernel_size not in (1, 3):
+            raise NotImplementedError(f'FCNHead: kernel_size 1 or 3, got {kernel_size!r}')
+        if num_convs == 0 and self.in_channels != self.channels:
+            raise ValueError(f'FCNHead: num_convs=0 needs in_channels == channels, got {self.in_channels} and {self.channels}')
+        self.num_convs, self.concat_input, self.kernel_size = num_convs, bool(concat_input), kernel_size
+        pad = (kernel_size // 2) * dilation
+        convs = [ConvModule(self.in_channels if i == 0 else self.channels, self.channels, kernel_size, padding=pad, dilation=dilation)
+                 for i in range(num_convs)]
+        self.convs = nn.Sequential(*convs) if convs else nn.Identity()
+        if self.concat_input:
+            self.conv_cat = ConvModule(self.in_channels + self.channels, self.channels, kernel_size, padding=kernel_size // 2)
 
     def forward(self, inputs, return_features=False, tape=None, training=True):
         # (the features this head returns are the PRE-dropout ones, fcn_head.py:92-98, so its Dropout2d stays a pass of its own -- an eighth
         # of the decode head's tensor; the decode head returns the ASPP bottleneck output and folds its dropout, see above)
-        feats = self.convs[0](inputs[self.in_index], tape)
+        x = inputs[self.in_index]
+        if self.num_convs == 1 and not self.concat_input:
+            feats = self.convs[0](x, tape)
+        else:
+            ci, ch = self.in_channels, self.channels
+            cat = _concat_var(x, ci + ch, tape) if self.concat_input else None
+            feats = x
+            for i in range(self.num_convs):
+                last = cat is not None and i == self.num_convs - 1
+                feats = self.convs[i](feats, tape, out=cat.slice(ci, ci + ch) if last else None)
+            if cat is not None:
+                if self.num_convs == 0:
+                    _identity_into(x, cat, ci, tape)
+                _identity_into(x, cat, 0, tape)
+                feats = self.conv_cat(cat, tape)
         logits = self.cls_seg(feats, tape, training)
         return (logits, feats) if return_features else logits
 

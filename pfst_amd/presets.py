@@ -24,6 +24,26 @@ def model_cfg(num_classes=6, in_channels=3, dropout=0.1):
         train_cfg=dict(), test_cfg=dict(mode='whole'))
 
 
+BASELINE_KINDS = ('pspnet', 'deeplabv3', 'fcn')
+
+
+def baseline_model_cfg(kind, num_classes, in_channels, depth=50, dropout=0.1):
+    """The comparison models of the reference (configs/_base_/models/pspnet_r50-d8.py, deeplabv3_r50-d8.py, fcn_r50-d8.py): the same
+    ResNetV1c-d8 backbone and auxiliary FCN head on layer3 as model_cfg, under a PSPHead, an ASPPHead or a two-layer FCNHead with
+    concat_input.  Plain BN, as the reference's DeepLabV3+ file; `depth` 50 or 101 (the reference's PSPNet file runs 101).  The class
+    weights of the reference's two-class PSPNet edit are a property of its data set: add `class_weight` to the loss dicts where wanted."""
+    if kind not in BASELINE_KINDS:
+        raise ValueError(f'baseline_model_cfg: kind must be one of {BASELINE_KINDS}, got {kind!r}')
+    cfg = model_cfg(num_classes, in_channels, dropout)
+    cfg['backbone']['depth'] = depth
+    common = dict(in_channels=2048, in_index=3, channels=512, dropout_ratio=dropout, num_classes=num_classes, norm_cfg=dict(NORM_CFG),
+                  align_corners=False, loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0))
+    head = dict(pspnet=dict(type='PSPHead', pool_scales=(1, 2, 3, 6)), deeplabv3=dict(type='ASPPHead', dilations=(1, 12, 24, 36)),
+                fcn=dict(type='FCNHead', num_convs=2, concat_input=True))[kind]
+    cfg['decode_head'] = dict(head, **common)
+    return cfg
+
+
 def uda_cfg(num_classes=6, in_channels=3, dropout=0.1, blur=True, color_jitter_probability=0.2, downscale=0.5,
             pseudo_threshold=0.98, max_iters=40000):
     return dict(

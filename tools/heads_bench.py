@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""Times the four pyramid operations of PSPHead (csrc/pyramid.hip) at the flagship tile's shape -- N = 8, a 128 x 128 grid,
+scales (1, 2, 3, 6), 2048 channels pooled and 512 channels per scale resized -- beside (a) the same operations composed from torch's own
+device ops in the same process (four adaptive_avg_pool2d; four interpolate + cat; their autograd backward, the graph built outside the
+timed region), (b) the resize halves through the library's generic pfst_resize_bilinear / _bwd, one launch per scale, and (c) the bytes each
+launch must move at the measured copy rate.  Variants alternate inside every round; per variant the median, minimum and maximum over the
+rounds of the mean of --inner back-to-back runs between two device events.  Then a supervised step (EncoderDecoder.train_step under SGD) of
+the three comparison models and the flagship at 8 x 1024^2, alternating blocks, host clock between device synchronisations.  One JSON line
+(and --out FILE).
+
+  python tools/heads_bench.py [--tiles 8] [--grid 128] [--rounds 7] [--inner 5] [--steps 12] [--no-step] [--no-ops] [--out FILE]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+COPY_TB_S = 6.29          # the device-to-device copy rate measured on the MI355X (read + write bytes per second)
+SCALES = (1, 2, 3, 6)
+
+
+def alternate(variants, rounds, inner):
+    """variants: {name: fn}.  -> {name: dict(median_ms, min_ms, max_ms)} of the per-round mean over `inner` runs; the order flips every round"""
+    import torch
+    for fn in variants.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    names = list(variants)
+    for r in range(rounds):
+        for k in (names if r % 2 == 0 else names[::-1]):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(inner):
+                variants[k]()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b) / inner)
+    return {k: dict(median_ms=round(statistics.median(v), 4), min_ms=round(min(v), 4), max_ms=round(max(v), 4)) for k, v in ms.items()}
+
+
+def verdict(r, ours, others, moved_bytes):
+    """ours beats another variant when its slowest round is faster than the other's fastest"""
+    r['bytes_MB'] = round(moved_bytes / 1e6, 1)
+    r['floor_ms_at_copy_rate'] = round(moved_bytes / (COPY_TB_S * 1e12) * 1e3, 4)
+    r['fraction_of_copy_rate'] = round(r['floor_ms_at_copy_rate'] / r[ours]['median_ms'], 3)
+    for o in others:
+        r[f'{o}_over_{ours}'] = round(r[o]['median_ms'] / r[ours]['median_ms'], 2)
+        r[f'beats_{o}_beyond_spread'] = r[ours]['max_ms'] < r[o]['min_ms']
+    return r
+
+
+def ops_bench(args):
+    import torch
+    import torch.nn.functional as F
+    from pfst_amd import hip_ops as ops
+    N, G, K = args.tiles, args.grid, len(SCALES)
+    CI, CH = 2048, 512
+    torch.manual_seed(0)
+    cells = sum(s * s for s in SCALES)
+    x = torch.randn(N, CI, G, G, device='cuda')
+    res = dict(tiles=N, grid=G, scales=list(SCALES), rounds=args.rounds, inner=args.inner)
+    plane_in, plane_up = 4 * N * CI * G * G, 4 * N * K * CH * G * G
+
+    # ---- pooling forward: x read once; torch: four passes
+    res['pool'] = verdict(alternate(dict(pyramid=lambda: ops.pyramid_pool(x, SCALES),
+                                         torch=lambda: [F.adaptive_avg_pool2d(x, s) for s in SCALES]), args.rounds, args.inner),
+                          'pyramid', ['torch'], plane_in + 4 * N * CI * cells)
+    # ---- pooling backward: dL/dx written once; torch: autograd over the four pools (four passes + three accumulations)
+    gs = [torch.randn(N, CI, s, s, device='cuda') for s in SCALES]
+    xr = x.detach().requires_grad_(True)
+    pooled = [F.adaptive_avg_pool2d(xr, s) for s in SCALES]
+    dx = torch.empty_like(x)
+    res['pool_bwd'] = verdict(alternate(dict(pyramid=lambda: ops.pyramid_pool_bwd(gs, SCALES, dx),
+                                             torch=lambda: torch.autograd.grad(pooled, xr, gs, retain_graph=True)), args.rounds, args.inner),
+                              'pyramid', ['torch'], plane_in + 4 * N * CI * cells)
+    del pooled, xr, dx, gs
+    # ---- resize forward into the concat slices
+    grids = [torch.randn(N, CH, s, s, device='cuda').relu_() for s in SCALES]
+    cat = torch.empty(N, CI + K * CH, G, G, device='cuda')
+    up = cat[:, CI:]
+    dense = torch.empty(N, K * CH, G, G, device='cuda')
+
+    def generic_up():
+        for k, gk in enumerate(grids):
+            ops.resize_bilinear(gk, (G, G), out=up[:, k * CH:(k + 1) * CH])
+    res['upsample'] = verdict(alternate(dict(pyramid=lambda: ops.pyramid_upsample(grids, SCALES, up),
+                                             torch=lambda: torch.cat([F.interpolate(gk, (G, G), mode='bilinear', align_corners=False) for gk in grids], 1, out=dense),
+                                             generic=generic_up), args.rounds, args.inner),
+                              'pyramid', ['torch', 'generic'], plane_up + 4 * N * CH * cells)
+    # ---- resize backward out of the concat gradient
+    dcat = torch.randn(N, CI + K * CH, G, G, device='cuda')
+    dy = dcat[:, CI:]
+    gr = [gk.detach().requires_grad_(True) for gk in grids]
+    ups = torch.cat([F.interpolate(gk, (G, G), mode='bilinear', align_corners=False) for gk in gr], 1)
+    dyd = dy.contiguous()
+
+    def generic_up_bwd():
+        return [ops.resize_bilinear_bwd(dy[:, k * CH:(k + 1) * CH], (s, s)) for k, s in enumerate(SCALES)]
+    res['upsample_bwd'] = verdict(alternate(dict(pyramid=lambda: ops.pyramid_upsample_bwd(dy, SCALES),
+                                                 torch=lambda: torch.autograd.grad(ups, gr, dyd, retain_graph=True), generic=generic_up_bwd),
+                                            args.rounds, args.inner),
+                                  'pyramid', ['torch', 'generic'], plane_up + 4 * N * CH * cells)
+    return res
+
+
+def step_bench(args):
+    import torch
+    from pfst_amd.optim import build_optimizer
+    from pfst_amd.presets import SGD_OPTIMIZER, baseline_model_cfg, model_cfg
+    from pfst_amd.registry import build_segmentor
+    from pfst_amd.synthetic import synth_batch
+    batch = synth_batch(args.tiles, args.size, 6, 3, seed=1234, device='cuda')
+    batch = {k: v for k, v in batch.items() if not k.startswith('target_')}
+    cfgs = dict(deeplabv3plus=model_cfg(6, 3), pspnet=baseline_model_cfg('pspnet', 6, 3), deeplabv3=baseline_model_cfg('deeplabv3', 6, 3),
+                fcn=baseline_model_cfg('fcn', 6, 3))
+    times = {k: [] for k in cfgs}
+    blocks, per_block = 3, -(-args.steps // 3)
+    # one model resident at a time (activations of an 8 x 1024^2 step are tens of GB): blocks of one kind run back to back, kinds in turn
+    for blk in range(blocks):
+        for kind in (list(cfgs) if blk % 2 == 0 else list(cfgs)[::-1]):
+            torch.manual_seed(0)
+            model = build_segmentor(cfgs[kind])
+            model.init_weights()
+            model.cuda()
+            opt = build_optimizer(model, dict(SGD_OPTIMIZER, lr=6e-5))
+            for _ in range(2):
+                model.train_step(batch, opt)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(per_block):
+                model.train_step(batch, opt)
+            torch.cuda.synchronize()
+            times[kind].append(1000.0 * (time.perf_counter() - t0) / per_block)
+            del model, opt
+    out = dict(tiles=args.tiles, size=args.size, steps_per_block=per_block, blocks=blocks)
+    for kind, v in times.items():
+        out[kind] = dict(median_ms_per_step=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2))
+    return out
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--tiles', type=int, default=8)
+    p.add_argument('--grid', type=int, default=128)
+    p.add_argument('--size', type=int, default=1024)
+    p.add_argument('--rounds', type=int, default=7)
+    p.add_argument('--inner', type=int, default=5)
+    p.add_argument('--steps', type=int, default=12, help='timed supervised steps per model')
+    p.add_argument('--no-step', action='store_true')
+    p.add_argument('--no-ops', action='store_true')
+    p.add_argument('--out', default=None)
+    args = p.parse_args(argv)
+    import torch
+    import pfst_amd  # noqa: F401
+    res = dict(device=torch.cuda.get_device_name(0))
+    if not args.no_ops:
+        res['ops'] = ops_bench(args)
+        torch.cuda.empty_cache()
+    if not args.no_step:
+        res['supervised_step'] = step_bench(args)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+    return res
+
+
+if __name__ == '__main__':
+    main()

@@ -12,7 +12,8 @@ Supervised training (source-only / target-only baselines, a source-trained start
 builds a bare EncoderDecoder (registry.build_train_model) whose own train_step runs; `cfg.data.train` is then a plain dataset dict
 (type / data_root / img_dir / ann_dir / pipeline) and the optimizer usually the SGD of configs/_base_/schedules/schedule_*.py.
 `--supervised` drops the `uda` section of a config or preset (a UDADataset in data.train is replaced by its `source` entry; a preset takes
-schedule_40k's SGD + poly schedule).  Checkpoints of such a run have bare keys: tools/test.py reads them without key revision, and
+schedule_40k's SGD + poly schedule); `--supervised --model pspnet|deeplabv3|fcn` swaps in the reference's comparison models (PSPNet,
+DeepLabV3, FCN: presets.baseline_model_cfg) on the same backbone, `--synthetic` included.  Checkpoints of such a run have bare keys: tools/test.py reads them without key revision, and
 `--init-student-from CKPT` starts a self-training run (a `uda` config) with them in both the student and the EMA teacher."""
 import argparse
 import os
@@ -29,6 +30,9 @@ def parse_args(argv=None):
     p.add_argument('--init-student-from', help='a bare-keyed segmentor checkpoint (backbone.* / decode_head.* / auxiliary_head.*, e.g. of a '
                                                'supervised run) loaded into the student AND the EMA teacher of a `uda` config; every key must match')
     p.add_argument('--supervised', action='store_true', help='drop the `uda` section: train the bare segmentor on img / gt_semantic_seg')
+    p.add_argument('--model', choices=['pspnet', 'deeplabv3', 'fcn'],
+                   help='with --supervised: replace cfg.model by the comparison model of that name (presets.baseline_model_cfg: PSPHead / ASPPHead / '
+                        'two-layer FCNHead on the same backbone and auxiliary head), keeping num_classes, in_channels and the backbone depth')
     p.add_argument('--resume-from')
     p.add_argument('--no-validate', action='store_true')
     g = p.add_mutually_exclusive_group()
@@ -79,6 +83,18 @@ def load_cfg(args):
         raise FileNotFoundError(args.config)
     if args.cfg_options:
         cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
+    if args.model:
+        if not args.supervised:
+            raise ValueError('--model builds a comparison model for supervised training: pass --supervised (self-training over these heads takes '
+                             'a config whose PFGSTLoss has downscale=None, README)')
+        from pfst_amd.presets import baseline_model_cfg
+        old = cfg.model
+        new = baseline_model_cfg(args.model, old['decode_head']['num_classes'], old['backbone'].get('in_channels', 3),
+                                 depth=old['backbone'].get('depth', 50), dropout=old['decode_head'].get('dropout_ratio', 0.1))
+        new['pretrained'] = old.get('pretrained')
+        cfg.model = new
+        if args.cfg_options:                                  # options addressed at the new model's keys apply to it
+            cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
     if args.max_iters:
         cfg.runner['max_iters'] = args.max_iters
     if args.supervised:
