@@ -1,5 +1,6 @@
-// The four-tap source of one full-resolution pixel of a bilinear resize (align_corners=False) and its blend: shared by the fused
-// up-sampling loss kernels (loss.hip, dice_loss.hip) so that both interpolate a pixel's logits with the same arithmetic, bit for bit.
+// The four-tap source of one full-resolution pixel of a bilinear resize (align_corners=False) and its blend: shared by every kernel that
+// interpolates a pixel's logits in registers -- the fused up-sampling losses (loss.hip, dice_loss.hip, sigmoid_loss.hip through
+// upsample_walk.h), entropy_labels.hip and ohem.hip -- so that all of them use the same arithmetic, bit for bit.
 #pragma once
 #include "common.h"
 

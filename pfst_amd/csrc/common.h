@@ -73,12 +73,37 @@ static inline int ew_grid(i64 n, int block = 256) {
   return (int)g;
 }
 
+// grid size for a grid-stride kernel of four pixels per thread and pass
+static inline int px_blocks(i64 n) {
+  i64 g = (n + 1023) / 1024;
+  if (g > 4096) g = 4096;
+  return g < 1 ? 1 : (int)g;
+}
+
+// The x4 / x8 inter-cell block forms of the fused up-sampling losses (upsample_walk.h), ONE rule for loss.hip, dice_loss.hip and
+// sigmoid_loss.hip: ratio S = 4 / 8 exactly, C <= 8 (the classes live in registers), the label 2-byte and `pairs` -- the addresses of what
+// the family reads or writes in pixel pairs (lse, pixel weights; null counts as aligned), or-ed -- 8-byte aligned, and a grid whose y fits:
+// `rows` low-resolution rows per workgroup row (15 owned cells; 16 blocks in the CE forward, whose two tiles the bound does not count).
+static inline bool blocks_form_ok(int S, int C, int h, int w, int H, int W, const void* label, uintptr_t pairs, int rows = 15) {
+  return (S == 4 || S == 8) && C <= 8 && H == S * h && W == S * w && (pairs & 7) == 0 && ((uintptr_t)label & 1) == 0 && h < 65535 * rows;
+}
+// forward: tiles of 16 x 16 blocks, b = -1 ... w - 1; two tiles per workgroup at x4, one at x8 (64 pixels per thread)
+static inline dim3 fwd_blocks_grid(int S, int h, int w, int N) { return dim3(cdiv(w + 1, 16), cdiv(h + 1, S == 4 ? 32 : 16), N); }
+// backward: a workgroup owns 15 x 15 cells
+static inline dim3 bwd_blocks_grid(int h, int w, int N) { return dim3(cdiv(w, 15), cdiv(h, 15), N); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 __device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -136,6 +161,15 @@ __device__ __forceinline__ void bilin_src(int dst, float scale, int in_size, int
   i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
   l1 = __fsub_rn(s, (float)i0);
   l0 = __fsub_rn(1.f, l1);
+}
+// The adjoint of that resize as a gather: the output pixels whose taps can reach input pixel (iy, ix) lie in [oy_lo, oy_hi] x [ox_lo, ox_hi]
+// (a superset by one pixel each way; the caller keeps a pixel by its tap weight from bilin_src, so the margin costs tests, never terms).
+__device__ __forceinline__ void bilin_footprint(int iy, int ix, float sh, float sw, int Ho, int Wo, int& oy_lo, int& oy_hi, int& ox_lo,
+                                                int& ox_hi) {
+  oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
+  ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
+  oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, Ho - 1);
+  ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, Wo - 1);
 }
 // scale / shift of the normalisation, ONE definition for bn_apply, bn_backward and the fused data-gradient epilogue: the ReLU gate
 // recomputed in backward must be bit-identical to the forward decision, so the roundings are pinned

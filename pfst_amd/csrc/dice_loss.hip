@@ -12,16 +12,10 @@
 #include <limits.h>
 #include <algorithm>
 #include "common.h"
-#include "bilin.h"
+#include "upsample_walk.h"
 #include "../../include/pfst_hip.h"
 
 namespace {
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // three block-wide sums at once; results valid in thread 0.  smem: 12 doubles.
 __device__ __forceinline__ void block_sum3_d(double& a, double& b, double& c, double* smem) {
@@ -138,9 +132,63 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(const float* __restrict__
   }
 }
 
-// The x4 / x8 cases (H == S h, W == S w, C <= 8) by inter-cell blocks, as ce_fwd_blocks_kernel: one thread per S x S block of
-// full-resolution pixels that interpolate from the same four cells, whose 4 x C logits are loaded once.  Per pixel the arithmetic is
-// ce_fwd_blocks_kernel's (same coordinates, weights, class order): the same lse bits, whether formed here or read.
+// What the Dice forward does with a pixel of fwd_blocks_walk (upsample_walk.h): the log-sum-exp, read or formed -- with ce_fwd_kernel's
+// arithmetic on the frame's logits, so the same bits either way -- and stored in pairs, the pixel's terms of I, P, T and the head's accuracy
+// counts.  The sums are the kernel's own arrays: a functor that is indexed by a loop variable would stay in memory until that loop is unrolled.
+template <bool E2>
+struct DiceFwdPx {
+  const float* __restrict__ li;
+  float* __restrict__ ls;
+  int C, ign, hign;
+  float expo;
+  double (&I)[8], (&P)[8];
+  int (&T)[8];
+  int correct, valid, bad;
+  float2 e2, lo;
+  __device__ __forceinline__ void pair(i64 p) {
+    e2 = make_float2(0.f, 0.f);
+    if (li) e2 = *reinterpret_cast<const float2*>(li + p);
+  }
+  __device__ __forceinline__ void pixel(int k, int l, const float (&zc)[8], float mx, int arg) {
+    float e = k ? e2.y : e2.x;
+    if (!li) {
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        if (c < C) se += expf(zc[c] - mx);
+      e = mx + logf(se);
+    }
+    lo.x = k ? lo.x : e;
+    lo.y = k ? e : lo.y;
+    const int tl = min(l, C - 1);
+    const bool ok = l != ign;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        const float x = zc[c] - e, pc = expf(x);
+        const bool hit = c == tl;
+        T[c] += hit ? 1 : 0;
+        I[c] += (double)(hit && ok ? pc : 0.f);
+        P[c] += (double)pow_e<E2>(pc, x, expo);
+      }
+    }
+    // the head's accuracy and label check, as ce_fwd_kernel counts them (hign: the HEAD's ignore_index); on copies that are stored back
+    // unconditionally, since updates of the members under the branches would be merged into one store through a selected address
+    int co = correct, va = valid, ba = bad;
+    if (l != hign && l < C) {
+      va += 1;
+      if (arg == l) co += 1;
+    } else if (l != hign && l != ign) {
+      ba += 1;
+    }
+    correct = co; valid = va; bad = ba;
+  }
+  __device__ __forceinline__ void pair_end(i64 p) {
+    if (ls) *reinterpret_cast<float2*>(ls + p) = lo;
+  }
+};
+
+// The x4 / x8 cases (H == S h, W == S w, C <= 8) by inter-cell blocks.
 // grid: (ceil((w + 1) / 16), ceil((h + 1) / (16 TILES)), N), 16 x 16 threads
 template <int S, int TILES, bool E2>
 __global__ __launch_bounds__(256) void dice_fwd_blocks_kernel(const float* __restrict__ logits, int C, int h, int w,
@@ -149,98 +197,14 @@ __global__ __launch_bounds__(256) void dice_fwd_blocks_kernel(const float* __res
                                                               double* __restrict__ slab, long long* __restrict__ cnt) {
   __shared__ double smd[4][16];
   __shared__ int smi[4][12];
-  const int n = blockIdx.z, H = S * h, W = S * w, hw = h * w;
-  const int bx = blockIdx.x * 16 + (threadIdx.x & 15) - 1;
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* li = lse_in ? lse_in + (i64)n * H * W : nullptr;
-  float* ls = lse_in ? nullptr : lse_out + (i64)n * H * W;
+  const i64 n = blockIdx.z, HW = (i64)S * h * S * w;
   double I[8], P[8];
   int T[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) { I[c] = 0.0; P[c] = 0.0; T[c] = 0; }
-  int correct = 0, valid = 0, bad = 0;
-  for (int it = 0; it < TILES; ++it) {
-    const int by = (blockIdx.y * TILES + it) * 16 + (threadIdx.x >> 4) - 1;
-    if (bx > w - 1 || by > h - 1) continue;
-    const int xl = max(bx, 0), xr = min(xl + 1, w - 1), yt = max(by, 0), yb = min(yt + 1, h - 1);
-    float v[2][2][8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float* q = lp + (i64)(c < C ? c : 0) * hw;
-      v[0][0][c] = q[yt * w + xl];
-      v[0][1][c] = q[yt * w + xr];
-      v[1][0][c] = q[yb * w + xl];
-      v[1][1][c] = q[yb * w + xr];
-    }
-    float lx0[S], lx1[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      const int ox = S * bx + S / 2 + j;
-      int x0, x1;
-      lx0[j] = lx1[j] = 0.f;
-      if (ox >= 0 && ox < W) bilin_src(ox, 1.f / S, w, x0, x1, lx0[j], lx1[j]);
-    }
-#pragma unroll
-    for (int r = 0; r < S; ++r) {
-      const int oy = S * by + S / 2 + r;
-      if (oy < 0 || oy >= H) continue;
-      int y0, y1;
-      float ly0, ly1;
-      bilin_src(oy, 1.f / S, h, y0, y1, ly0, ly1);
-#pragma unroll
-      for (int half = 0; half < S / 2; ++half) {
-        const int ox = S * bx + S / 2 + 2 * half;                  // pixel pairs are inside the image together (W = S w, ox even)
-        if (ox < 0 || ox >= W) continue;
-        const i64 p = (i64)oy * W + ox;
-        const unsigned short l2 = *reinterpret_cast<const unsigned short*>(lab + p);
-        float2 e2 = make_float2(0.f, 0.f);
-        if (li) e2 = *reinterpret_cast<const float2*>(li + p);
-        float lo[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int j = 2 * half + k;
-          const int l = k ? (l2 >> 8) : (l2 & 255);
-          float mx = -INFINITY;
-          int arg = 0;
-          float zc[8];
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            zc[c] = c < C ? bilin_blend(v[0][0][c], v[0][1][c], v[1][0][c], v[1][1][c], lx0[j], lx1[j], ly0, ly1) : -INFINITY;
-            if (c < C && zc[c] > mx) { mx = zc[c]; arg = c; }
-          }
-          float e = k ? e2.y : e2.x;
-          if (!li) {
-            float se = 0.f;
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-              if (c < C) se += expf(zc[c] - mx);
-            e = mx + logf(se);
-          }
-          lo[k] = e;
-          const int tl = min(l, C - 1);
-          const bool ok = l != ign;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            if (c < C) {
-              const float x = zc[c] - e, pc = expf(x);
-              const bool hit = c == tl;
-              T[c] += hit ? 1 : 0;
-              I[c] += (double)(hit && ok ? pc : 0.f);
-              P[c] += (double)pow_e<E2>(pc, x, expo);
-            }
-          }
-          if (l != hign && l < C) {
-            valid += 1;
-            if (arg == l) correct += 1;
-          } else if (l != hign && l != ign) {
-            bad += 1;
-          }
-        }
-        if (ls) *reinterpret_cast<float2*>(ls + p) = make_float2(lo[0], lo[1]);
-      }
-    }
-  }
+  DiceFwdPx<E2> px{lse_in ? lse_in + n * HW : nullptr, lse_in ? nullptr : lse_out + n * HW, C, ign, hign, expo, I, P, T, 0, 0, 0};
+  fwd_blocks_walk<S, TILES>(logits + n * C * h * w, C, h, w, label + n * HW, px);
+  int correct = px.correct, valid = px.valid, bad = px.bad;
   // one row of partials per workgroup: lanes by shuffles, the four waves through LDS in wave order
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
@@ -363,256 +327,114 @@ __global__ __launch_bounds__(256) void dice_s_kernel(const float* __restrict__ l
   }
 }
 
-// grid: (blocks over h*w, C, N).  One thread per low-resolution logit; gathers its full-res footprint (ce_bwd_kernel's gather).
+// The Dice gradient's term of one class for bwd_class_gather (upsample_walk.h): p_c (g_c - s) with s = sum_k g_k p_k from dice_s_kernel.
+// No pixel is skipped (an ignored pixel still carries the b p^(e-1) term) and the tap weights have no multiplier.
+template <bool E2>
+struct DiceClassPx {
+  const float* __restrict__ ls;
+  const float* __restrict__ sp;
+  int C, ign, c;
+  float e1, ca, cb;
+  float d;
+  __device__ __forceinline__ bool cell_skip(int, int) const { return false; }
+  template <class Z>
+  __device__ __forceinline__ float cell_weight(int p, int l, const Z& z) {
+    const float x = z(0) - ls[p], pc = expf(x);
+    d = pc * (dice_g<E2>(pc, x, ca, cb, l != ign && min(l, C - 1) == c, e1) - sp[p]);
+    return 1.f;
+  }
+  template <class Z>
+  __device__ __forceinline__ float term(int, const Z&) const { return d; }
+};
+
+// grid: (blocks over h*w, C, N).  One thread per low-resolution logit; gathers its full-res footprint.
 template <bool E2>
 __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__ logits, int C, int h, int w, const unsigned char* __restrict__ label,
                                                        int H, int W, int ign, float sh, float sw, float e1, const float* __restrict__ lse,
                                                        const float* __restrict__ coef, const float* __restrict__ s_in, float scale,
                                                        float* __restrict__ dlogits, int accumulate) {
-  const int c = blockIdx.y, n = blockIdx.z;
-  const float* lp = logits + ((i64)n * C + c) * h * w;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* ls = lse + (i64)n * H * W;
-  const float* sp = s_in + (i64)n * H * W;
-  const float ca = coef[((i64)n * C + c) * 2], cb = coef[((i64)n * C + c) * 2 + 1];
-  float* dp = dlogits + ((i64)n * C + c) * h * w;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h * w; i += gridDim.x * blockDim.x) {
-    const int iy = i / w, ix = i - iy * w;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, H - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, W - 1);
-    float acc = 0.f;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float ly0, ly1;
-      bilin_src(oy, sh, h, y0, y1, ly0, ly1);
-      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        Bilin b;
-        b.y0 = y0; b.y1 = y1; b.ly0 = ly0; b.ly1 = ly1;
-        bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-        const float wx = (b.x0 == ix ? b.lx0 : 0.f) + (b.x1 == ix ? b.lx1 : 0.f);
-        if (wx == 0.f) continue;
-        const int p = oy * W + ox;
-        const int l = lab[p];
-        const float x = interp(lp, w, b) - ls[p], pc = expf(x);
-        const float g = dice_g<E2>(pc, x, ca, cb, l != ign && min(l, C - 1) == c, e1);
-        acc = fmaf(wy * wx, pc * (g - sp[p]), acc);
+  const int c = blockIdx.y;
+  const i64 n = blockIdx.z, HW = (i64)H * W, nc = n * C + c, plane = nc * h * w;
+  DiceClassPx<E2> px{lse + n * HW, s_in + n * HW, C, ign, c, e1, coef[nc * 2], coef[nc * 2 + 1]};
+  bwd_class_gather(logits + plane, h, w, label + n * HW, H, W, sh, sw, scale, dlogits + plane, accumulate, px);
+}
+
+// The Dice gradient's terms of all classes (C <= 8) for bwd_blocks_walk and bwd_cells_gather: a pixel's soft-max, its g and
+// s = sum_k g_k p_k are formed once, in registers (the kernel's own arrays, as in DiceFwdPx); the term of class c is p_c (g_c - s).
+// No pixel is skipped and the tap weights have no multiplier.
+template <bool E2>
+struct DiceBwdPx {
+  const float* __restrict__ ls;
+  int C, ign;
+  float e1;
+  const float (&ca)[8], (&cb)[8];
+  float (&pc)[8], (&g)[8];
+  float2 ls2;
+  float s;
+  __device__ __forceinline__ void pair(i64 p) { ls2 = *reinterpret_cast<const float2*>(ls + p); }
+  template <class Z>
+  __device__ __forceinline__ void softmax(int l, float lsp, const Z& z) {
+    const int tl = min(l, C - 1);
+    const bool ok = l != ign;
+    s = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {               // pc, g beyond C stay unset: term() is asked for c < C only
+        const float x = z(c) - lsp;
+        pc[c] = expf(x);
+        g[c] = dice_g<E2>(pc[c], x, ca[c], cb[c], ok && c == tl, e1);
+        s = fmaf(g[c], pc[c], s);
       }
     }
-    acc *= scale;
-    dp[i] = accumulate ? dp[i] + acc : acc;
+  }
+  __device__ __forceinline__ bool skip(int, int) const { return false; }
+  __device__ __forceinline__ bool cell_skip(int, int) const { return false; }
+  template <class Z>
+  __device__ __forceinline__ float weight(int k, int l, const Z& z) {
+    softmax(l, k ? ls2.y : ls2.x, z);
+    return 1.f;
+  }
+  template <class Z>
+  __device__ __forceinline__ float cell_weight(int p, int l, const Z& z) {
+    softmax(l, ls[p], z);
+    return 1.f;
+  }
+  template <class Z>
+  __device__ __forceinline__ float term(int c, const Z&) const { return pc[c] * (g[c] - s); }
+};
+// an image's (a, b) of pfst_dice_finalize's table, by class
+__device__ __forceinline__ void dice_coef(const float* __restrict__ coef, i64 n, int C, float (&ca)[8], float (&cb)[8]) {
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    ca[c] = c < C ? coef[(n * C + c) * 2] : 0.f;
+    cb[c] = c < C ? coef[(n * C + c) * 2 + 1] : 0.f;
   }
 }
 
-// The same gather with ONE thread per low-resolution cell for all classes (C <= 8), as ce_bwd_cells_kernel: a pixel's soft-max, its g and
-// s = sum_k g_k p_k stay in registers.                                                                    grid: (blocks over h*w, 1, N)
+// ONE thread per low-resolution cell for all classes (C <= 8).                                          grid: (blocks over h*w, 1, N)
 template <bool E2>
 __global__ __launch_bounds__(256) void dice_bwd_cells_kernel(const float* __restrict__ logits, int C, int h, int w,
                                                              const unsigned char* __restrict__ label, int H, int W, int ign, float sh, float sw,
                                                              float e1, const float* __restrict__ lse, const float* __restrict__ coef,
                                                              float scale, float* __restrict__ dlogits, int accumulate) {
-  const int n = blockIdx.z;
-  const int hw = h * w;
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* ls = lse + (i64)n * H * W;
-  float* dp = dlogits + (i64)n * C * hw;
-  float ca[8], cb[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    ca[c] = c < C ? coef[((i64)n * C + c) * 2] : 0.f;
-    cb[c] = c < C ? coef[((i64)n * C + c) * 2 + 1] : 0.f;
-  }
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
-    const int iy = i / w, ix = i - iy * w;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, H - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, W - 1);
-    float acc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] = 0.f;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float ly0, ly1;
-      bilin_src(oy, sh, h, y0, y1, ly0, ly1);
-      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        Bilin b;
-        b.y0 = y0; b.y1 = y1; b.ly0 = ly0; b.ly1 = ly1;
-        bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-        const float wx = (b.x0 == ix ? b.lx0 : 0.f) + (b.x1 == ix ? b.lx1 : 0.f);
-        if (wx == 0.f) continue;
-        const int p = oy * W + ox;
-        const int l = lab[p];
-        const int tl = min(l, C - 1);
-        const bool ok = l != ign;
-        const float wg = wy * wx, lsp = ls[p];
-        float pc[8], g[8], s = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          pc[c] = g[c] = 0.f;
-          if (c < C) {
-            const float x = interp(lp + (i64)c * hw, w, b) - lsp;
-            pc[c] = expf(x);
-            g[c] = dice_g<E2>(pc[c], x, ca[c], cb[c], ok && c == tl, e1);
-            s = fmaf(g[c], pc[c], s);
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-          if (c < C) acc[c] = fmaf(wg, pc[c] * (g[c] - s), acc[c]);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c < C) {
-        const float a = acc[c] * scale;
-        dp[(i64)c * hw + i] = accumulate ? dp[(i64)c * hw + i] + a : a;
-      }
-    }
-  }
+  const i64 n = blockIdx.z, HW = (i64)H * W, img = n * C * h * w;
+  float ca[8], cb[8], pc[8], g[8];
+  dice_coef(coef, n, C, ca, cb);
+  DiceBwdPx<E2> px{lse + n * HW, C, ign, e1, ca, cb, pc, g};
+  bwd_cells_gather(logits + img, C, h, w, label + n * HW, H, W, sh, sw, scale, dlogits + img, accumulate, px);
 }
 
-// The x4 / x8 cases by inter-cell blocks, ce_bwd_blocks_kernel's scheme: one thread loads the 4 x C corner logits of its S x S block once,
-// evaluates each pixel's soft-max, g and s once and keeps the 4 x C corner sums in registers; the corner sums of a 16 x 16 tile of blocks
-// meet in LDS in four conflict-free phases and the 15 x 15 cells whose four blocks lie inside the workgroup are written out.  No pixel is
-// skipped: an ignored pixel still carries the b p^(e-1) term.                                    grid: (ceil(w / 15), ceil(h / 15), N)
+// The x4 / x8 cases by inter-cell blocks.                                                        grid: (ceil(w / 15), ceil(h / 15), N)
 template <int S, bool E2>
 __global__ __launch_bounds__(256) void dice_bwd_blocks_kernel(const float* __restrict__ logits, int C, int h, int w,
                                                               const unsigned char* __restrict__ label, int ign, float e1,
                                                               const float* __restrict__ lse, const float* __restrict__ coef, float scale,
                                                               float* __restrict__ dlogits, int accumulate) {
-  constexpr int TB = 16, OWN = TB - 1;
-  __shared__ float cell[8][TB + 1][TB + 1];
-  const int n = blockIdx.z, H = S * h, W = S * w, hw = h * w;
-  const int tx = threadIdx.x & (TB - 1), ty = threadIdx.x >> 4;
-  const int cx0 = blockIdx.x * OWN, cy0 = blockIdx.y * OWN;        // first cell this workgroup owns
-  const int bx = cx0 - 1 + tx, by = cy0 - 1 + ty;                  // this thread's block: taps (b, b + 1), clamped at the borders
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* ls = lse + (i64)n * H * W;
-  for (int i = threadIdx.x; i < 8 * (TB + 1) * (TB + 1); i += 256) (&cell[0][0][0])[i] = 0.f;
-  float ca[8], cb[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    ca[c] = c < C ? coef[((i64)n * C + c) * 2] : 0.f;
-    cb[c] = c < C ? coef[((i64)n * C + c) * 2 + 1] : 0.f;
-  }
-  float acc[2][2][8];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int c = 0; c < 8; ++c) acc[a][b][c] = 0.f;
-  if (bx <= w - 1 && by <= h - 1) {
-    const int xl = max(bx, 0), xr = min(xl + 1, w - 1), yt = max(by, 0), yb = min(yt + 1, h - 1);
-    float v[2][2][8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float* q = lp + (i64)(c < C ? c : 0) * hw;
-      v[0][0][c] = q[yt * w + xl];
-      v[0][1][c] = q[yt * w + xr];
-      v[1][0][c] = q[yb * w + xl];
-      v[1][1][c] = q[yb * w + xr];
-    }
-    float lx0[S], lx1[S], wxl[S], wxr[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      const int ox = S * bx + S / 2 + j;
-      int x0 = 0, x1 = 0;
-      lx0[j] = lx1[j] = 0.f;
-      if (ox >= 0 && ox < W) bilin_src(ox, 1.f / S, w, x0, x1, lx0[j], lx1[j]);
-      wxl[j] = (x0 == bx ? lx0[j] : 0.f) + (x1 == bx ? lx1[j] : 0.f);
-      wxr[j] = (x0 == bx + 1 ? lx0[j] : 0.f) + (x1 == bx + 1 ? lx1[j] : 0.f);
-    }
-#pragma unroll
-    for (int r = 0; r < S; ++r) {
-      const int oy = S * by + S / 2 + r;
-      if (oy < 0 || oy >= H) continue;
-      int y0, y1;
-      float ly0, ly1;
-      bilin_src(oy, 1.f / S, h, y0, y1, ly0, ly1);
-      const float wyt = (y0 == by ? ly0 : 0.f) + (y1 == by ? ly1 : 0.f);
-      const float wyb = (y0 == by + 1 ? ly0 : 0.f) + (y1 == by + 1 ? ly1 : 0.f);
-#pragma unroll
-      for (int half = 0; half < S / 2; ++half) {
-        const int ox = S * bx + S / 2 + 2 * half;                  // pixel pairs are inside the image together (W = S w, ox even)
-        if (ox < 0 || ox >= W) continue;
-        const i64 p = (i64)oy * W + ox;
-        const unsigned short l2 = *reinterpret_cast<const unsigned short*>(lab + p);
-        const float2 ls2 = *reinterpret_cast<const float2*>(ls + p);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int j = 2 * half + k;
-          const int l = k ? (l2 >> 8) : (l2 & 255);
-          const int tl = min(l, C - 1);
-          const bool ok = l != ign;
-          const float lsp = k ? ls2.y : ls2.x;
-          const float wtl = wyt * wxl[j], wtr = wyt * wxr[j], wbl = wyb * wxl[j], wbr = wyb * wxr[j];
-          float pc[8], g[8], s = 0.f;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            pc[c] = g[c] = 0.f;
-            if (c < C) {
-              const float z = bilin_blend(v[0][0][c], v[0][1][c], v[1][0][c], v[1][1][c], lx0[j], lx1[j], ly0, ly1);
-              pc[c] = expf(z - lsp);
-              g[c] = dice_g<E2>(pc[c], z - lsp, ca[c], cb[c], ok && c == tl, e1);
-              s = fmaf(g[c], pc[c], s);
-            }
-          }
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            if (c < C) {
-              const float d = pc[c] * (g[c] - s);
-              acc[0][0][c] = fmaf(wtl, d, acc[0][0][c]);
-              acc[0][1][c] = fmaf(wtr, d, acc[0][1][c]);
-              acc[1][0][c] = fmaf(wbl, d, acc[1][0][c]);
-              acc[1][1][c] = fmaf(wbr, d, acc[1][1][c]);
-            }
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        if (c < C) cell[c][ty + a][tx + b] += acc[a][b][c];
-      __syncthreads();
-    }
-  }
-  float* dp = dlogits + (i64)n * C * hw;
-  for (int i = threadIdx.x; i < OWN * OWN; i += 256) {
-    const int u = i / OWN, q = i - u * OWN;
-    const int gy = cy0 + u, gx = cx0 + q;
-    if (gy >= h || gx >= w) continue;
-    for (int c = 0; c < C; ++c) {
-      const float a = cell[c][u + 1][q + 1] * scale;
-      float* o = dp + (i64)c * hw + gy * w + gx;
-      *o = accumulate ? *o + a : a;
-    }
-  }
-}
-
-inline int px_blocks(i64 n) {
-  i64 g = (n + 1023) / 1024;
-  if (g > 4096) g = 4096;
-  return g < 1 ? 1 : (int)g;
-}
-
-// form: 0 = the generic kernels, 4 / 8 = the inter-cell block kernels of that ratio (the caller chooses, the library checks)
-inline bool form_ok(int form, int C, int h, int w, int H, int W, const void* lse, const void* label) {
-  if (form == 0) return true;
-  return (form == 4 || form == 8) && C <= 8 && H == form * h && W == form * w && ((uintptr_t)lse & 7) == 0 && ((uintptr_t)label & 1) == 0 &&
-         h < 65535 * 15;
+  const i64 n = blockIdx.z, HW = (i64)S * h * S * w, img = n * C * h * w;
+  float ca[8], cb[8], pc[8], g[8];
+  dice_coef(coef, n, C, ca, cb);
+  DiceBwdPx<E2> px{lse + n * HW, C, ign, e1, ca, cb, pc, g};
+  bwd_blocks_walk<S>(logits + img, C, h, w, label + n * HW, scale, dlogits + img, accumulate, px);
 }
 
 }  // namespace
@@ -623,7 +445,7 @@ extern "C" int pfst_dice_upsample_fwd(const float* logits, int N, int C, int h, 
   PFST_CHECK_ARG(logits && label && slab && counts && N > 0 && C > 0 && C <= 255 && h > 0 && w > 0 && H > 0 && W > 0 && N <= 65535);
   PFST_CHECK_ARG((lse_in != nullptr) != (lse_out != nullptr) && exponent >= 1.f && (i64)H * W < INT_MAX - 2048);
   const void* lse = lse_in ? (const void*)lse_in : (const void*)lse_out;
-  PFST_CHECK_ARG(form_ok(form, C, h, w, H, W, lse, label));
+  PFST_CHECK_ARG(form == 0 || blocks_form_ok(form, C, h, w, H, W, label, (uintptr_t)lse));
   hipStream_t s = (hipStream_t)stream;
   const bool e2 = exponent == 2.f;
   if (form == 0) {
@@ -637,10 +459,8 @@ extern "C" int pfst_dice_upsample_fwd(const float* logits, int N, int C, int h, 
       hipLaunchKernelGGL(dice_fwd_kernel<false>, dim3(gx, N), dim3(256), 0, s, logits, C, h, w, label, H, W, ignore_index, head_ignore_index, sh,
                          sw, exponent, lse_in, lse_out, slab, counts);
   } else {
-    // tiles per workgroup as pfst_ce_upsample_fwd: two at x4, one at x8 (64 pixels per thread)
-    const int gx = cdiv(w + 1, 16), gy = cdiv(h + 1, form == 4 ? 32 : 16);
-    PFST_CHECK_ARG(blocks == gx * gy);
-    const dim3 grid(gx, gy, N);
+    const dim3 grid = fwd_blocks_grid(form, h, w, N);
+    PFST_CHECK_ARG(blocks == (int)(grid.x * grid.y));
 #define PFST_DICE_FWD(S, TILES, E2)                                                                                                         \
   hipLaunchKernelGGL((dice_fwd_blocks_kernel<S, TILES, E2>), grid, dim3(256), 0, s, logits, C, h, w, label, ignore_index, head_ignore_index, \
                      exponent, lse_in, lse_out, slab, counts)
@@ -668,13 +488,13 @@ extern "C" int pfst_dice_upsample_bwd(const float* logits, int N, int C, int h, 
                                       int ignore_index, float exponent, int form, const float* lse, const float* coef, float scale,
                                       float* work, float* dlogits, int accumulate, pfst_stream_t stream) {
   PFST_CHECK_ARG(logits && label && lse && coef && dlogits && N > 0 && C > 0 && C <= 255 && h > 0 && w > 0 && H > 0 && W > 0 && N <= 65535);
-  PFST_CHECK_ARG(exponent >= 1.f && (i64)H * W < INT_MAX - 2048 && form_ok(form, C, h, w, H, W, lse, label) && (form != 0 || C <= 8 || work));
+  PFST_CHECK_ARG(exponent >= 1.f && (i64)H * W < INT_MAX - 2048 && (form == 0 || blocks_form_ok(form, C, h, w, H, W, label, (uintptr_t)lse)) && (form != 0 || C <= 8 || work));
   hipStream_t s = (hipStream_t)stream;
   const bool e2 = exponent == 2.f;
   const float e1 = exponent - 1.f, sh = (float)h / (float)H, sw = (float)w / (float)W;
   const int gx = cdiv((i64)h * w, 256);
   if (form != 0) {
-    const dim3 grid(cdiv(w, 15), cdiv(h, 15), N);
+    const dim3 grid = bwd_blocks_grid(h, w, N);
 #define PFST_DICE_BWD(S, E2)                                                                                                          \
   hipLaunchKernelGGL((dice_bwd_blocks_kernel<S, E2>), grid, dim3(256), 0, s, logits, C, h, w, label, ignore_index, e1, lse, coef, scale, \
                      dlogits, accumulate)

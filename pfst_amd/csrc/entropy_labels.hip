@@ -162,12 +162,6 @@ __global__ __launch_bounds__(256) void entropy_label_kernel(const float* __restr
   }
 }
 
-inline int px_blocks(i64 n) {
-  i64 g = (n + 1023) / 1024;
-  if (g > 4096) g = 4096;
-  return g < 1 ? 1 : (int)g;
-}
-
 inline bool shape_ok(const void* logits, int N, int C, int h, int w, int H, int W) {
   return logits && N > 0 && N <= 65535 && C > 0 && C <= 255 && h > 0 && w > 0 && H > 0 && W > 0 && (i64)H * W < INT_MAX - 2048 * 4096 &&
          (i64)h * w * C < INT_MAX;

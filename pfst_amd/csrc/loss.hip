@@ -8,7 +8,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "common.h"
-#include "bilin.h"
+#include "upsample_walk.h"
 #include "../../include/pfst_hip.h"
 
 namespace {
@@ -79,6 +79,9 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
 // inter-cell blocks, as ce_bwd_blocks_kernel below: one thread per S x S block of full-resolution
 // pixels that interpolate from the same four cells -- their 4 x C logits are loaded once instead of once per pixel.  Per pixel the arithmetic
 // is the one above (same coordinates and weights from bilin_src, same class order): bit-identical lse, the same loss terms.
+// This kernel keeps its own text of the walk that dice_loss.hip and sigmoid_loss.hip take from fwd_blocks_walk (keep the two in step: the
+// lse and the arg-max are theirs too).  Built from the frame, the compiler keeps every column's horizontal blends across the rows of a block,
+// as it does for those two families anyway, and the x8 kernel goes from 89 to 171 VGPRs, 5 to 2 waves / SIMD (profiles/loss_walk_refactor.txt).
 // Two tiles of 16 x 16 blocks per workgroup: every workgroup ends in four block sums and three fp64 atomics on one cache line; measured at
 // 8 x 1024^2: one tile 122 us, two 97, four 109 (too few workgroups), 1024-thread workgroups of four tiles 113 (profiles/r05_small_kernels.txt).
 // grid: (ceil((w + 1) / 16), ceil((h + 1) / 32), N), 16 x 16 threads
@@ -177,120 +180,57 @@ __global__ __launch_bounds__(256) void ce_fwd_blocks_kernel(const float* __restr
   }
 }
 
+// What the CE gradient reads per pixel and its terms for the gather frames of upsample_walk.h: d_c = softmax_c - [c == label] from the
+// forward's log-sum-exp, weighted by pixel weight x class weight; an ignored or out-of-range label adds nothing.
+struct CeBwdPx {
+  const float* __restrict__ ls;
+  const float* __restrict__ pwp;
+  const float* __restrict__ cw;
+  int C, ignore;
+  int c0;                        // the class that the frame calls 0: the launch row's in bwd_class_gather, else 0
+  int l;                         // the current pixel's label and log-sum-exp
+  float lsp;
+  __device__ __forceinline__ bool cell_skip(int, int l_) const { return l_ == ignore || l_ >= C; }
+  template <class Z>
+  __device__ __forceinline__ float cell_weight(int p, int l_, const Z&) {
+    float g = pwp ? pwp[p] : 1.f;
+    if (cw) g *= cw[l_];
+    l = l_;
+    lsp = ls[p];
+    return g;
+  }
+  template <class Z>
+  __device__ __forceinline__ float term(int k, const Z& z) const { return expf(z(k) - lsp) - (l == c0 + k ? 1.f : 0.f); }
+};
+
 // grid: (blocks over h*w, C, N).  One thread per low-resolution logit; gathers its full-res footprint.
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, int C, int h, int w,
                                                      const unsigned char* __restrict__ label, const float* __restrict__ pw,
                                                      const float* __restrict__ cw, int H, int W, int ignore, float sh, float sw,
                                                      const float* __restrict__ lse, float scale, float* __restrict__ dlogits,
                                                      int accumulate) {
-  const int c = blockIdx.y, n = blockIdx.z;
-  const float* lp = logits + ((i64)n * C + c) * h * w;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* ls = lse + (i64)n * H * W;
-  const float* pwp = pw ? pw + (i64)n * H * W : nullptr;
-  float* dp = dlogits + ((i64)n * C + c) * h * w;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h * w; i += gridDim.x * blockDim.x) {
-    const int iy = i / w, ix = i - iy * w;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, H - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, W - 1);
-    float acc = 0.f;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float ly0, ly1;
-      bilin_src(oy, sh, h, y0, y1, ly0, ly1);
-      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        Bilin b;
-        b.y0 = y0; b.y1 = y1; b.ly0 = ly0; b.ly1 = ly1;
-        bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-        const float wx = (b.x0 == ix ? b.lx0 : 0.f) + (b.x1 == ix ? b.lx1 : 0.f);
-        if (wx == 0.f) continue;
-        const int p = oy * W + ox;
-        const int l = lab[p];
-        if (l == ignore || l >= C) continue;
-        float g = pwp ? pwp[p] : 1.f;
-        if (cw) g *= cw[l];
-        const float prob = expf(interp(lp, w, b) - ls[p]);
-        acc = fmaf(wy * wx * g, prob - (l == c ? 1.f : 0.f), acc);
-      }
-    }
-    acc *= scale;
-    dp[i] = accumulate ? dp[i] + acc : acc;
-  }
+  const int c = blockIdx.y;
+  const i64 n = blockIdx.z, HW = (i64)H * W, plane = (n * C + c) * h * w;
+  CeBwdPx px{lse + n * HW, pw ? pw + n * HW : nullptr, cw, C, ignore, c};
+  bwd_class_gather(logits + plane, h, w, label + n * HW, H, W, sh, sw, scale, dlogits + plane, accumulate, px);
 }
 
-// The same gather with ONE thread per low-resolution cell for all classes (C <= 8): the per-pixel work that does not depend on the class --
-// source coordinates and weights, label, log-sum-exp, pixel weight -- is done once instead of C times, the C accumulators live in
-// registers.  Per class the terms and their order are those of ce_bwd_kernel: bit-identical gradients.       grid: (blocks over h*w, 1, N)
+// ONE thread per low-resolution cell for all classes (C <= 8).                                          grid: (blocks over h*w, 1, N)
 __global__ __launch_bounds__(256) void ce_bwd_cells_kernel(const float* __restrict__ logits, int C, int h, int w,
                                                            const unsigned char* __restrict__ label, const float* __restrict__ pw,
                                                            const float* __restrict__ cw, int H, int W, int ignore, float sh, float sw,
                                                            const float* __restrict__ lse, float scale, float* __restrict__ dlogits,
                                                            int accumulate) {
-  const int n = blockIdx.z;
-  const int hw = h * w;
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* ls = lse + (i64)n * H * W;
-  const float* pwp = pw ? pw + (i64)n * H * W : nullptr;
-  float* dp = dlogits + (i64)n * C * hw;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
-    const int iy = i / w, ix = i - iy * w;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, H - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, W - 1);
-    float acc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] = 0.f;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float ly0, ly1;
-      bilin_src(oy, sh, h, y0, y1, ly0, ly1);
-      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        Bilin b;
-        b.y0 = y0; b.y1 = y1; b.ly0 = ly0; b.ly1 = ly1;
-        bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-        const float wx = (b.x0 == ix ? b.lx0 : 0.f) + (b.x1 == ix ? b.lx1 : 0.f);
-        if (wx == 0.f) continue;
-        const int p = oy * W + ox;
-        const int l = lab[p];
-        if (l == ignore || l >= C) continue;
-        float g = pwp ? pwp[p] : 1.f;
-        if (cw) g *= cw[l];
-        const float wg = wy * wx * g, lsp = ls[p];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          if (c < C) {
-            const float prob = expf(interp(lp + (i64)c * hw, w, b) - lsp);
-            acc[c] = fmaf(wg, prob - (l == c ? 1.f : 0.f), acc[c]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c < C) {
-        const float a = acc[c] * scale;
-        dp[(i64)c * hw + i] = accumulate ? dp[(i64)c * hw + i] + a : a;
-      }
-    }
-  }
+  const i64 n = blockIdx.z, HW = (i64)H * W, img = n * C * h * w;
+  CeBwdPx px{lse + n * HW, pw ? pw + n * HW : nullptr, cw, C, ignore, 0};
+  bwd_cells_gather(logits + img, C, h, w, label + n * HW, H, W, sh, sw, scale, dlogits + img, accumulate, px);
 }
 
-// The x4 / x8 cases of the same gradient (H == S h, W == S w: the decode head's logits at 1/4, the auxiliary head's at 1/8 resolution; C <= 8)
-// by INTER-CELL BLOCKS instead of cells.  The S x S full-resolution pixels between four neighbouring cell centres -- pixels S b + S/2 ...
-// S b + 3S/2 - 1 of block b in each direction (4b+2 ... 4b+5 at S = 4),
-// b = -1 ... w-1 (the outermost blocks are the half-width borders whose taps are clamped) -- all interpolate from the same four cells:
-// one thread loads those 4 x C logits ONCE, evaluates each pixel's softmax once (the per-cell gather above evaluates every pixel in each
-// of the up to four cells it touches: 4x the exponentials, 16x the logit loads), and keeps the 4 x C corner sums in registers.  A
-// workgroup is 16 x 16 blocks; the corner sums meet in LDS in four conflict-free phases (in a phase every thread adds to a different
-// cell), and the 15 x 15 cells whose four blocks all lie inside the workgroup are written out -- neighbouring workgroups overlap by one
-// block row / column.  Per pixel and tap the term is the one of ce_bwd_cells_kernel (same source coordinates, weights, interpolation and
-// fma); the ORDER of a cell's <= 64 terms differs (block by block instead of raster order), deterministically.
+// The x4 / x8 cases of the same gradient by inter-cell blocks: bwd_blocks_walk's scheme (upsample_walk.h, where it is described), on this
+// kernel's own text -- keep the two in step.  Built from the frame with the CeBwdPx functor the x4 kernel is unchanged (108 VGPRs, the same
+// instruction mix, 67 us at 8 x 6 x 256^2) but the x8 kernel, at the same 206 VGPRs, comes out 1.3 % slower (101.9 -> 103.4 us at
+// 8 x 6 x 128^2 over four alternated runs each, profiles/loss_walk_refactor.txt): the frame is optimised once on its own and once more
+// inside the kernel, and the x8 body then keeps fewer of its class-count branches.
 // grid: (ceil(w / 15), ceil(h / 15), N)
 template <int S>
 __global__ __launch_bounds__(256) void ce_bwd_blocks_kernel(const float* __restrict__ logits, int C, int h, int w,
@@ -516,10 +456,10 @@ __global__ void ce_finalize_kernel(const double* __restrict__ acc, double numel,
   out[2] = (float)acc[3];
 }
 
-inline int px_blocks(i64 n) {
-  i64 g = (n + 1023) / 1024;
-  if (g > 4096) g = 4096;
-  return g < 1 ? 1 : (int)g;
+// the x4 / x8 form of a CE launch (the library picks the route itself): 4, 8, or 0 = the generic kernels
+inline int ce_form(int C, int h, int w, int H, int W, const void* label, const float* lse, const float* pw, int rows) {
+  const uintptr_t pairs = (uintptr_t)lse | (uintptr_t)pw;
+  return blocks_form_ok(4, C, h, w, H, W, label, pairs, rows) ? 4 : blocks_form_ok(8, C, h, w, H, W, label, pairs, rows) ? 8 : 0;
 }
 
 }  // namespace
@@ -530,12 +470,12 @@ extern "C" int pfst_ce_upsample_fwd(const float* logits, int N, int C, int h, in
   // 16 pixels per thread: every workgroup ends in three same-address fp64 atomics, and 8192 workgroups of four pixels per thread spent
   // half of the launch in that tail (profiles/r05_small_kernels.txt: 322 -> 149 us at 8 x 1024^2)
   const int gx = (int)std::max<i64>(1, std::min<i64>(4096, ((i64)H * W + 4095) / 4096));
-  const bool blocks_ok = C <= 8 && (((uintptr_t)lse | (uintptr_t)pix_weight) & 7) == 0 && ((uintptr_t)label & 1) == 0 && h < 65535 * 16;
-  if (blocks_ok && H == 4 * h && W == 4 * w)
-    hipLaunchKernelGGL((ce_fwd_blocks_kernel<4, 2>), dim3(cdiv(w + 1, 16), cdiv(h + 1, 32), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w,
+  const int form = ce_form(C, h, w, H, W, label, lse, pix_weight, 16);
+  if (form == 4)
+    hipLaunchKernelGGL((ce_fwd_blocks_kernel<4, 2>), fwd_blocks_grid(4, h, w, N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w,
                        label, pix_weight, class_weight, ignore_index, lse, acc);
-  else if (blocks_ok && H == 8 * h && W == 8 * w)        // the auxiliary head's logits at 1/8 resolution: 64 pixels per thread, one tile per workgroup
-    hipLaunchKernelGGL((ce_fwd_blocks_kernel<8, 1>), dim3(cdiv(w + 1, 16), cdiv(h + 1, 16), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w,
+  else if (form == 8)        // the auxiliary head's logits at 1/8 resolution: 64 pixels per thread, one tile per workgroup
+    hipLaunchKernelGGL((ce_fwd_blocks_kernel<8, 1>), fwd_blocks_grid(8, h, w, N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w,
                        label, pix_weight, class_weight, ignore_index, lse, acc);
   else
     hipLaunchKernelGGL(ce_fwd_kernel, dim3(gx, N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, label,
@@ -549,12 +489,12 @@ extern "C" int pfst_ce_upsample_bwd(const float* logits, int N, int C, int h, in
                                     float* dlogits, int accumulate, pfst_stream_t stream) {
   PFST_CHECK_ARG(logits && label && lse && dlogits && N > 0 && C > 0 && C <= 255 && h > 0 && w > 0 && H > 0 && W > 0 && N <= 65535);
   int gx = cdiv((i64)h * w, 256);
-  const bool blocks_ok = C <= 8 && (((uintptr_t)lse | (uintptr_t)pix_weight) & 7) == 0 && ((uintptr_t)label & 1) == 0 && h < 65535 * 15;
-  if (blocks_ok && H == 4 * h && W == 4 * w)
-    hipLaunchKernelGGL(ce_bwd_blocks_kernel<4>, dim3(cdiv(w, 15), cdiv(h, 15), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, label,
+  const int form = ce_form(C, h, w, H, W, label, lse, pix_weight, 15);
+  if (form == 4)
+    hipLaunchKernelGGL(ce_bwd_blocks_kernel<4>, bwd_blocks_grid(h, w, N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, label,
                        pix_weight, class_weight, ignore_index, lse, scale, dlogits, accumulate);
-  else if (blocks_ok && H == 8 * h && W == 8 * w)
-    hipLaunchKernelGGL(ce_bwd_blocks_kernel<8>, dim3(cdiv(w, 15), cdiv(h, 15), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, label,
+  else if (form == 8)
+    hipLaunchKernelGGL(ce_bwd_blocks_kernel<8>, bwd_blocks_grid(h, w, N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, label,
                        pix_weight, class_weight, ignore_index, lse, scale, dlogits, accumulate);
   else if (C <= 8)     // one thread per low-resolution cell, all classes in registers; more classes: one launch row per class
     hipLaunchKernelGGL(ce_bwd_cells_kernel, dim3(gx, 1, N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, label, pix_weight,

@@ -338,12 +338,6 @@ __global__ __launch_bounds__(256) void ohem_weight_kernel(float* __restrict__ ke
   if (threadIdx.x == 0 && kept) atomicAdd(reinterpret_cast<u64*>(&info[2]), (u64)kept);
 }
 
-inline int px_blocks(i64 n) {
-  i64 g = (n + 1023) / 1024;
-  if (g > 4096) g = 4096;
-  return g < 1 ? 1 : (int)g;
-}
-
 }  // namespace
 
 extern "C" int pfst_ohem_workspace_bytes(int N, int H, int W, long long* bytes) {

@@ -1010,7 +1010,7 @@ inline int sps_blocks(i64 hw, int N) {
   return g < 1 ? 1 : (int)g;
 }
 
-inline int px_blocks(i64 n) {
+inline int px_blocks256(i64 n) {
   i64 g = (n + 255) / 256;
   if (g > 4096) g = 4096;
   return g < 1 ? 1 : (int)g;
@@ -1039,7 +1039,7 @@ void launch_sim_map_k(const float* feat, int N, int C, int H, int W, int dil, in
 template <int K>
 void launch_sim_map_bwd_k(const float* feat, const float* sim, const float* norm, const float* gsim, int N, int C, int H, int W, int dil,
                           int gauss, float inv_sigma2, int cc, float* dfeat, int accumulate, float* coef, hipStream_t s) {
-  const dim3 gp(px_blocks((i64)H * W), N);
+  const dim3 gp(px_blocks256((i64)H * W), N);
   if (gauss) hipLaunchKernelGGL((sim_bwd_coef_kernel<K, true>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, inv_sigma2, coef);
   else hipLaunchKernelGGL((sim_bwd_coef_kernel<K, false>), gp, dim3(256), 0, s, sim, norm, gsim, H, W, dil, 0.f, coef);
   const int hal = (K / 2) * dil, la = kt_edge(hal) * kt_edge(hal);
@@ -1056,7 +1056,7 @@ extern "C" int pfst_sim_map(const float* feat, int N, int C, int H, int W, int d
                             pfst_stream_t stream) {
   PFST_CHECK_ARG(feat && sim && norm && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
   PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
-  const dim3 grid(px_blocks((i64)H * W), N);
+  const dim3 grid(px_blocks256((i64)H * W), N);
   if (sim_type == 0 && simq_ok(feat, sim, C, H, W, dil) && (reinterpret_cast<uintptr_t>(norm) & 15) == 0) {
     const dim3 gq((unsigned)(((i64)H * W) / 256), N);
     const size_t lds = 4 * SIMQ_VALS * 64 * sizeof(float);
@@ -1079,7 +1079,7 @@ extern "C" int pfst_sim_map_bwd(const float* feat, const float* sim, const float
                                 int sim_type, float sigma, float* dfeat, int accumulate, float* coef_ws, pfst_stream_t stream) {
   PFST_CHECK_ARG(feat && sim && norm && gsim && dfeat && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1);
   PFST_CHECK_ARG(sim_type == 0 || (sim_type == 1 && sigma > 0.f));
-  const dim3 grid(px_blocks((i64)H * W), N);
+  const dim3 grid(px_blocks256((i64)H * W), N);
   if (sim_type == 0 && coef_ws && simq_ok(feat, dfeat, C, H, W, dil) && (reinterpret_cast<uintptr_t>(coef_ws) & 15) == 0) {
     PFST_CHECK_ARG(coef_ws != nullptr);
     hipLaunchKernelGGL((sim_bwd_coef_kernel<3, false>), grid, dim3(256), 0, (hipStream_t)stream, sim, norm, gsim, H, W, dil, 0.f, coef_ws);
@@ -1134,7 +1134,7 @@ extern "C" int pfst_src_sim_stats(const float* sim, const unsigned char* gt, int
   PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(stats, 0, 6 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  const int gxs = px_blocks((i64)H * W);
+  const int gxs = px_blocks256((i64)H * W);
   double* det = nullptr;
   if (pfst_deterministic()) {
     det = static_cast<double*>(pfst_det_scratch((size_t)gxs * N * 6 * sizeof(double), s));
@@ -1153,7 +1153,7 @@ extern "C" int pfst_src_sim_grad(const float* sim, const unsigned char* gt, int 
   PFST_CHECK_ARG(sim && gt && stats && gsim && losses && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 &&
                  ksize_ok(ksize));
   PFST_CHECK_ARG(loss_type >= 0 && loss_type <= 2);
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_grad_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, sim,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_grad_kernel<K_>, dim3(px_blocks256((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, sim,
                                               gt, H, W, Hg, Wg, dil, loss_type, margin_pos, margin_neg, stats, w_pos, w_neg, w_pos_std,
                                               w_neg_std, gsim, losses, reinterpret_cast<const SrcSel*>(select)));
   PFST_CHECK_LAUNCH();
@@ -1171,7 +1171,7 @@ extern "C" int pfst_src_sim_select(const float* sim, const unsigned char* gt, in
   unsigned int* hist = reinterpret_cast<unsigned int*>(st + 2);
   for (int pass = 0; pass < 4; ++pass) {
     if (pass == 0) hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, 2);
-    PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_sel_hist_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, sim, gt, H, W,
+    PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(src_sel_hist_kernel<K_>, dim3(px_blocks256((i64)H * W), N), dim3(256), 0, s, sim, gt, H, W,
                                                 Hg, Wg, dil, st, hist));
     hipLaunchKernelGGL(src_sel_scan_kernel, dim3(1), dim3(256), 0, s, st, hist, src_perc, pass == 0 ? 1 : 0);
   }
@@ -1182,7 +1182,7 @@ extern "C" int pfst_src_sim_select(const float* sim, const unsigned char* gt, in
 extern "C" int pfst_softmax_down(const float* logits, int N, int C, int h, int w, int ds, float* prob, int H, int W, pfst_stream_t stream) {
   PFST_CHECK_ARG(logits && prob && N > 0 && N <= 65535 && C > 0 && h > 0 && w > 0 && ds >= 1 && H > 0 && W > 0);
   PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
-  hipLaunchKernelGGL(softmax_down_kernel, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, ds, prob, H, W);
+  hipLaunchKernelGGL(softmax_down_kernel, dim3(px_blocks256((i64)H * W), N), dim3(256), 0, (hipStream_t)stream, logits, C, h, w, ds, prob, H, W);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
@@ -1192,7 +1192,7 @@ extern "C" int pfst_trg_valid_mask(const unsigned char* gt, const unsigned char*
   PFST_CHECK_ARG(gt && mix_mask && valid && count && N > 0 && N <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && dil >= 1 && ksize_ok(ksize));
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(count, 0, sizeof(unsigned long long), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(trg_valid_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, gt, mix_mask, H, W,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(trg_valid_kernel<K_>, dim3(px_blocks256((i64)H * W), N), dim3(256), 0, s, gt, mix_mask, H, W,
                                               Hg, Wg, dil, valid, all_in, count));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
@@ -1206,7 +1206,7 @@ extern "C" int pfst_sim_topk_loss(const float* ema_sim, const float* prob, const
   PFST_CHECK_ARG(top_k >= 0 && top_k <= ksize * ksize - 1);     // 0 = all K^2 pairs (top_k=None)
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(acc, 0, 2 * sizeof(double), s) != hipSuccess) return PFST_ERR_LAUNCH;
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(topk_loss_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, s, ema_sim, prob, valid,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(topk_loss_kernel<K_>, dim3(px_blocks256((i64)H * W), N), dim3(256), 0, s, ema_sim, prob, valid,
                                               count, C, H, W, dil, top_k, w_pos, w_neg, gP, acc, g_sim));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
@@ -1216,7 +1216,7 @@ extern "C" int pfst_cross_prob_bwd(const float* prob, const float* gP, int N, in
                                    int unfold_grad, float* dlogits, int h, int w, pfst_stream_t stream) {
   PFST_CHECK_ARG(prob && gP && dlogits && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0 && dil >= 1 && ds >= 1 && ksize_ok(ksize));
   PFST_CHECK_ARG((H - 1) * ds < h && (W - 1) * ds < w);
-  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(cross_prob_bwd_kernel<K_>, dim3(px_blocks((i64)H * W), N), dim3(256), 0, (hipStream_t)stream,
+  PFST_KSIZE_SWITCH(ksize, hipLaunchKernelGGL(cross_prob_bwd_kernel<K_>, dim3(px_blocks256((i64)H * W), N), dim3(256), 0, (hipStream_t)stream,
                                               prob, gP, C, H, W, dil, ds, unfold_grad, dlogits, h, w));
   PFST_CHECK_LAUNCH();
   return PFST_OK;

@@ -12,19 +12,13 @@
 #include <limits.h>
 #include <algorithm>
 #include "common.h"
-#include "bilin.h"
+#include "upsample_walk.h"
 #include "../../include/pfst_hip.h"
 
 // plain + - * round one by one; every fused multiply-add below is written as one
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // exp(-a), a >= 0, on the hardware's base-2 exponential (v_exp_f32).  libm's expf spends its instructions on the range reduction of an
 // argument of either sign and on denormal results; here the argument is never positive and a result below 2^-126 may be 0.  The rounding
@@ -144,9 +138,53 @@ __global__ __launch_bounds__(256) void sig_fwd_kernel(const float* __restrict__ 
   }
 }
 
-// The x4 / x8 cases (H == S h, W == S w, C <= 8) by inter-cell blocks, as ce_fwd_blocks_kernel: one thread per S x S block of
-// full-resolution pixels that interpolate from the same four cells, whose 4 x C logits are loaded once.  Per pixel the interpolation and the
-// arg-max are ce_fwd_blocks_kernel's (same coordinates, weights, class order).
+// an image-independent (k_pos, k_neg) table, by class
+__device__ __forceinline__ void sig_coef(const float* __restrict__ coef, int C, float (&kpos)[8], float (&kneg)[8]) {
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    kpos[c] = c < C ? coef[2 * c] : 0.f;
+    kneg[c] = c < C ? coef[2 * c + 1] : 0.f;
+  }
+}
+
+// What the sigmoid losses' forward does with a pixel of fwd_blocks_walk (upsample_walk.h): the accuracy counts from the frame's arg-max
+// and, where the pixel counts and its weight is not zero, its C weighted loss terms.  The tables and sums are the kernel's own arrays: a
+// functor that is indexed by a loop variable would stay in memory until that loop is unrolled.
+template <int GM>
+struct SigFwdPx {
+  const float* __restrict__ pwp;
+  int C, ign;
+  float gamma;
+  const float (&kpos)[8], (&kneg)[8];
+  double (&sum)[8];
+  int correct, valid, bad;
+  float2 g2;
+  __device__ __forceinline__ void pair(i64 p) {
+    g2 = make_float2(1.f, 1.f);
+    if (pwp) g2 = *reinterpret_cast<const float2*>(pwp + p);
+  }
+  __device__ __forceinline__ void pixel(int k, int l, const float (&zc)[8], float, int arg) {
+    const float wgt = k ? g2.y : g2.x;
+    // on copies that are stored back unconditionally: updates of the members under the branches would be merged into one store through a
+    // selected address
+    int co = correct, va = valid, ba = bad;
+    if (l != ign && l < C) {
+      va += 1;
+      if (arg == l) co += 1;
+      if (wgt != 0.f) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (c < C) sum[c] += (double)(wgt * sig_loss<GM>(zc[c], c == l, kpos[c], kneg[c], gamma));
+      }
+    } else if (l != ign) {
+      ba += 1;
+    }
+    correct = co; valid = va; bad = ba;
+  }
+  __device__ __forceinline__ void pair_end(i64) {}
+};
+
+// The x4 / x8 cases (H == S h, W == S w, C <= 8) by inter-cell blocks.
 // grid: (ceil((w + 1) / 16), ceil((h + 1) / (16 TILES)), N), 16 x 16 threads
 template <int S, int TILES, int GM>
 __global__ __launch_bounds__(256) void sig_fwd_blocks_kernel(const float* __restrict__ logits, int C, int h, int w,
@@ -155,85 +193,15 @@ __global__ __launch_bounds__(256) void sig_fwd_blocks_kernel(const float* __rest
                                                              long long* __restrict__ cnt) {
   __shared__ double smd[4][8];
   __shared__ int smi[4][4];
-  const int n = blockIdx.z, H = S * h, W = S * w, hw = h * w;
-  const int bx = blockIdx.x * 16 + (threadIdx.x & 15) - 1;
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* pwp = pw ? pw + (i64)n * H * W : nullptr;
+  const i64 n = blockIdx.z, HW = (i64)S * h * S * w;
   float kpos[8], kneg[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    kpos[c] = c < C ? coef[2 * c] : 0.f;
-    kneg[c] = c < C ? coef[2 * c + 1] : 0.f;
-  }
+  sig_coef(coef, C, kpos, kneg);
   double sum[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) sum[c] = 0.0;
-  int correct = 0, valid = 0, bad = 0;
-  for (int it = 0; it < TILES; ++it) {
-    const int by = (blockIdx.y * TILES + it) * 16 + (threadIdx.x >> 4) - 1;
-    if (bx > w - 1 || by > h - 1) continue;
-    const int xl = max(bx, 0), xr = min(xl + 1, w - 1), yt = max(by, 0), yb = min(yt + 1, h - 1);
-    float v[2][2][8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float* q = lp + (i64)(c < C ? c : 0) * hw;
-      v[0][0][c] = q[yt * w + xl];
-      v[0][1][c] = q[yt * w + xr];
-      v[1][0][c] = q[yb * w + xl];
-      v[1][1][c] = q[yb * w + xr];
-    }
-    float lx0[S], lx1[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      const int ox = S * bx + S / 2 + j;
-      int x0, x1;
-      lx0[j] = lx1[j] = 0.f;
-      if (ox >= 0 && ox < W) bilin_src(ox, 1.f / S, w, x0, x1, lx0[j], lx1[j]);
-    }
-#pragma unroll
-    for (int r = 0; r < S; ++r) {
-      const int oy = S * by + S / 2 + r;
-      if (oy < 0 || oy >= H) continue;
-      int y0, y1;
-      float ly0, ly1;
-      bilin_src(oy, 1.f / S, h, y0, y1, ly0, ly1);
-#pragma unroll
-      for (int half = 0; half < S / 2; ++half) {
-        const int ox = S * bx + S / 2 + 2 * half;                  // pixel pairs are inside the image together (W = S w, ox even)
-        if (ox < 0 || ox >= W) continue;
-        const i64 p = (i64)oy * W + ox;
-        const unsigned short l2 = *reinterpret_cast<const unsigned short*>(lab + p);
-        float2 g2 = make_float2(1.f, 1.f);
-        if (pwp) g2 = *reinterpret_cast<const float2*>(pwp + p);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int j = 2 * half + k;
-          const int l = k ? (l2 >> 8) : (l2 & 255);
-          const float wgt = k ? g2.y : g2.x;
-          float mx = -INFINITY;
-          int arg = 0;
-          float zc[8];
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            zc[c] = c < C ? bilin_blend(v[0][0][c], v[0][1][c], v[1][0][c], v[1][1][c], lx0[j], lx1[j], ly0, ly1) : -INFINITY;
-            if (c < C && zc[c] > mx) { mx = zc[c]; arg = c; }
-          }
-          if (l != ign && l < C) {
-            valid += 1;
-            if (arg == l) correct += 1;
-            if (wgt != 0.f) {
-#pragma unroll
-              for (int c = 0; c < 8; ++c)
-                if (c < C) sum[c] += (double)(wgt * sig_loss<GM>(zc[c], c == l, kpos[c], kneg[c], gamma));
-            }
-          } else if (l != ign) {
-            bad += 1;
-          }
-        }
-      }
-    }
-  }
+  SigFwdPx<GM> px{pw ? pw + n * HW : nullptr, C, ign, gamma, kpos, kneg, sum, 0, 0, 0};
+  fwd_blocks_walk<S, TILES>(logits + n * C * h * w, C, h, w, label + n * HW, px);
+  int correct = px.correct, valid = px.valid, bad = px.bad;
   // one row of partials per workgroup: lanes by shuffles, the four waves through LDS in wave order
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
@@ -293,232 +261,80 @@ __global__ __launch_bounds__(1024) void sig_finalize_kernel(const double* __rest
   }
 }
 
-// grid: (blocks over h*w, C, N).  One thread per low-resolution logit; gathers its full-res footprint (ce_bwd_kernel's gather).  The gradient
-// is separable per class, so any C runs without a per-pixel work map.
+// What the sigmoid losses' gradient reads per pixel and its terms for the backward frames of upsample_walk.h: sig_grad of each class,
+// weighted by the pixel weight; an ignored or out-of-range label or a zero weight adds nothing.  The gradient is separable per class, so
+// any C runs (bwd_class_gather) without a per-pixel work map.  kpos / kneg: the kernel's own arrays, as in SigFwdPx.
+template <int GM>
+struct SigBwdPx {
+  const float* __restrict__ pwp;
+  int C, ign;
+  float gamma;
+  const float (&kpos)[8], (&kneg)[8];
+  int c0;                        // the class that the frame calls 0: the launch row's in bwd_class_gather (its table entry is [0]), else 0
+  float2 g2;
+  int l;                         // the current pixel's label
+  __device__ __forceinline__ void pair(i64 p) {
+    g2 = make_float2(1.f, 1.f);
+    if (pwp) g2 = *reinterpret_cast<const float2*>(pwp + p);
+  }
+  __device__ __forceinline__ bool skip(int k, int l_) const { return l_ == ign || l_ >= C || (k ? g2.y : g2.x) == 0.f; }
+  __device__ __forceinline__ bool cell_skip(int p, int l_) const {
+    if (l_ == ign || l_ >= C) return true;
+    return (pwp ? pwp[p] : 1.f) == 0.f;
+  }
+  template <class Z>
+  __device__ __forceinline__ float weight(int k, int l_, const Z&) {
+    l = l_;
+    return k ? g2.y : g2.x;
+  }
+  template <class Z>
+  __device__ __forceinline__ float cell_weight(int p, int l_, const Z&) {
+    l = l_;
+    return pwp ? pwp[p] : 1.f;
+  }
+  template <class Z>
+  __device__ __forceinline__ float term(int c, const Z& z) const { return sig_grad<GM>(z(c), l == c0 + c, kpos[c], kneg[c], gamma); }
+};
+
+// grid: (blocks over h*w, C, N).  One thread per low-resolution logit; gathers its full-res footprint.
 template <int GM>
 __global__ __launch_bounds__(256) void sig_bwd_kernel(const float* __restrict__ logits, int C, int h, int w, const unsigned char* __restrict__ label,
                                                       const float* __restrict__ pw, int H, int W, int ign, float sh, float sw,
                                                       const float* __restrict__ coef, float gamma, float scale, float* __restrict__ dlogits,
                                                       int accumulate) {
-  const int c = blockIdx.y, n = blockIdx.z;
-  const float* lp = logits + ((i64)n * C + c) * h * w;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* pwp = pw ? pw + (i64)n * H * W : nullptr;
-  const float kpos = coef[2 * c], kneg = coef[2 * c + 1];
-  float* dp = dlogits + ((i64)n * C + c) * h * w;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h * w; i += gridDim.x * blockDim.x) {
-    const int iy = i / w, ix = i - iy * w;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, H - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, W - 1);
-    float acc = 0.f;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float ly0, ly1;
-      bilin_src(oy, sh, h, y0, y1, ly0, ly1);
-      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        Bilin b;
-        b.y0 = y0; b.y1 = y1; b.ly0 = ly0; b.ly1 = ly1;
-        bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-        const float wx = (b.x0 == ix ? b.lx0 : 0.f) + (b.x1 == ix ? b.lx1 : 0.f);
-        if (wx == 0.f) continue;
-        const int p = oy * W + ox;
-        const int l = lab[p];
-        if (l == ign || l >= C) continue;
-        const float g = pwp ? pwp[p] : 1.f;
-        if (g == 0.f) continue;
-        acc = fmaf(wy * wx * g, sig_grad<GM>(interp(lp, w, b), l == c, kpos, kneg, gamma), acc);
-      }
-    }
-    acc *= scale;
-    dp[i] = accumulate ? dp[i] + acc : acc;
-  }
+  const int c = blockIdx.y;
+  const i64 n = blockIdx.z, HW = (i64)H * W, plane = (n * C + c) * h * w;
+  const float kpos[8] = {coef[2 * c]}, kneg[8] = {coef[2 * c + 1]};
+  SigBwdPx<GM> px{pw ? pw + n * HW : nullptr, C, ign, gamma, kpos, kneg, c};
+  bwd_class_gather(logits + plane, h, w, label + n * HW, H, W, sh, sw, scale, dlogits + plane, accumulate, px);
 }
 
-// The same gather with ONE thread per low-resolution cell for all classes (C <= 8), as ce_bwd_cells_kernel: the per-pixel work that does not
-// depend on the class is done once.                                                                        grid: (blocks over h*w, 1, N)
+// ONE thread per low-resolution cell for all classes (C <= 8).                                          grid: (blocks over h*w, 1, N)
 template <int GM>
 __global__ __launch_bounds__(256) void sig_bwd_cells_kernel(const float* __restrict__ logits, int C, int h, int w,
                                                             const unsigned char* __restrict__ label, const float* __restrict__ pw, int H, int W,
                                                             int ign, float sh, float sw, const float* __restrict__ coef, float gamma,
                                                             float scale, float* __restrict__ dlogits, int accumulate) {
-  const int n = blockIdx.z;
-  const int hw = h * w;
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* pwp = pw ? pw + (i64)n * H * W : nullptr;
-  float* dp = dlogits + (i64)n * C * hw;
+  const i64 n = blockIdx.z, HW = (i64)H * W, img = n * C * h * w;
   float kpos[8], kneg[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    kpos[c] = c < C ? coef[2 * c] : 0.f;
-    kneg[c] = c < C ? coef[2 * c + 1] : 0.f;
-  }
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
-    const int iy = i / w, ix = i - iy * w;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, H - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, W - 1);
-    float acc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] = 0.f;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float ly0, ly1;
-      bilin_src(oy, sh, h, y0, y1, ly0, ly1);
-      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        Bilin b;
-        b.y0 = y0; b.y1 = y1; b.ly0 = ly0; b.ly1 = ly1;
-        bilin_src(ox, sw, w, b.x0, b.x1, b.lx0, b.lx1);
-        const float wx = (b.x0 == ix ? b.lx0 : 0.f) + (b.x1 == ix ? b.lx1 : 0.f);
-        if (wx == 0.f) continue;
-        const int p = oy * W + ox;
-        const int l = lab[p];
-        if (l == ign || l >= C) continue;
-        const float g = pwp ? pwp[p] : 1.f;
-        if (g == 0.f) continue;
-        const float wg = wy * wx * g;
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-          if (c < C) acc[c] = fmaf(wg, sig_grad<GM>(interp(lp + (i64)c * hw, w, b), l == c, kpos[c], kneg[c], gamma), acc[c]);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c < C) {
-        const float a = acc[c] * scale;
-        dp[(i64)c * hw + i] = accumulate ? dp[(i64)c * hw + i] + a : a;
-      }
-    }
-  }
+  sig_coef(coef, C, kpos, kneg);
+  SigBwdPx<GM> px{pw ? pw + n * HW : nullptr, C, ign, gamma, kpos, kneg, 0};
+  bwd_cells_gather(logits + img, C, h, w, label + n * HW, H, W, sh, sw, scale, dlogits + img, accumulate, px);
 }
 
-// The x4 / x8 cases by inter-cell blocks, ce_bwd_blocks_kernel's scheme: one thread loads the 4 x C corner logits of its S x S block once,
-// evaluates each pixel's C terms once and keeps the 4 x C corner sums in registers; the corner sums of a 16 x 16 tile of blocks meet in LDS
-// in four conflict-free phases and the 15 x 15 cells whose four blocks lie inside the workgroup are written out.
-// grid: (ceil(w / 15), ceil(h / 15), N)
+// The x4 / x8 cases by inter-cell blocks.                                                        grid: (ceil(w / 15), ceil(h / 15), N)
 template <int S, int GM>
 __global__ __launch_bounds__(256) void sig_bwd_blocks_kernel(const float* __restrict__ logits, int C, int h, int w,
                                                              const unsigned char* __restrict__ label, const float* __restrict__ pw, int ign,
                                                              const float* __restrict__ coef, float gamma, float scale,
                                                              float* __restrict__ dlogits, int accumulate) {
-  constexpr int TB = 16, OWN = TB - 1;
-  __shared__ float cell[8][TB + 1][TB + 1];
-  const int n = blockIdx.z, H = S * h, W = S * w, hw = h * w;
-  const int tx = threadIdx.x & (TB - 1), ty = threadIdx.x >> 4;
-  const int cx0 = blockIdx.x * OWN, cy0 = blockIdx.y * OWN;        // first cell this workgroup owns
-  const int bx = cx0 - 1 + tx, by = cy0 - 1 + ty;                  // this thread's block: taps (b, b + 1), clamped at the borders
-  const float* lp = logits + (i64)n * C * hw;
-  const unsigned char* lab = label + (i64)n * H * W;
-  const float* pwp = pw ? pw + (i64)n * H * W : nullptr;
-  for (int i = threadIdx.x; i < 8 * (TB + 1) * (TB + 1); i += 256) (&cell[0][0][0])[i] = 0.f;
+  const i64 n = blockIdx.z, HW = (i64)S * h * S * w, img = n * C * h * w;
   float kpos[8], kneg[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    kpos[c] = c < C ? coef[2 * c] : 0.f;
-    kneg[c] = c < C ? coef[2 * c + 1] : 0.f;
-  }
-  float acc[2][2][8];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int c = 0; c < 8; ++c) acc[a][b][c] = 0.f;
-  if (bx <= w - 1 && by <= h - 1) {
-    const int xl = max(bx, 0), xr = min(xl + 1, w - 1), yt = max(by, 0), yb = min(yt + 1, h - 1);
-    float v[2][2][8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float* q = lp + (i64)(c < C ? c : 0) * hw;
-      v[0][0][c] = q[yt * w + xl];
-      v[0][1][c] = q[yt * w + xr];
-      v[1][0][c] = q[yb * w + xl];
-      v[1][1][c] = q[yb * w + xr];
-    }
-    float lx0[S], lx1[S], wxl[S], wxr[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      const int ox = S * bx + S / 2 + j;
-      int x0 = 0, x1 = 0;
-      lx0[j] = lx1[j] = 0.f;
-      if (ox >= 0 && ox < W) bilin_src(ox, 1.f / S, w, x0, x1, lx0[j], lx1[j]);
-      wxl[j] = (x0 == bx ? lx0[j] : 0.f) + (x1 == bx ? lx1[j] : 0.f);
-      wxr[j] = (x0 == bx + 1 ? lx0[j] : 0.f) + (x1 == bx + 1 ? lx1[j] : 0.f);
-    }
-#pragma unroll
-    for (int r = 0; r < S; ++r) {
-      const int oy = S * by + S / 2 + r;
-      if (oy < 0 || oy >= H) continue;
-      int y0, y1;
-      float ly0, ly1;
-      bilin_src(oy, 1.f / S, h, y0, y1, ly0, ly1);
-      const float wyt = (y0 == by ? ly0 : 0.f) + (y1 == by ? ly1 : 0.f);
-      const float wyb = (y0 == by + 1 ? ly0 : 0.f) + (y1 == by + 1 ? ly1 : 0.f);
-#pragma unroll
-      for (int half = 0; half < S / 2; ++half) {
-        const int ox = S * bx + S / 2 + 2 * half;                  // pixel pairs are inside the image together (W = S w, ox even)
-        if (ox < 0 || ox >= W) continue;
-        const i64 p = (i64)oy * W + ox;
-        const unsigned short l2 = *reinterpret_cast<const unsigned short*>(lab + p);
-        float2 g2 = make_float2(1.f, 1.f);
-        if (pwp) g2 = *reinterpret_cast<const float2*>(pwp + p);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int j = 2 * half + k;
-          const int l = k ? (l2 >> 8) : (l2 & 255);
-          const float g = k ? g2.y : g2.x;
-          if (l == ign || l >= C || g == 0.f) continue;
-          const float wtl = wyt * wxl[j] * g, wtr = wyt * wxr[j] * g, wbl = wyb * wxl[j] * g, wbr = wyb * wxr[j] * g;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            if (c < C) {
-              const float z = bilin_blend(v[0][0][c], v[0][1][c], v[1][0][c], v[1][1][c], lx0[j], lx1[j], ly0, ly1);
-              const float d = sig_grad<GM>(z, l == c, kpos[c], kneg[c], gamma);
-              acc[0][0][c] = fmaf(wtl, d, acc[0][0][c]);
-              acc[0][1][c] = fmaf(wtr, d, acc[0][1][c]);
-              acc[1][0][c] = fmaf(wbl, d, acc[1][0][c]);
-              acc[1][1][c] = fmaf(wbr, d, acc[1][1][c]);
-            }
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        if (c < C) cell[c][ty + a][tx + b] += acc[a][b][c];
-      __syncthreads();
-    }
-  }
-  float* dp = dlogits + (i64)n * C * hw;
-  for (int i = threadIdx.x; i < OWN * OWN; i += 256) {
-    const int u = i / OWN, q = i - u * OWN;
-    const int gy = cy0 + u, gx = cx0 + q;
-    if (gy >= h || gx >= w) continue;
-    for (int c = 0; c < C; ++c) {
-      const float a = cell[c][u + 1][q + 1] * scale;
-      float* o = dp + (i64)c * hw + gy * w + gx;
-      *o = accumulate ? *o + a : a;
-    }
-  }
+  sig_coef(coef, C, kpos, kneg);
+  SigBwdPx<GM> px{pw ? pw + n * HW : nullptr, C, ign, gamma, kpos, kneg, 0};
+  bwd_blocks_walk<S>(logits + img, C, h, w, label + n * HW, scale, dlogits + img, accumulate, px);
 }
 
-// form: 0 = the generic kernels, 4 / 8 = the inter-cell block kernels of that ratio (the caller chooses, the library checks)
-inline bool form_ok(int form, int C, int h, int w, int H, int W, const void* pw, const void* label) {
-  if (form == 0) return true;
-  return (form == 4 || form == 8) && C <= 8 && H == form * h && W == form * w && ((uintptr_t)pw & 7) == 0 && ((uintptr_t)label & 1) == 0 &&
-         h < 65535 * 15;
-}
 inline bool shape_ok(int N, int C, int h, int w, int H, int W) {
   return N > 0 && N <= 65535 && C > 0 && C <= 255 && h > 0 && w > 0 && H > 0 && W > 0 && (i64)H * W < INT_MAX - 2048 && (i64)h * w < INT_MAX - 2048;
 }
@@ -537,7 +353,7 @@ extern "C" int pfst_sigloss_upsample_fwd(const float* logits, int N, int C, int 
                                          int H, int W, int ignore_index, const float* coef, float gamma, int form, double* slab,
                                          long long* counts, int blocks, pfst_stream_t stream) {
   PFST_CHECK_ARG(logits && label && coef && slab && counts && shape_ok(N, C, h, w, H, W));
-  PFST_CHECK_ARG(gamma >= 0.f && form_ok(form, C, h, w, H, W, pix_weight, label));
+  PFST_CHECK_ARG(gamma >= 0.f && (form == 0 || blocks_form_ok(form, C, h, w, H, W, label, (uintptr_t)pix_weight)));
   hipStream_t s = (hipStream_t)stream;
   const int gm = gamma_mode(gamma);
   if (form == 0) {
@@ -550,10 +366,8 @@ extern "C" int pfst_sigloss_upsample_fwd(const float* logits, int N, int C, int 
     PFST_SIG_GM(gm, PFST_SIG_FWD);
 #undef PFST_SIG_FWD
   } else {
-    // tiles per workgroup as pfst_ce_upsample_fwd: two at x4, one at x8 (64 pixels per thread)
-    const int gx = cdiv(w + 1, 16), gy = cdiv(h + 1, form == 4 ? 32 : 16);
-    PFST_CHECK_ARG(blocks == gx * gy);
-    const dim3 grid(gx, gy, N);
+    const dim3 grid = fwd_blocks_grid(form, h, w, N);
+    PFST_CHECK_ARG(blocks == (int)(grid.x * grid.y));
 #define PFST_SIG_FWD4(GM)                                                                                                              \
   hipLaunchKernelGGL((sig_fwd_blocks_kernel<4, 2, GM>), grid, dim3(256), 0, s, logits, C, h, w, label, pix_weight, ignore_index, coef, gamma, \
                      slab, counts)
@@ -582,13 +396,13 @@ extern "C" int pfst_sigloss_upsample_bwd(const float* logits, int N, int C, int 
                                          int H, int W, int ignore_index, const float* coef, float gamma, int form, float scale, float* dlogits,
                                          int accumulate, pfst_stream_t stream) {
   PFST_CHECK_ARG(logits && label && coef && dlogits && shape_ok(N, C, h, w, H, W));
-  PFST_CHECK_ARG(gamma >= 0.f && form_ok(form, C, h, w, H, W, pix_weight, label));
+  PFST_CHECK_ARG(gamma >= 0.f && (form == 0 || blocks_form_ok(form, C, h, w, H, W, label, (uintptr_t)pix_weight)));
   hipStream_t s = (hipStream_t)stream;
   const int gm = gamma_mode(gamma);
   const float sh = (float)h / (float)H, sw = (float)w / (float)W;
   const int gx = cdiv((i64)h * w, 256);
   if (form != 0) {
-    const dim3 grid(cdiv(w, 15), cdiv(h, 15), N);
+    const dim3 grid = bwd_blocks_grid(h, w, N);
 #define PFST_SIG_BWD4(GM)                                                                                                                 \
   hipLaunchKernelGGL((sig_bwd_blocks_kernel<4, GM>), grid, dim3(256), 0, s, logits, C, h, w, label, pix_weight, ignore_index, coef, gamma, scale, \
                      dlogits, accumulate)

@@ -239,10 +239,8 @@ __global__ void resize_bilinear_bwd_kernel(const float* __restrict__ dy, i64 dy_
   float* dp = dx + (i64)n * dx_bs + (i64)c * Hi * Wi;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Hi * Wi; i += gridDim.x * blockDim.x) {
     const int iy = i / Wi, ix = i - iy * Wi;
-    int oy_lo = (int)floorf(((float)iy - 0.5f) / sh - 0.5f) - 1, oy_hi = (int)ceilf(((float)iy + 1.5f) / sh - 0.5f) + 1;
-    int ox_lo = (int)floorf(((float)ix - 0.5f) / sw - 0.5f) - 1, ox_hi = (int)ceilf(((float)ix + 1.5f) / sw - 0.5f) + 1;
-    oy_lo = max(oy_lo, 0); oy_hi = min(oy_hi, Ho - 1);
-    ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, Wo - 1);
+    int oy_lo, oy_hi, ox_lo, ox_hi;
+    bilin_footprint(iy, ix, sh, sw, Ho, Wo, oy_lo, oy_hi, ox_lo, ox_hi);
     float acc = 0.f;
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
       int y0, y1; float ly0, ly1;

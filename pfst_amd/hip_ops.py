@@ -1311,17 +1311,24 @@ def ce_finalize(acc, numel, loss_weight):
     return out
 
 
-def dice_form(logits, label_u8, lse=None, generic=False):
-    """which kernels a Dice term runs on: 4 / 8 = the inter-cell block kernels of that ratio (C <= 8, H == S h, W == S w, lse 8-byte and
-    label 2-byte aligned), 0 = the generic ones; generic=True forces 0 (tests compare the two forms on one shape).
+def _blocks_form(logits, label_u8, aligned8, generic):
+    """the form rule of the fused up-sampling losses: 4 / 8 = the inter-cell block kernels of that ratio (C <= 8, H == S h, W == S w, label
+    2-byte aligned and `aligned8` -- the tensor the family reads in pixel pairs, or None -- 8-byte aligned), 0 = the generic ones.
     -> (form, rows of partials per image)"""
     n, c, h, w = logits.shape
     H, W = label_u8.shape[-2:]
     for s, tile_rows in ((4, 32), (8, 16)):
         if (not generic and c <= 8 and H == s * h and W == s * w and label_u8.data_ptr() % 2 == 0 and h < 65535 * 15
-                and (lse is None or lse.data_ptr() % 8 == 0)):
+                and (aligned8 is None or aligned8.data_ptr() % 8 == 0)):
             return s, ((w + 16) // 16) * ((h + tile_rows) // tile_rows)
     return 0, (H * W + 1023) // 1024
+
+
+def dice_form(logits, label_u8, lse=None, generic=False):
+    """which kernels a Dice term runs on: 4 / 8 = the inter-cell block kernels of that ratio (C <= 8, H == S h, W == S w, lse 8-byte and
+    label 2-byte aligned), 0 = the generic ones; generic=True forces 0 (tests compare the two forms on one shape).
+    -> (form, rows of partials per image)"""
+    return _blocks_form(logits, label_u8, lse, generic)
 
 
 def dice_upsample_fwd(logits, label_u8, ignore_index=255, head_ignore_index=255, exponent=2.0, lse=None, generic=False):
@@ -1382,13 +1389,7 @@ def sigloss_form(logits, label_u8, pix_weight=None, generic=False):
     """which kernels a sigmoid loss term (FocalLoss, CrossEntropyLoss(use_sigmoid)) runs on, by dice_form's rules: 4 / 8 = the inter-cell
     block kernels of that ratio (C <= 8, H == S h, W == S w, pixel weights 8-byte and label 2-byte aligned), 0 = the generic ones;
     generic=True forces 0.  -> (form, rows of partials per image)"""
-    n, c, h, w = logits.shape
-    H, W = label_u8.shape[-2:]
-    for s, tile_rows in ((4, 32), (8, 16)):
-        if (not generic and c <= 8 and H == s * h and W == s * w and label_u8.data_ptr() % 2 == 0 and h < 65535 * 15
-                and (pix_weight is None or pix_weight.data_ptr() % 8 == 0)):
-            return s, ((w + 16) // 16) * ((h + tile_rows) // tile_rows)
-    return 0, (H * W + 1023) // 1024
+    return _blocks_form(logits, label_u8, pix_weight, generic)
 
 
 def _sigloss_args(logits, label_u8, pix_weight, coef):
