@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "amax.h"
+#include "bn_bwd.h"
 #include "../../include/pfst_hip.h"
 
 // cache policy of bn_apply's streams (raw buffer aux bits on gfx950: 2 = nt): build-time knobs for A/B builds
@@ -24,15 +25,41 @@ namespace {
 
 constexpr int BN_SPLIT_TARGET = 2048;  // aim for this many blocks in the reduction passes
 
+// this workgroup's place in a (blocks along the plane, C, N) grid; rev: the tensor is walked from its end (planes, images and blocks in
+// descending order) -- see pfst_bn_order()
+struct BnBlock { int bx, c, n; };
+__device__ __forceinline__ BnBlock bn_block(int rev) {
+  return {(int)(rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x), (int)(rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y),
+          (int)(rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z)};
+}
+// plane (n, c) of a tensor of dense planes with batch stride bs
+template <typename T>
+__device__ __forceinline__ T* bn_plane(T* p, i64 bs, const BnBlock& b, int HW) { return p + (i64)b.n * bs + (i64)b.c * HW; }
+
+// thread 0 publishes its workgroup's two sums of channel b.c: det_part != NULL (deterministic mode, api.cpp): they go to slot (n, chunk) of
+// det_part[c][gridDim.z * gridDim.x][2] and bn_det_sum_kernel adds the slots in index order; else they are added atomically into ws
+__device__ __forceinline__ void bn_publish_sums(double* __restrict__ ws, double* __restrict__ det_part, const BnBlock& b, double s0, double s1) {
+  if (det_part) {
+    double* d = det_part + (((i64)b.c * gridDim.z + b.n) * gridDim.x + b.bx) * 2;
+    d[0] = s0;
+    d[1] = s1;
+  } else {
+    atomicAdd(&ws[2 * b.c], s0);
+    atomicAdd(&ws[2 * b.c + 1], s1);
+  }
+}
+__device__ __forceinline__ float amax4(float am, const float4& o) {
+  return fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+}
+
 // grid: (splits, C, N); each block reduces a contiguous chunk of one (image, channel) plane
-// det_part != NULL (deterministic mode, api.cpp): this block's two sums go to slot (n, split) of det_part[c][gridDim.z * gridDim.x][2] instead of
-// being added atomically into ws; bn_det_sum_kernel adds the slots in index order
+// det_part: see bn_publish_sums
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, i64 x_bs, int HW, int chunk,
                                                        double* __restrict__ ws, double* __restrict__ det_part = nullptr) {
   __shared__ double sm[32];
-  const int c = blockIdx.y, n = blockIdx.z;
-  const float* xp = x + (i64)n * x_bs + (i64)c * HW;
-  const int beg = blockIdx.x * chunk;
+  const BnBlock b = bn_block(0);
+  const float* xp = bn_plane(x, x_bs, b, HW);
+  const int beg = b.bx * chunk;
   const int end = min(beg + chunk, HW);
   double s = 0.0, ss = 0.0;
   if ((chunk & 3) == 0 && (HW & 3) == 0 && ((uintptr_t)xp & 15) == 0) {
@@ -49,16 +76,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     }
   }
   block_sum2_d(s, ss, sm);
-  if (threadIdx.x == 0) {
-    if (det_part) {
-      double* d = det_part + (((i64)c * gridDim.z + n) * gridDim.x + blockIdx.x) * 2;
-      d[0] = s;
-      d[1] = ss;
-    } else {
-      atomicAdd(&ws[2 * c], s);
-      atomicAdd(&ws[2 * c + 1], ss);
-    }
-  }
+  if (threadIdx.x == 0) bn_publish_sums(ws, det_part, b, s, ss);
 }
 
 // deterministic mode: ws[2c], ws[2c+1] = the T slots of channel c summed in index order     grid: ceil(C / 256)
@@ -230,15 +248,15 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   // rev: walk the tensor from its end (planes, images and blocks in descending order) -- see pfst_bn_order()
   // amax != NULL: max |y| of what this launch writes goes to that slot group (amax.h): the scale of the next f16x3 GEMM's operand
   float am = 0.f;
-  const int c = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y, n = rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z;
-  const int bxi = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const BnBlock b = bn_block(rev);
+  const int c = b.c, n = b.n, bxi = b.bx;
   float sc, sh;
   bn_affine(mean[c], invstd[c], gamma[c], beta[c], sc, sh);
   const float pm = post ? post[n * C + c] : 1.f;
   const float rsc = res_coef ? res_coef[c].z : 1.f, rsh = res_coef ? res_coef[c].w : 0.f;
-  const float* xp = x + (i64)n * x_bs + (i64)c * HW;
-  const float* rp = res ? res + (i64)n * res_bs + (i64)c * HW : nullptr;
-  float* yp = y + (i64)n * y_bs + (i64)c * HW;
+  const float* xp = bn_plane(x, x_bs, b, HW);
+  const float* rp = res ? bn_plane(res, res_bs, b, HW) : nullptr;
+  float* yp = bn_plane(y, y_bs, b, HW);
   const int stride = gridDim.x * blockDim.x;
   if ((HW & 3) == 0 && (((uintptr_t)xp | (uintptr_t)yp | (uintptr_t)rp) & 15) == 0) {
     const int n4 = HW >> 2;
@@ -272,10 +290,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         }
         if (mask && i < n4) {
           // ReLU bitmask for the backward pass (the host guarantees HW % 256 == 0, so all 64 lanes are here and hold 256
-          // consecutive elements): word [i >> 6][k] bit (lane) <-> component k of lane's float4, i.e. element 4*lane + k
+          // consecutive elements): lanes 0 ... 3 write the four words of float4 number i's group, layout in bn_bwd.h
           const unsigned long long b0 = __ballot(w.x > 0.f), b1 = __ballot(w.y > 0.f), b2 = __ballot(w.z > 0.f), b3 = __ballot(w.w > 0.f);
           const int l = threadIdx.x & 63;
-          if (l < 4) mask[((i64)n * C + c) * (HW >> 6) + (i64)(i >> 6) * 4 + l] = l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3));
+          if (l < 4) relu_mask_plane(mask, n, c, C, HW)[relu_mask_word(i, l)] = l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3));
         }
         if (relu) { w.x = fmaxf(w.x, 0.f); w.y = fmaxf(w.y, 0.f); w.z = fmaxf(w.z, 0.f); w.w = fmaxf(w.w, 0.f); }
         if (post) { w.x *= pm; w.y *= pm; w.z *= pm; w.w *= pm; }
@@ -296,32 +314,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   if (amax) amax_publish(amax, am);
 }
 
-// ReLU gate of element i of a plane: from the bitmask bn_apply wrote (layout there), else from the saved output y, else
-// (no residual) recomputed from x exactly as bn_apply did
-__device__ __forceinline__ bool relu_on(const unsigned long long* __restrict__ mp, const float* __restrict__ yp, int i, float xv,
-                                        float sc, float sh) {
-  if (mp) return (mp[(i >> 8) * 4 + (i & 3)] >> ((i >> 2) & 63)) & 1ull;
-  return (yp ? yp[i] : __fmaf_rn(xv, sc, sh)) > 0.f;
-}
-
-// ReLU gates of the 4 elements of float4 number i4 of a plane (same sources as relu_on)
-__device__ __forceinline__ void relu_on4(const unsigned long long* __restrict__ mp, const float* __restrict__ yp, int i4, const float4& xv,
-                                         float sc, float sh, bool (&on)[4]) {
-  if (mp) {
-    const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(mp + (i4 >> 6) * 4);       // wave-uniform address: broadcast loads
-    const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(mp + (i4 >> 6) * 4 + 2);
-    const int l = i4 & 63;
-    on[0] = (a.x >> l) & 1ull; on[1] = (a.y >> l) & 1ull; on[2] = (b.x >> l) & 1ull; on[3] = (b.y >> l) & 1ull;
-  } else if (yp) {
-    const float4 yv = reinterpret_cast<const float4*>(yp)[i4];
-    on[0] = yv.x > 0.f; on[1] = yv.y > 0.f; on[2] = yv.z > 0.f; on[3] = yv.w > 0.f;
-  } else {
-    on[0] = __fmaf_rn(xv.x, sc, sh) > 0.f; on[1] = __fmaf_rn(xv.y, sc, sh) > 0.f; on[2] = __fmaf_rn(xv.z, sc, sh) > 0.f; on[3] = __fmaf_rn(xv.w, sc, sh) > 0.f;
-  }
-}
-
 // backward pass 1: ws[2c] += sum dz, ws[2c+1] += sum dz*xhat     grid: (splits, C, N)
-// VEC (host: HW % 4 == 0, 16-byte aligned planes): float4 streams
+// VEC (host: bn_vec_route): float4 streams.  Element arithmetic: bn_bwd.h
 template <bool VEC>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, i64 dy_bs, const float* __restrict__ y,
                                                             i64 y_bs, const float* __restrict__ x, i64 x_bs,
@@ -330,21 +324,18 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
                                                             int HW, int chunk, int relu, const unsigned long long* __restrict__ mask,
                                                             double* __restrict__ ws, int rev, const float* __restrict__ post,
                                                             double* __restrict__ det_part = nullptr) {
-  // post != NULL: the incoming gradient is the gradient of y * post[n][c] (bn_apply's folded Dropout2d factor): dz = dy * post * gate
   __shared__ double sm[32];
-  const int c = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y, n = rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z;
-  const int bxi = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
-  const float mu = mean[c], is = invstd[c];
-  const float pm = post ? post[n * gridDim.y + c] : 1.f;
-  // ReLU mask: from the saved output y, or (no residual) recomputed bit-identically to bn_apply from x -- saves the y read
+  const BnBlock b = bn_block(rev);
+  const int C = gridDim.y;
+  const float mu = mean[b.c], is = invstd[b.c];
+  const float pm = post ? post[b.n * C + b.c] : 1.f;
+  // ReLU gate: from the mask, from the saved output y, or (no residual) recomputed bit-identically to bn_apply from x -- saves the y read
   float sc, sh;
-  bn_affine(mu, is, gamma[c], beta ? beta[c] : 0.f, sc, sh);
-  const i64 base = (i64)c * HW;
-  const float* gp = dy + (i64)n * dy_bs + base;
-  const float* yp = y ? y + (i64)n * y_bs + base : nullptr;
-  const unsigned long long* mp = mask ? mask + ((i64)n * gridDim.y + c) * (HW >> 6) : nullptr;
-  const float* xp = x + (i64)n * x_bs + base;
-  const int beg = bxi * chunk;
+  bn_affine(mu, is, gamma[b.c], beta ? beta[b.c] : 0.f, sc, sh);
+  const float* gp = bn_plane(dy, dy_bs, b, HW);
+  const BnGate gate{relu != 0, mask ? relu_mask_plane(mask, b.n, b.c, C, HW) : nullptr, y ? bn_plane(y, y_bs, b, HW) : nullptr, sc, sh, post != nullptr, pm};
+  const float* xp = bn_plane(x, x_bs, b, HW);
+  const int beg = b.bx * chunk;
   const int end = min(beg + chunk, HW);
   double s = 0.0, sx = 0.0;
   if (VEC) {
@@ -365,44 +356,21 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
       for (int u = 0; u < U; ++u) {
         const int i4 = i0 + u * blockDim.x;
         if (i4 >= e4) break;
-        float4 g = gq[u];
-        const float4 xv = xq[u];
-        if (post) { g.x *= pm; g.y *= pm; g.z *= pm; g.w *= pm; }
-        if (relu) {
-          bool on[4];
-          relu_on4(mp, yp, i4, xv, sc, sh, on);
-          if (!on[0]) g.x = 0.f;
-          if (!on[1]) g.y = 0.f;
-          if (!on[2]) g.z = 0.f;
-          if (!on[3]) g.w = 0.f;
-        }
-        s += ((double)g.x + (double)g.y) + ((double)g.z + (double)g.w);
-        sx += ((double)g.x * (double)((xv.x - mu) * is) + (double)g.y * (double)((xv.y - mu) * is)) +
-              ((double)g.z * (double)((xv.z - mu) * is) + (double)g.w * (double)((xv.w - mu) * is));
+        const float4 dz = gate.dz4(gq[u], i4, xq[u]);
+        s += bn_bwd_sum4(dz);
+        sx += bn_bwd_dot4(dz, xq[u], mu, is);
       }
     }
   } else {
     for (int i = beg + threadIdx.x; i < end; i += blockDim.x) {
-      float dz = gp[i];
       const float xv = xp[i];
-      if (post) dz *= pm;
-      if (relu && !relu_on(mp, yp, i, xv, sc, sh)) dz = 0.f;
-      const float xh = (xv - mu) * is;
+      const float dz = gate.dz(gp[i], i, xv);
       s += (double)dz;
-      sx += (double)dz * (double)xh;
+      sx += bn_bwd_dot(dz, xv, mu, is);
     }
   }
   block_sum2_d(s, sx, sm);
-  if (threadIdx.x == 0) {
-    if (det_part) {                                  // deterministic mode: slot (n, chunk) of channel c (see bn_stats_kernel)
-      double* d = det_part + (((i64)c * gridDim.z + n) * gridDim.x + bxi) * 2;
-      d[0] = s;
-      d[1] = sx;
-    } else {
-      atomicAdd(&ws[2 * c], s);
-      atomicAdd(&ws[2 * c + 1], sx);
-    }
-  }
+  if (threadIdx.x == 0) bn_publish_sums(ws, det_part, b, s, sx);
 }
 
 // the two sums from the data-gradient epilogue's partials part[c][T][2] (pfst_bnb_fuse_t) -> ws[2c], ws[2c+1]     grid: C blocks
@@ -421,6 +389,14 @@ __global__ __launch_bounds__(256) void bn_bwd_partials_kernel(const float* __res
   }
 }
 
+// the workgroup that starts a channel adds the parameter gradients from the two sums
+__device__ __forceinline__ void bn_bwd_param_grads(const BnBlock& b, const double* __restrict__ ws, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  if (b.bx == 0 && b.n == 0 && threadIdx.x == 0) {
+    if (dgamma) dgamma[b.c] += (float)ws[2 * b.c + 1];
+    if (dbeta) dbeta[b.c] += (float)ws[2 * b.c];
+  }
+}
+
 #ifndef PFST_BN_BWD_APPLY_U
 #define PFST_BN_BWD_APPLY_U 1
 #endif
@@ -436,33 +412,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            int C, int HW, double inv_count, int relu,
                                                            const unsigned long long* __restrict__ mask, const double* __restrict__ ws, int rev,
                                                            float* __restrict__ amax, const float* __restrict__ post) {
-  const int c = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y, n = rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z;
-  const int bxi = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const BnBlock b = bn_block(rev);
   float am = 0.f;                                      // max |dx| written here -> slot group `amax` (f16x3 scale of the gradient operand)
-  const float mu = mean[c], is = invstd[c];
-  const float pm = post ? post[n * C + c] : 1.f;       // folded Dropout2d factor (see bn_bwd_reduce_kernel)
-  // the two projections are subtracted in fp64: dz - mean(dz) cancels heavily when dz has a large common mode
-  const double m1 = ws[2 * c] * inv_count, m2 = ws[2 * c + 1] * inv_count;
-  const double gs = (double)gamma[c] * (double)is;
-  float sc, sh;
-  bn_affine(mu, is, gamma[c], beta ? beta[c] : 0.f, sc, sh);
-  if (bxi == 0 && n == 0 && threadIdx.x == 0) {
-    if (dgamma) dgamma[c] += (float)ws[2 * c + 1];
-    if (dbeta) dbeta[c] += (float)ws[2 * c];
-  }
-  const i64 base = (i64)c * HW;
-  const float* gp = dy + (i64)n * dy_bs + base;
-  const float* yp = y ? y + (i64)n * y_bs + base : nullptr;
-  const unsigned long long* mp = mask ? mask + ((i64)n * gridDim.y + c) * (HW >> 6) : nullptr;
-  const float* xp = x + (i64)n * x_bs + base;
-  float* dxp = dx + (i64)n * dx_bs + base;
-  float* drp = dres ? dres + (i64)n * dres_bs + base : nullptr;
+  const float pm = post ? post[b.n * C + b.c] : 1.f;   // folded Dropout2d factor (BnGate); read before the sums: its branch would wait for them
+  const pfst_bn_bwd_rec_t r = bn_bwd_rec(ws, mean, invstd, gamma, beta, b.c, inv_count);
+  bn_bwd_param_grads(b, ws, dgamma, dbeta);
+  const float* gp = bn_plane(dy, dy_bs, b, HW);
+  const BnGate gate{relu != 0, mask ? relu_mask_plane(mask, b.n, b.c, C, HW) : nullptr, y ? bn_plane(y, y_bs, b, HW) : nullptr, r.sc, r.sh, post != nullptr, pm};
+  const float* xp = bn_plane(x, x_bs, b, HW);
+  float* dxp = bn_plane(dx, dx_bs, b, HW);
+  float* drp = dres ? bn_plane(dres, dres_bs, b, HW) : nullptr;
   const int stride = gridDim.x * blockDim.x;
   if (VEC) {
     // PFST_BN_BWD_APPLY_U 16-byte loads per operand in flight per thread (the host sizes the grid to match)
     constexpr int U = PFST_BN_BWD_APPLY_U;
     const int n4 = HW >> 2;
-    for (int i0 = bxi * blockDim.x + threadIdx.x; i0 < n4; i0 += U * stride) {
+    for (int i0 = b.bx * blockDim.x + threadIdx.x; i0 < n4; i0 += U * stride) {
       float4 gq[U], xq[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -476,24 +441,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
       for (int u = 0; u < U; ++u) {
         const int i4 = i0 + u * stride;
         if (i4 >= n4) break;
-        float4 g = gq[u];
-        const float4 xv = xq[u];
-        if (post) { g.x *= pm; g.y *= pm; g.z *= pm; g.w *= pm; }
-        if (relu) {
-          bool on[4];
-          relu_on4(mp, yp, i4, xv, sc, sh, on);
-          if (!on[0]) g.x = 0.f;
-          if (!on[1]) g.y = 0.f;
-          if (!on[2]) g.z = 0.f;
-          if (!on[3]) g.w = 0.f;
-        }
-        float4 o;
-        o.x = (float)(gs * ((double)g.x - m1 - (((double)xv.x - (double)mu) * (double)is) * m2));
-        o.y = (float)(gs * ((double)g.y - m1 - (((double)xv.y - (double)mu) * (double)is) * m2));
-        o.z = (float)(gs * ((double)g.z - m1 - (((double)xv.z - (double)mu) * (double)is) * m2));
-        o.w = (float)(gs * ((double)g.w - m1 - (((double)xv.w - (double)mu) * (double)is) * m2));
+        float4 g = gate.dz4(gq[u], i4, xq[u]);
+        const float4 o = bn_bwd_dx4(g, xq[u], r);
         reinterpret_cast<float4*>(dxp)[i4] = o;
-        am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        am = amax4(am, o);
         if (drp) {
           if (dres_acc) {
             const float4 old = reinterpret_cast<const float4*>(drp)[i4];
@@ -504,13 +455,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
       }
     }
   } else {
-    for (int i = bxi * blockDim.x + threadIdx.x; i < HW; i += stride) {
-      float dz = gp[i];
+    for (int i = b.bx * blockDim.x + threadIdx.x; i < HW; i += stride) {
       const float xv = xp[i];
-      if (post) dz *= pm;
-      if (relu && !relu_on(mp, yp, i, xv, sc, sh)) dz = 0.f;
-      const double xh = ((double)xv - (double)mu) * (double)is;
-      const float o = (float)(gs * ((double)dz - m1 - xh * m2));
+      const float dz = gate.dz(gp[i], i, xv);
+      const float o = bn_bwd_dx(dz, xv, r);
       dxp[i] = o;
       am = fmaxf(am, fabsf(o));
       if (drp) drp[i] = dres_acc ? drp[i] + dz : dz;
@@ -522,8 +470,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // ---- two BatchNorm layers behind ONE gated gradient (pfst_bn_backward_dual) --------------------------------------------------------------
 // A stage's first Bottleneck ends in out = relu(bn3(conv3(.)) + bn_d(conv_d(x))) (resnet.py:298-307): bn3 and the downsample branch's BN both
 // receive g = [out > 0] dL/dout.  Layer by layer that is four passes reading g (two reductions, two apply passes: 10 N of traffic); here one
-// reduction reads (g, xa, xb) and one apply pass writes both input gradients: 8 N.  Same arithmetic as the single-layer kernels, element by
-// element (fp64 projections, the same summation order inside a workgroup).
+// reduction reads (g, xa, xb) and one apply pass writes both input gradients: 8 N.  The element arithmetic is the single-layer kernels' own
+// (bn_bwd.h) and the summation order inside a workgroup is theirs: the results are the two single-layer calls', bit for bit
+// (test_e_dual_equals_two_single_layers).
 struct BnDualSide {
   const float* x; i64 x_bs;             // the layer's pre-BN tensor
   const float* mean; const float* invstd; const float* gamma;
@@ -537,15 +486,14 @@ struct BnDualSide {
 __global__ __launch_bounds__(256) void bn_bwd_reduce_dual_kernel(const float* __restrict__ dy, i64 dy_bs, const unsigned long long* __restrict__ mask,
                                                                  BnDualSide a, BnDualSide b, int HW, int chunk, int rev) {
   __shared__ double sm[32];
-  const int c = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y, n = rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z;
-  const int bxi = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const BnBlock blk = bn_block(rev);
+  const int c = blk.c;
   const float mua = a.mean[c], isa = a.invstd[c], mub = b.mean[c], isb = b.invstd[c];
-  const i64 base = (i64)c * HW;
-  const float* gp = dy + (i64)n * dy_bs + base;
-  const unsigned long long* mp = mask + ((i64)n * gridDim.y + c) * (HW >> 6);
-  const float* xap = a.x + (i64)n * a.x_bs + base;
-  const float* xbp = b.x + (i64)n * b.x_bs + base;
-  const int beg = bxi * chunk;
+  const BnGate gate{true, relu_mask_plane(mask, blk.n, c, (int)gridDim.y, HW), nullptr, 0.f, 0.f, false, 1.f};
+  const float* gp = bn_plane(dy, dy_bs, blk, HW);
+  const float* xap = bn_plane(a.x, a.x_bs, blk, HW);
+  const float* xbp = bn_plane(b.x, b.x_bs, blk, HW);
+  const int beg = blk.bx * chunk;
   const int end = min(beg + chunk, HW);
   double s = 0.0, sa = 0.0, sb = 0.0;
   constexpr int U = 4;
@@ -565,19 +513,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_dual_kernel(const float* __
     for (int u = 0; u < U; ++u) {
       const int i4 = i0 + u * blockDim.x;
       if (i4 >= e4) break;
-      float4 g = gq[u];
-      const float4 xa = aq[u], xb = bq[u];
-      bool on[4];
-      relu_on4(mp, nullptr, i4, xa, 0.f, 0.f, on);
-      if (!on[0]) g.x = 0.f;
-      if (!on[1]) g.y = 0.f;
-      if (!on[2]) g.z = 0.f;
-      if (!on[3]) g.w = 0.f;
-      s += ((double)g.x + (double)g.y) + ((double)g.z + (double)g.w);
-      sa += ((double)g.x * (double)((xa.x - mua) * isa) + (double)g.y * (double)((xa.y - mua) * isa)) +
-            ((double)g.z * (double)((xa.z - mua) * isa) + (double)g.w * (double)((xa.w - mua) * isa));
-      sb += ((double)g.x * (double)((xb.x - mub) * isb) + (double)g.y * (double)((xb.y - mub) * isb)) +
-            ((double)g.z * (double)((xb.z - mub) * isb) + (double)g.w * (double)((xb.w - mub) * isb));
+      const float4 dz = gate.dz4(gq[u], i4, aq[u]);
+      s += bn_bwd_sum4(dz);
+      sa += bn_bwd_dot4(dz, aq[u], mua, isa);
+      sb += bn_bwd_dot4(dz, bq[u], mub, isb);
     }
   }
   double s2 = s;
@@ -585,61 +524,39 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_dual_kernel(const float* __
   __syncthreads();
   block_sum2_d(s2, sb, sm);
   if (threadIdx.x == 0) {
-    atomicAdd(&a.ws[2 * c], s);
-    atomicAdd(&a.ws[2 * c + 1], sa);
-    atomicAdd(&b.ws[2 * c], s2);
-    atomicAdd(&b.ws[2 * c + 1], sb);
+    bn_publish_sums(a.ws, nullptr, blk, s, sa);
+    bn_publish_sums(b.ws, nullptr, blk, s2, sb);
   }
 }
 
 // apply: dxa, dxb from one read of g     grid: (blocks over HW, C, N)
 __global__ __launch_bounds__(256) void bn_bwd_apply_dual_kernel(const float* __restrict__ dy, i64 dy_bs, const unsigned long long* __restrict__ mask,
                                                                 BnDualSide a, BnDualSide b, int C, int HW, double inv_count, int rev) {
-  const int c = rev ? C - 1 - blockIdx.y : blockIdx.y, n = rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z;
-  const int bxi = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const BnBlock blk = bn_block(rev);
   float ama = 0.f, amb = 0.f;
-  const float mua = a.mean[c], isa = a.invstd[c], mub = b.mean[c], isb = b.invstd[c];
-  const double m1a = a.ws[2 * c] * inv_count, m2a = a.ws[2 * c + 1] * inv_count;
-  const double m1b = b.ws[2 * c] * inv_count, m2b = b.ws[2 * c + 1] * inv_count;
-  const double gsa = (double)a.gamma[c] * (double)isa, gsb = (double)b.gamma[c] * (double)isb;
-  if (bxi == 0 && n == 0 && threadIdx.x == 0) {
-    if (a.dgamma) a.dgamma[c] += (float)a.ws[2 * c + 1];
-    if (a.dbeta) a.dbeta[c] += (float)a.ws[2 * c];
-    if (b.dgamma) b.dgamma[c] += (float)b.ws[2 * c + 1];
-    if (b.dbeta) b.dbeta[c] += (float)b.ws[2 * c];
-  }
-  const i64 base = (i64)c * HW;
-  const float* gp = dy + (i64)n * dy_bs + base;
-  const unsigned long long* mp = mask + ((i64)n * C + c) * (HW >> 6);
-  const float* xap = a.x + (i64)n * a.x_bs + base;
-  const float* xbp = b.x + (i64)n * b.x_bs + base;
-  float* dap = a.dx + (i64)n * a.dx_bs + base;
-  float* dbp = b.dx + (i64)n * b.dx_bs + base;
+  const pfst_bn_bwd_rec_t ra = bn_bwd_rec(a.ws, a.mean, a.invstd, a.gamma, nullptr, blk.c, inv_count);
+  const pfst_bn_bwd_rec_t rb = bn_bwd_rec(b.ws, b.mean, b.invstd, b.gamma, nullptr, blk.c, inv_count);
+  bn_bwd_param_grads(blk, a.ws, a.dgamma, a.dbeta);
+  bn_bwd_param_grads(blk, b.ws, b.dgamma, b.dbeta);
+  const BnGate gate{true, relu_mask_plane(mask, blk.n, blk.c, C, HW), nullptr, 0.f, 0.f, false, 1.f};
+  const float* gp = bn_plane(dy, dy_bs, blk, HW);
+  const float* xap = bn_plane(a.x, a.x_bs, blk, HW);
+  const float* xbp = bn_plane(b.x, b.x_bs, blk, HW);
+  float* dap = bn_plane(a.dx, a.dx_bs, blk, HW);
+  float* dbp = bn_plane(b.dx, b.dx_bs, blk, HW);
   const int stride = gridDim.x * blockDim.x;
   const int n4 = HW >> 2;
-  for (int i4 = bxi * blockDim.x + threadIdx.x; i4 < n4; i4 += stride) {
-    float4 g = reinterpret_cast<const float4*>(gp)[i4];
+  for (int i4 = blk.bx * blockDim.x + threadIdx.x; i4 < n4; i4 += stride) {
+    const float4 g0 = reinterpret_cast<const float4*>(gp)[i4];
     const float4 xa = reinterpret_cast<const float4*>(xap)[i4];
     const float4 xb = reinterpret_cast<const float4*>(xbp)[i4];
-    bool on[4];
-    relu_on4(mp, nullptr, i4, xa, 0.f, 0.f, on);
-    if (!on[0]) g.x = 0.f;
-    if (!on[1]) g.y = 0.f;
-    if (!on[2]) g.z = 0.f;
-    if (!on[3]) g.w = 0.f;
-    float4 o;
-    o.x = (float)(gsa * ((double)g.x - m1a - (((double)xa.x - (double)mua) * (double)isa) * m2a));
-    o.y = (float)(gsa * ((double)g.y - m1a - (((double)xa.y - (double)mua) * (double)isa) * m2a));
-    o.z = (float)(gsa * ((double)g.z - m1a - (((double)xa.z - (double)mua) * (double)isa) * m2a));
-    o.w = (float)(gsa * ((double)g.w - m1a - (((double)xa.w - (double)mua) * (double)isa) * m2a));
-    reinterpret_cast<float4*>(dap)[i4] = o;
-    ama = fmaxf(fmaxf(ama, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    o.x = (float)(gsb * ((double)g.x - m1b - (((double)xb.x - (double)mub) * (double)isb) * m2b));
-    o.y = (float)(gsb * ((double)g.y - m1b - (((double)xb.y - (double)mub) * (double)isb) * m2b));
-    o.z = (float)(gsb * ((double)g.z - m1b - (((double)xb.z - (double)mub) * (double)isb) * m2b));
-    o.w = (float)(gsb * ((double)g.w - m1b - (((double)xb.w - (double)mub) * (double)isb) * m2b));
-    reinterpret_cast<float4*>(dbp)[i4] = o;
-    amb = fmaxf(fmaxf(amb, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    const float4 g = gate.dz4(g0, i4, xa);
+    const float4 oa = bn_bwd_dx4(g, xa, ra);
+    reinterpret_cast<float4*>(dap)[i4] = oa;
+    ama = amax4(ama, oa);
+    const float4 ob = bn_bwd_dx4(g, xb, rb);
+    reinterpret_cast<float4*>(dbp)[i4] = ob;
+    amb = amax4(amb, ob);
   }
   if (a.amax) amax_publish(a.amax, ama);
   __syncthreads();                     // (amax_publish's LDS slots are reused by the second call)
@@ -654,14 +571,7 @@ __global__ void bn_bwd_rec_kernel(const double* __restrict__ ws, const float* __
   if (c >= C) return;
   if (dgamma) dgamma[c] += (float)ws[2 * c + 1];
   if (dbeta) dbeta[c] += (float)ws[2 * c];
-  pfst_bn_bwd_rec_t r;
-  r.m1 = ws[2 * c] * inv_count;
-  r.m2 = ws[2 * c + 1] * inv_count;
-  r.gs = (double)gamma[c] * (double)invstd[c];
-  r.mu = mean[c];
-  r.is = invstd[c];
-  bn_affine(mean[c], invstd[c], gamma[c], beta[c], r.sc, r.sh);
-  rec[c] = r;
+  rec[c] = bn_bwd_rec(ws, mean, invstd, gamma, beta, c, inv_count);
 }
 
 // split one HW plane into `splits` chunks (multiples of 4) so the reduction launches ~BN_SPLIT_TARGET blocks
@@ -679,10 +589,10 @@ inline void split_for(int HW, int C, int N, int& splits, int& chunk) {
 // out (+)= g where the ReLU bitmask has the element's bit (the identity branch of a residual block written out after all: engine.Var._flush_pending)
 __global__ __launch_bounds__(256) void relu_gate_kernel(const float* __restrict__ g, i64 g_bs, const unsigned long long* __restrict__ mask,
                                                         float* __restrict__ out, i64 out_bs, int C, int HW, int accumulate) {
-  const int c = blockIdx.y, n = blockIdx.z;
-  const float* gp = g + (i64)n * g_bs + (i64)c * HW;
-  float* op = out + (i64)n * out_bs + (i64)c * HW;
-  const unsigned long long* mp = mask + ((i64)n * C + c) * (HW >> 6);
+  const BnBlock b = bn_block(0);
+  const float* gp = bn_plane(g, g_bs, b, HW);
+  float* op = bn_plane(out, out_bs, b, HW);
+  const unsigned long long* mp = relu_mask_plane(mask, b.n, b.c, C, HW);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
     const float v = relu_on(mp, nullptr, i, 0.f, 0.f, 0.f) ? gp[i] : 0.f;
     op[i] = accumulate ? op[i] + v : v;
@@ -696,6 +606,37 @@ inline double* bn_det_part(int C, int N, int splits, hipStream_t s, bool& ok) {
   double* p = static_cast<double*>(pfst_det_scratch((size_t)C * N * splits * 2 * sizeof(double), s));
   ok = p != nullptr;
   return p;
+}
+
+// THE float4-route condition of a launch: whole float4s per plane, every batch stride a multiple of 4 floats, every base 16-byte aligned.
+// An operand that is not given goes in as stride 0 / NULL.  ("Path conditions of the BatchNorm entries")
+inline bool bn_vec_route(int HW, std::initializer_list<long long> strides, std::initializer_list<const void*> bases) {
+  long long s = HW;
+  uintptr_t p = 0;
+  for (long long v : strides) s |= v;
+  for (const void* q : bases) p |= (uintptr_t)q;
+  return (s & 3) == 0 && (p & 15) == 0;
+}
+
+// Traversal order of the streaming BatchNorm kernels (bit 0: normalise pass, bit 1: backward reduction, bit 2: backward apply run from the
+// END of the tensor).  A pass that starts where its producer stopped finds the producer's last ~100-200 MB in the Infinity Cache.
+constexpr int pfst_bn_order() { return 3; }      // measured (round 3): 3 and 7 -0.4 % on the step against 0 = all ascending
+
+// the reduction pass of one layer: ws[2c], ws[2c+1] = (sum dz, sum dz * xhat) over dy and x.  clear: ws is zeroed here (else the caller has);
+// deterministic mode: slots + bn_det_sum_kernel's ordered sum instead of the atomics
+int bn_bwd_reduce(hipStream_t s, bool clear, bool vec, const float* dy, i64 dy_bs, const float* y, i64 y_bs, const float* x, i64 x_bs,
+                  const float* mean, const float* invstd, const float* gamma, const float* beta, int N, int C, int HW, int relu,
+                  const unsigned long long* mask, double* ws, const float* post) {
+  if (clear && hipMemsetAsync(ws, 0, sizeof(double) * 2 * C, s) != hipSuccess) return PFST_ERR_LAUNCH;
+  int splits, chunk;
+  split_for(HW, C, N, splits, chunk);
+  bool det_ok;
+  double* const det = bn_det_part(C, N, splits, s, det_ok);
+  PFST_CHECK_DET(det_ok);
+  hipLaunchKernelGGL(vec ? bn_bwd_reduce_kernel<true> : bn_bwd_reduce_kernel<false>, dim3(splits, C, N), dim3(256), 0, s, dy, dy_bs, y, y_bs,
+                     x, x_bs, mean, invstd, gamma, beta, HW, chunk, relu, mask, ws, (pfst_bn_order() >> 1) & 1, post, det);
+  if (det) hipLaunchKernelGGL(bn_det_sum_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, det, N * splits, C, ws);
+  return PFST_OK;
 }
 
 }  // namespace
@@ -739,10 +680,6 @@ extern "C" int pfst_bn_finalize_partials(const float* partials, int T, int C, do
   return PFST_OK;
 }
 
-// Traversal order of the streaming BatchNorm kernels (bit 0: normalise pass, bit 1: backward reduction, bit 2: backward apply run from the
-// END of the tensor).  A pass that starts where its producer stopped finds the producer's last ~100-200 MB in the Infinity Cache.
-static constexpr int pfst_bn_order() { return 3; }      // measured (round 3): 3 and 7 -0.4 % on the step against 0 = all ascending
-
 extern "C" int pfst_bn_apply(const float* x, long long x_bs, const float* residual, long long res_bs, float* y, long long y_bs,
                              const float* mean, const float* invstd, const float* gamma, const float* beta,
                              int N, int C, int HW, int relu, unsigned long long* relu_mask, float* y_amax, const float* post_scale,
@@ -751,8 +688,7 @@ extern "C" int pfst_bn_apply(const float* x, long long x_bs, const float* residu
   PFST_CHECK_ARG(!residual_coef || residual);
   PFST_CHECK_ARG(!post_scale || !residual);          // the folded Dropout2d factor belongs to a plain conv -> BN -> ReLU layer
   // the bitmask comes out of the float4 path only: whole 256-element groups per wave, 16-byte aligned planes
-  PFST_CHECK_ARG(!relu_mask || (relu && HW % 256 == 0 && ((x_bs | y_bs | (residual ? res_bs : 0)) & 3) == 0 &&
-                                (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0));
+  PFST_CHECK_ARG(!relu_mask || (relu && HW % 256 == 0 && bn_vec_route(HW, {x_bs, y_bs, residual ? res_bs : 0}, {x, y, residual})));
   int gx = cdiv(HW, 256 * 4 * 4);
   if (gx < 1) gx = 1;
   hipLaunchKernelGGL(bn_apply_kernel, dim3(gx, C, N), dim3(256), 0, (hipStream_t)stream, x, x_bs, residual, res_bs, y, y_bs, mean,
@@ -774,34 +710,16 @@ extern "C" int pfst_bn_backward(const float* dy, long long dy_bs, const float* y
   PFST_CHECK_ARG(!relu || relu_mask || y || beta);   // ReLU mask from y, or recomputed from x with beta (no residual)
   PFST_CHECK_ARG(!bwd_partials || bwd_slots > 0);
   hipStream_t s = (hipStream_t)stream;
-  const bool fused = bwd_partials != nullptr;      // the sums came out of the launch that produced dy: no reduction pass
-  if (fused) hipLaunchKernelGGL(bn_bwd_partials_kernel, dim3(C), dim3(256), 0, s, bwd_partials, bwd_slots, mean, invstd, ws);
-  else if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * C, s) != hipSuccess) return PFST_ERR_LAUNCH;
-  int splits, chunk;
-  split_for(HW, C, N, splits, chunk);
-  bool det_ok = true;
-  double* const det = fused ? nullptr : bn_det_part(C, N, splits, s, det_ok);      // deterministic mode: slots + ordered sum instead of atomics
-  PFST_CHECK_DET(det_ok);
-  const bool vec = (HW & 3) == 0 && ((dy_bs | x_bs | dx_bs | (y ? y_bs : 0) | (dres ? dres_bs : 0)) & 3) == 0 &&
-                   (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)y | (uintptr_t)dres) & 15) == 0;
+  const bool vec = bn_vec_route(HW, {dy_bs, x_bs, dx_bs, y ? y_bs : 0, dres ? dres_bs : 0}, {dy, x, dx, y, dres});
+  if (bwd_partials)                                // the sums came out of the launch that produced dy: no reduction pass
+    hipLaunchKernelGGL(bn_bwd_partials_kernel, dim3(C), dim3(256), 0, s, bwd_partials, bwd_slots, mean, invstd, ws);
+  else if (const int err = bn_bwd_reduce(s, true, vec, dy, dy_bs, y, y_bs, x, x_bs, mean, invstd, gamma, beta, N, C, HW, relu, relu_mask, ws, post_scale))
+    return err;
   int gx = cdiv(HW, 256 * 4 * (vec ? PFST_BN_BWD_APPLY_U : 1));
   if (gx < 1) gx = 1;
-  const double inv_count = 1.0 / ((double)N * HW);
-  if (vec) {
-    if (!fused)
-      hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(splits, C, N), dim3(256), 0, s, dy, dy_bs, y, y_bs, x, x_bs, mean, invstd, gamma,
-                         beta, HW, chunk, relu, relu_mask, ws, (pfst_bn_order() >> 1) & 1, post_scale, det);
-    if (!fused && det) hipLaunchKernelGGL(bn_det_sum_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, det, N * splits, C, ws);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(gx, C, N), dim3(256), 0, s, dy, dy_bs, y, y_bs, x, x_bs, mean, invstd, gamma, beta,
-                       dx, dx_bs, dres, dres_bs, dres_accumulate, dgamma, dbeta, C, HW, inv_count, relu, relu_mask, ws, (pfst_bn_order() >> 2) & 1, dx_amax, post_scale);
-  } else {
-    if (!fused)
-      hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(splits, C, N), dim3(256), 0, s, dy, dy_bs, y, y_bs, x, x_bs, mean, invstd, gamma,
-                         beta, HW, chunk, relu, relu_mask, ws, (pfst_bn_order() >> 1) & 1, post_scale, det);
-    if (!fused && det) hipLaunchKernelGGL(bn_det_sum_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, det, N * splits, C, ws);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(gx, C, N), dim3(256), 0, s, dy, dy_bs, y, y_bs, x, x_bs, mean, invstd, gamma, beta,
-                       dx, dx_bs, dres, dres_bs, dres_accumulate, dgamma, dbeta, C, HW, inv_count, relu, relu_mask, ws, (pfst_bn_order() >> 2) & 1, dx_amax, post_scale);
-  }
+  hipLaunchKernelGGL(vec ? bn_bwd_apply_kernel<true> : bn_bwd_apply_kernel<false>, dim3(gx, C, N), dim3(256), 0, s, dy, dy_bs, y, y_bs, x,
+                     x_bs, mean, invstd, gamma, beta, dx, dx_bs, dres, dres_bs, dres_accumulate, dgamma, dbeta, C, HW,
+                     1.0 / ((double)N * HW), relu, relu_mask, ws, (pfst_bn_order() >> 2) & 1, dx_amax, post_scale);
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }
@@ -816,8 +734,7 @@ extern "C" int pfst_bn_backward_dual(const float* dy, long long dy_bs, const uns
   PFST_CHECK_ARG(dy && relu_mask && xa && mean_a && invstd_a && gamma_a && dxa && ws_a && xb && mean_b && invstd_b && gamma_b && dxb && ws_b);
   PFST_CHECK_ARG(ws_a != ws_b && dxa != dxb && N > 0 && C > 0 && HW > 0 && C <= 65535 && N <= 65535);
   PFST_CHECK_ARG(!bwd_partials_a || bwd_slots_a > 0);
-  if (pfst_deterministic() || HW % 256 != 0 || ((dy_bs | xa_bs | xb_bs | dxa_bs | dxb_bs) & 3) != 0 ||
-      (((uintptr_t)dy | (uintptr_t)xa | (uintptr_t)xb | (uintptr_t)dxa | (uintptr_t)dxb) & 15) != 0) {
+  if (pfst_deterministic() || HW % 256 != 0 || !bn_vec_route(HW, {dy_bs, xa_bs, xb_bs, dxa_bs, dxb_bs}, {dy, xa, xb, dxa, dxb})) {
     pfst_set_error(__FILE__, __LINE__, "dual BatchNorm backward needs HW % 256 == 0, 16-byte aligned planes and the default (atomic) reductions: "
                                        "run the two layers through pfst_bn_backward");
     return PFST_ERR_UNSUPPORTED;
@@ -825,17 +742,15 @@ extern "C" int pfst_bn_backward_dual(const float* dy, long long dy_bs, const uns
   hipStream_t s = (hipStream_t)stream;
   const BnDualSide a{xa, (i64)xa_bs, mean_a, invstd_a, gamma_a, dxa, (i64)dxa_bs, dgamma_a, dbeta_a, ws_a, dxa_amax};
   const BnDualSide b{xb, (i64)xb_bs, mean_b, invstd_b, gamma_b, dxb, (i64)dxb_bs, dgamma_b, dbeta_b, ws_b, dxb_amax};
-  int splits, chunk;
-  split_for(HW, C, N, splits, chunk);
   if (hipMemsetAsync(ws_b, 0, sizeof(double) * 2 * C, s) != hipSuccess) return PFST_ERR_LAUNCH;
   if (bwd_partials_a) {
     // layer a's sums came out of the launch that completed dL/dout (pfst_bnb_fuse_t): only layer b's reduction reads the tensors
-    const float* none = nullptr;
-    double* nodet = nullptr;
     hipLaunchKernelGGL(bn_bwd_partials_kernel, dim3(C), dim3(256), 0, s, bwd_partials_a, bwd_slots_a, mean_a, invstd_a, ws_a);
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(splits, C, N), dim3(256), 0, s, dy, (i64)dy_bs, none, (i64)0, xb, (i64)xb_bs, mean_b, invstd_b,
-                       gamma_b, none, HW, chunk, 1, relu_mask, ws_b, (pfst_bn_order() >> 1) & 1, none, nodet);
+    if (const int err = bn_bwd_reduce(s, false, true, dy, dy_bs, nullptr, 0, xb, xb_bs, mean_b, invstd_b, gamma_b, nullptr, N, C, HW, 1, relu_mask, ws_b, nullptr))
+      return err;
   } else {
+    int splits, chunk;
+    split_for(HW, C, N, splits, chunk);
     if (hipMemsetAsync(ws_a, 0, sizeof(double) * 2 * C, s) != hipSuccess) return PFST_ERR_LAUNCH;
     hipLaunchKernelGGL(bn_bwd_reduce_dual_kernel, dim3(splits, C, N), dim3(256), 0, s, dy, (i64)dy_bs, relu_mask, a, b, HW, chunk,
                        (pfst_bn_order() >> 1) & 1);
@@ -853,26 +768,11 @@ extern "C" int pfst_bn_backward_sums(const float* dy, long long dy_bs, const flo
   PFST_CHECK_ARG(dy && x && mean && invstd && gamma && beta && ws && rec && N > 0 && C > 0 && HW > 0 && C <= 65535 && N <= 65535);
   PFST_CHECK_ARG(!bwd_partials || bwd_slots > 0);
   hipStream_t s = (hipStream_t)stream;
-  if (bwd_partials) {
+  if (bwd_partials)
     hipLaunchKernelGGL(bn_bwd_partials_kernel, dim3(C), dim3(256), 0, s, bwd_partials, bwd_slots, mean, invstd, ws);
-  } else {
-    if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * C, s) != hipSuccess) return PFST_ERR_LAUNCH;
-    int splits, chunk;
-    split_for(HW, C, N, splits, chunk);
-    const bool vec = (HW & 3) == 0 && ((dy_bs | x_bs) & 3) == 0 && (((uintptr_t)dy | (uintptr_t)x) & 15) == 0;
-    const float* none = nullptr;
-    const unsigned long long* nomask = nullptr;
-    bool det_ok;
-    double* const det = bn_det_part(C, N, splits, s, det_ok);
-    PFST_CHECK_DET(det_ok);
-    if (vec)
-      hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(splits, C, N), dim3(256), 0, s, dy, (i64)dy_bs, none, (i64)0, x, (i64)x_bs, mean, invstd, gamma,
-                         beta, HW, chunk, 1, nomask, ws, (pfst_bn_order() >> 1) & 1, none, det);
-    else
-      hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(splits, C, N), dim3(256), 0, s, dy, (i64)dy_bs, none, (i64)0, x, (i64)x_bs, mean, invstd, gamma,
-                         beta, HW, chunk, 1, nomask, ws, (pfst_bn_order() >> 1) & 1, none, det);
-    if (det) hipLaunchKernelGGL(bn_det_sum_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, det, N * splits, C, ws);
-  }
+  else if (const int err = bn_bwd_reduce(s, true, bn_vec_route(HW, {dy_bs, x_bs}, {dy, x}), dy, dy_bs, nullptr, 0, x, x_bs, mean, invstd, gamma, beta,
+                                         N, C, HW, 1, nullptr, ws, nullptr))
+    return err;
   hipLaunchKernelGGL(bn_bwd_rec_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, ws, mean, invstd, gamma, beta, dgamma, dbeta, C,
                      1.0 / ((double)N * HW), rec);
   PFST_CHECK_LAUNCH();

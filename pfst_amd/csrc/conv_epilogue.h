@@ -217,7 +217,8 @@ __device__ __forceinline__ void conv_epilogue(pfst_f32x16 (&acc)[TM][TN], float*
     const int row0 = m0 + wm0;
     const bool gated = gsrc != nullptr;
     // what is added to a 32x32 block: the old values of `out`, or the gated tensor (16 loads issued back to back: one latency per block).
-    // Gate bits: the 64 pixel columns of a wave tile start at a multiple of 64, so a lane's bits for both column blocks (pixel pp and
+    // Gate bits (layout: relu_mask_plane / relu_mask_word in bn_bwd.h, restated by hand in mvoff below): the 64 pixel columns of a wave
+    // tile start at a multiple of 64, so a lane's bits for both column blocks (pixel pp and
     // pp + 32: bit + 8) sit in the SAME 32-bit half of the same mask word -- one 4-byte load per accumulator row serves the row's two
     // blocks, and a sign-extending bit-field extract turns the bit into an AND mask (two vector instructions per element).
     static_assert(TN <= 2, "the gate words are shared by the column blocks of a 64-pixel wave tile");

@@ -14,6 +14,7 @@
 #include <initializer_list>
 #include <type_traits>
 #include "common.h"
+#include "bn_bwd.h"
 #include "../../include/pfst_hip.h"
 
 namespace {
@@ -64,14 +65,14 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ plane, floa
   }
 }
 
-// the second pass of BatchNorm backward for one element, exactly as bn_bwd_apply_kernel evaluates it (ReLU gate recomputed from the
-// pre-normalisation value like bn_apply decided it, projections subtracted in fp64)
+// the second pass of BatchNorm backward for one element: the ReLU gate recomputed from the pre-normalisation value like bn_apply decided
+// it, then bn_bwd_dx (bn_bwd.h), the one projection that bn_bwd_apply_kernel calls as well
 __device__ __forceinline__ float bn_bwd_elem(float g, float xv, const pfst_bn_bwd_rec_t& r) {
   const float dz = __fmaf_rn(xv, r.sc, r.sh) > 0.f ? g : 0.f;
 #ifdef PFST_DIAG_DW_F32
   return (float)r.gs * (dz - (float)r.m1 - ((xv - r.mu) * r.is) * (float)r.m2);
 #endif
-  return (float)(r.gs * ((double)dz - r.m1 - (((double)xv - (double)r.mu) * (double)r.is) * r.m2));
+  return bn_bwd_dx(dz, xv, r);
 }
 __device__ __forceinline__ float4 bn_bwd_elem4(float4 g, float4 xv, const pfst_bn_bwd_rec_t& r) {
   return make_float4(bn_bwd_elem(g.x, xv.x, r), bn_bwd_elem(g.y, xv.y, r), bn_bwd_elem(g.z, xv.z, r), bn_bwd_elem(g.w, xv.w, r));

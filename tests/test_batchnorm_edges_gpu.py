@@ -9,7 +9,7 @@ rsh)]) [* post[n, c]]; gradients by the closed form dx = gs (dz - m1 - xhat m2),
 backward launch is an INPUT of that launch, so its reference is built with gate = (y_kernel > 0), the tensor bn_apply wrote: no element near
 zero has to be excluded anywhere.  The forward test asserts separately that y is within its bound everywhere, that (y_kernel > 0) agrees
 with (z_ref > 0) wherever |z_ref| exceeds that element's bound, and that the mask bits are exactly y_kernel > 0 in the layout documented in
-bn_apply_kernel.  N = 3, C = 5 (N != C, neither 1) and every per-channel vector differs per channel and per image; gamma is negative on odd
+csrc/bn_bwd.h.  N = 3, C = 5 (N != C, neither 1) and every per-channel vector differs per channel and per image; gamma is negative on odd
 channels; post is 0 on four of the fifteen planes and 1 / 0.9 elsewhere, in a pattern that is symmetric neither in n nor in c.
 
 Bounds, element-wise: mean |err| <= 2^-23 |ref| + 1e-10, invstd 2^-23 relative, running statistics 1e-5 (as test_batchnorm_train);
@@ -18,7 +18,7 @@ y, dx, dgamma, dbeta and the (m1, m2) record: K 2^-24 M_i with M_i the sum of th
 bn_apply on the vector and on the scalar path of the same data: bit for bit.  fp64 sums read back from the scratch: slot_sum_bound.
 
 Path conditions pinned here ("Path conditions of the BatchNorm entries"): per plane in bn_stats_kernel / bn_apply_kernel, per
-launch on the host in pfst_bn_backward / _backward_sums / _backward_dual, repeated in Python by hip_ops.bn_apply / bn_backward_dual for the
+launch on the host (bn_vec_route) in pfst_bn_backward / _backward_sums / _backward_dual, repeated in Python by hip_ops.bn_apply / bn_backward_dual for the
 mask.  In deterministic mode the two routes of one launch differ in the order of their fp64 sums, which the tests read back from the 'bn'
 scratch and from the record: every call with ONE misaligned operand must give the scalar route's bits (test_f_deterministic_routes plants a
 cancelling pair per channel so that the two orders differ by construction), and the slots are added in (image, chunk) order.
@@ -34,9 +34,9 @@ PFST_ERR_UNSUPPORTED and the caller is promised None (test_e_dual_declines[12-21
 Mutations of csrc/bn.hip tried against this file on the MI355X, each on its own (none committed):
   1. `post[n * C + c]` -> `post[c]` in bn_apply_kernel: test_b_apply_options, test_b_backward_options (their forward), every
      test_c_apply_on_views case (the post launch) fail.
-  2. `bxi` -> `blockIdx.x` for `beg` in bn_bwd_reduce_kernel: every chunk is still summed once, so only deterministic mode's slot order moves
-     (chunks of an image from the other end): test_f_deterministic_slot_order fails at both shapes on `bn_backward: slots out of order`.
-  3. `dres_bs` dropped from `vec` in pfst_bn_backward: the float4 kernels run on dres planes 4 and 8 bytes past alignment, the values stay
+  2. `b.bx` (then `bxi`) -> `blockIdx.x` for `beg` in bn_bwd_reduce_kernel: every chunk is still summed once, so only deterministic mode's slot
+     order moves (chunks of an image from the other end): test_f_deterministic_slot_order fails at both shapes on `bn_backward: slots out of order`.
+  3. `dres_bs` dropped from `vec` (now the operands handed to bn_vec_route) in pfst_bn_backward: the float4 kernels run on dres planes 4 and 8 bytes past alignment, the values stay
      right; test_f_deterministic_routes fails on `bn_backward with a misaligned dres (odd) did not take the scalar route`, nothing else notices.
   4. `y_bs` -> `(i64)C * HW` for `yp` in bn_apply_kernel: all test_c_apply_on_views cases with the output (or all operands) as a view fail
      (canaries written, y wrong); the writes stay inside the canary buffer, whose batch stride is at least C * HW.
@@ -251,7 +251,7 @@ def check_stats(mean, invstd, mean_ref, invstd_ref, what=''):
 
 
 def mask_bits(mask, N, C, HW):
-    """-> bool [N, C, HW] from the words of bn_apply's bitmask, layout as documented in bn_apply_kernel: the 256-element group q of a plane
+    """-> bool [N, C, HW] from the words of bn_apply's bitmask, layout as documented in csrc/bn_bwd.h: the 256-element group q of a plane
     has 4 words; word k, bit l <-> element 256 q + 4 l + k"""
     words = mask.cpu().numpy().view(np.uint64).reshape(N * C, HW // 256, 4)
     bits = ((words[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool)          # [plane][q][k][l]
@@ -787,6 +787,56 @@ def test_e_dual(ops, H, W, amax, partials):
         if amax:
             amax_is(sides[k]['amax'], dx, what)
     report()
+
+
+# (N, C, H, W), chunks per plane: every channel's fp64 sums have at most two addends into a zeroed ws (N * chunks <= 2), so the order of the
+# atomics cannot matter (0 + a is exact, a + b commutes) and the default mode's sums are reproducible bit for bit
+DUAL_EQ = [((2, 5, 16, 16), 1),        # one mask group per plane
+           ((2, 5, 32, 32), 1),        # HW = 1024
+           ((1, 5, 32, 64), 2)]        # two chunks per plane, walked in reversed order
+
+
+@pytest.mark.parametrize('partials', [False, True])
+@pytest.mark.parametrize('shape,chunks', DUAL_EQ)
+def test_e_dual_equals_two_single_layers(ops, shape, chunks, partials):
+    """bn_backward_dual == two bn_backward(mask=...) calls BIT FOR BIT: dx, dgamma, dbeta, the published maximum and the fp64 sums in ws, with
+    and without side a's sums arriving as partials, dy / xa / xb as channel slices.  The kernels of both routes take every element's
+    arithmetic from csrc/bn_bwd.h (bn_bwd_dx pins the roundings of the projection) and sum in the same order inside a workgroup; this test
+    holds them to it.  pfst_bn_backward_dual is called through the C ABI with a scratch of the test's own, so that ws can be read back (the
+    wrapper allocates and drops it)."""
+    N, C, H, W = shape
+    HW = H * W
+    assert bn_splits(HW, C, N)[0] == chunks and N * chunks <= 2
+    d = case(H, W, N, C)
+    t = {k: d[k].to(DEV) for k in ('x', 'xb', 'r', 'dy', 'gamma', 'gamma_b', 'beta')}
+    stats = {'a': ops.bn_stats(t['x']), 'b': ops.bn_stats(t['xb'])}
+    y, mask = ops.bn_apply(t['x'], *stats['a'], t['gamma'], t['beta'], True, t['r'], want_mask=True)
+    assert mask is not None
+    dgb = {k: (torch.randn(C, generator=g(70 + i)), torch.randn(C, generator=g(72 + i))) for i, k in enumerate('ab')}
+    o = Operands('slice', ('dy', 'xa', 'xb'), shape)
+    dyv, xv = o.src('dy', t['dy']), {'a': o.src('xa', t['x']), 'b': o.src('xb', t['xb'])}
+    gam = {'a': t['gamma'], 'b': t['gamma_b']}
+    part = slot_partials(d['dy'].double() * (y > 0).cpu(), d['x']).to(DEV) if partials else None
+    single = {}
+    for k in 'ab':
+        dg, db, am = dgb[k][0].to(DEV), dgb[k][1].to(DEV), ops.amax_slots(dyv.device)
+        kw = dict(partials=part, slots=N * 4) if partials and k == 'a' else {}
+        dx = ops.bn_backward(dyv, None, xv[k], *stats[k], gam[k], dg, db, True, mask=mask, amax=am, **kw)
+        single[k] = dict(dx=dx, dgamma=dg, dbeta=db, amax=float(am.max()), ws=bn_ws(ops, C))
+    dual = {k: dict(dx=torch.full(shape, SENT, device=DEV), dgamma=dgb[k][0].to(DEV), dbeta=dgb[k][1].to(DEV), amax=ops.amax_slots(dyv.device),
+                    ws=torch.full((C, 2), SENT, dtype=torch.float64, device=DEV)) for k in 'ab'}
+    A, B = dual['a'], dual['b']
+    ops.call('pfst_bn_backward_dual', dyv.data_ptr(), ops._bs(dyv), mask.data_ptr(),
+             xv['a'].data_ptr(), ops._bs(xv['a']), stats['a'][0].data_ptr(), stats['a'][1].data_ptr(), gam['a'].data_ptr(), A['dx'].data_ptr(), C * HW,
+             A['dgamma'].data_ptr(), A['dbeta'].data_ptr(), A['ws'].data_ptr(), ops._p(part), N * 4 if partials else 0, A['amax'].data_ptr(),
+             xv['b'].data_ptr(), ops._bs(xv['b']), stats['b'][0].data_ptr(), stats['b'][1].data_ptr(), gam['b'].data_ptr(), B['dx'].data_ptr(), C * HW,
+             B['dgamma'].data_ptr(), B['dbeta'].data_ptr(), B['ws'].data_ptr(), B['amax'].data_ptr(), N, C, HW, ops._stream())
+    o.check('bn_backward_dual')
+    for k in 'ab':
+        what = f'side {k} of {shape}, partials={partials}'
+        for f in ('ws', 'dgamma', 'dbeta', 'dx'):
+            assert torch.equal(dual[k][f], single[k][f]), f'{what}: {f} differs from the single-layer call'
+        assert float(dual[k]['amax'].max()) == single[k]['amax'] == float(single[k]['dx'].abs().max()), what + ': published maximum'
 
 
 @pytest.mark.parametrize('H,W,bad', [(32, 32, 'dy'), (32, 32, 'xa'), (32, 32, 'xb'), (12, 21, None)])
