@@ -643,6 +643,44 @@ int pfst_sigloss_upsample_bwd(const float* logits, int N, int C, int h, int w, c
                               int H, int W, int ignore_index, const float* coef, float gamma, int form, float scale, float* dlogits,
                               int accumulate, pfst_stream_t stream);
 
+/* ---- fused bilinear upsample + softmax + Lovasz-Softmax loss (losses/lovasz_loss.py behind decode_head.py:249-283), csrc/lovasz_loss.hip ----
+ * The class set is `slot` (int [C] on the device: the class's slot 0 .. K-1, or -1) and `cls` (int [K]: the class of a slot).  Segments: one
+ * per slot over the batch (per_image = 0: K segments of N*H*W elements) or one per (image, slot) (per_image = 1: N*K segments of H*W).
+ * workspace: pfst_lovasz_workspace_bytes(segments, elements per segment) bytes, 16-byte aligned, any contents; it carries the (key, value)
+ * ping-pong buffers, the digit histograms and the per-tile partials from pfst_lovasz_keys to pfst_lovasz_finalize.
+ * counters: 3 + N*K 64-bit words = (#correct, #valid, #bad labels, foreground count per (image, slot)), zeroed by pfst_lovasz_keys. */
+int pfst_lovasz_workspace_bytes(int segments, long long seg_stride, long long* bytes);
+/* The sort on its own: a stable ascending LSD radix sort (8-bit digits, 4 passes) of 32-bit keys in `segments` independent segments; segment
+ * s holds elements [s*seg_stride, s*seg_stride + len_s), len_s = seg_len[s] (device int [segments], clamped to [0, seg_stride]; NULL: every
+ * segment is full).  vals_in NULL: the value of an element is its index in its segment (vals_out is then the permutation).  Equal keys keep
+ * their input order; elements at and beyond len_s of the outputs are not written.  keys_out == keys_in (and vals) is allowed. */
+int pfst_lovasz_sort(const unsigned int* keys_in, const unsigned int* vals_in, int segments, long long seg_stride, const int* seg_len,
+                     void* workspace, unsigned int* keys_out, unsigned int* vals_out, pfst_stream_t stream);
+/* key pass: acc_seg / bad-label counts, the log-sum-exp map (exactly one of lse_in / lse_out [N][H][W], as pfst_dice_upsample_fwd) and, per
+ * slot and pixel, key = 0x3F800000 - bits(e), e = |fg - min(p_c, 1)| (0x3F800001 where label == ignore_index: behind every valid key) and
+ * value = pixel index in the segment (n, y, x order) | foreground << 31, into the workspace.  form: as pfst_dice_upsample_fwd. */
+int pfst_lovasz_keys(const float* logits, int N, int C, int h, int w, const unsigned char* label, int H, int W, int ignore_index,
+                     int form, const int* slot, int K, int per_image, const float* lse_in, float* lse_out, void* workspace,
+                     long long* counters, pfst_stream_t stream);
+/* sorts the workspace's segments in place (descending error, equal errors by ascending pixel index) */
+int pfst_lovasz_sort_keys(int N, int H, int W, int K, int per_image, void* workspace, pfst_stream_t stream);
+/* over the sorted order: g_k = J_k - J_{k-1} (lovasz_grad), coef_map[N][K][H][W] = sign(fg - p) * slot_weight[slot] * g_k at valid pixels
+ * (others are not written), and the per-tile fp64 partials of sum e_k g_k, in a fixed order (no atomics).  slot_weight: float [K] or NULL */
+int pfst_lovasz_grad(int N, int H, int W, int K, int per_image, const long long* counters, const float* slot_weight, void* workspace,
+                     float* coef_map, pfst_stream_t stream);
+/* sums[segments] = sum e_k g_k per segment; the class mean over the kept slots (mode_present: those with foreground among the segment's valid
+ * pixels), per image when per_image (reduction 0: mean over N, 1: sum); no kept slot: 0.  scale[N][K] = what the backward multiplies
+ * coef_map with (0 for a skipped slot); out[3] = (loss_weight * loss, acc_seg %, #bad labels) laid out as pfst_ce_finalize's */
+int pfst_lovasz_finalize(int N, int H, int W, int K, int per_image, int mode_present, int reduction, const long long* counters,
+                         const float* slot_weight, double loss_weight, void* workspace, double* sums, float* scale, float* out,
+                         pfst_stream_t stream);
+/* dlogits (+)= grad_scale * adjoint of the resize applied to p_j (d_j - sum_c d_c p_c), d_c = -scale[n][slot] coef_map[n][slot][pixel]
+ * (0 outside the class set), zero at pixels with label == ignore_index; gather form, no atomics.  work[N][H][W]: generic form at C > 8 only */
+int pfst_lovasz_upsample_bwd(const float* logits, int N, int C, int h, int w, const unsigned char* label, int H, int W,
+                             int ignore_index, int form, const int* slot, const int* cls, int K, const float* lse,
+                             const float* coef_map, const float* scale, float grad_scale, float* work, float* dlogits,
+                             int accumulate, pfst_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ import torch
 
 from ._lib import call, lib
 
-F32, U8, I64, F64 = torch.float32, torch.uint8, torch.int64, torch.float64
+F32, U8, I64, F64, I32 = torch.float32, torch.uint8, torch.int64, torch.float64, torch.int32
 
 
 def _stream():
@@ -1440,6 +1440,120 @@ def sigloss_upsample_bwd(logits, label_u8, coef, scale, gamma=0.0, pix_weight=No
     form, _ = sigloss_form(logits, label_u8, pix_weight, generic)
     call('pfst_sigloss_upsample_bwd', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), _p(pix_weight), H, W, int(ignore_index),
          coef.data_ptr(), float(gamma), form, float(scale), _dense(out).data_ptr(), int(accumulate), _stream())
+    return out
+
+
+def lovasz_form(logits, label_u8, lse=None, generic=False):
+    """which kernels a Lovasz term's key and backward passes run on, by dice_form's rules -> 4 / 8 (block frames) or 0 (generic)"""
+    return _blocks_form(logits, label_u8, lse, generic)[0]
+
+
+def lovasz_workspace(segments, seg_stride, dev):
+    """the workspace of `segments` segments of `seg_stride` elements: ping-pong (key, value) buffers, digit histograms, per-tile partials"""
+    nbytes = ctypes.c_longlong(0)
+    call('pfst_lovasz_workspace_bytes', int(segments), int(seg_stride), ctypes.addressof(nbytes))
+    return torch.empty((nbytes.value + 15) // 16 * 2, dtype=I64, device=dev)
+
+
+def lovasz_sort(keys, seg_len=None, vals=None, out=None):
+    """pfst_lovasz_sort: the stable ascending radix sort of the 32-bit patterns in keys (int32 [S, stride], read as unsigned), segment by
+    segment; seg_len: int32 [S] on the device (None: full segments); vals: int32 [S, stride] carried along (None: the index in the segment,
+    so that the second result is the permutation).  out: (keys_out, vals_out) to write into.  Elements at and beyond a segment's length
+    are not written.  -> (keys_out, vals_out)"""
+    _dense(_chk(keys, I32, 2), I32)
+    s, stride = keys.shape
+    if seg_len is not None and tuple(_dense(seg_len, I32).shape) != (s,):
+        raise ValueError(f'lovasz_sort: seg_len {tuple(seg_len.shape)} for {s} segments')
+    if vals is not None and _dense(vals, I32).shape != keys.shape:
+        raise ValueError('lovasz_sort: vals must have the shape of keys')
+    ko, vo = out if out is not None else (torch.empty_like(keys), torch.empty_like(keys))
+    if _dense(ko, I32).numel() < keys.numel() or _dense(vo, I32).numel() < keys.numel():
+        raise ValueError('lovasz_sort: output buffers are smaller than the keys')
+    ws = lovasz_workspace(s, stride, keys.device)
+    call('pfst_lovasz_sort', keys.data_ptr(), _p(vals), s, stride, _p(seg_len), ws.data_ptr(), ko.data_ptr(), vo.data_ptr(), _stream())
+    return ko, vo
+
+
+def lovasz_class_tables(classes, num_classes, dev):
+    """classes: 'all' | 'present' | a list of class indices -> (slot int32 [C]: the class's slot or -1, cls int32 [K]: the class of a slot)"""
+    cls = list(range(num_classes)) if classes in ('all', 'present') else [int(c) for c in classes]
+    if not cls or any(not 0 <= c < num_classes for c in cls) or len(set(cls)) != len(cls):
+        raise ValueError(f'LovaszLoss: classes {classes!r} must be distinct class indices in [0, {num_classes})')
+    slot = [-1] * num_classes
+    for k, c in enumerate(cls):
+        slot[c] = k
+    return torch.tensor(slot, dtype=I32, device=dev), torch.tensor(cls, dtype=I32, device=dev)
+
+
+def lovasz_upsample_fwd(logits, label_u8, slot, cls, slot_weight=None, ignore_index=255, per_image=False, present=True, reduction='mean',
+                        loss_weight=1.0, lse=None, generic=False, want_sorted=False, stage_hook=None):
+    """The Lovasz-Softmax loss of softmax(up(logits)) (csrc/lovasz_loss.hip): key pass, segmented radix sort, gradient pass, finalize -- four
+    ABI calls on the current stream, nothing read on the host.  slot / cls: lovasz_class_tables; slot_weight: float [K] (the class weights
+    by slot) or None; reduction ('mean' | 'sum') counts with per_image only.  lse: a CE / Dice term's log-sum-exp (None: formed here).
+    stage_hook(name): called after each stage's launches (tools/lovasz_bench.py records events there).
+    -> dict(out float32[3] = (loss, acc_seg %, #bad labels), map float [N, K, H, W] (unwritten where label == ignore_index), scale float
+    [N, K], lse, sums float64 [segments], counters int64 [3 + N K], form[, keys, vals: int32 [segments, L], the sorted order])"""
+    _dense(logits), _dense(label_u8, U8)
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    k = cls.numel()
+    if label_u8.numel() != n * H * W or tuple(_dense(slot, I32).shape) != (c,) or not 1 <= _dense(cls, I32).numel() <= c:
+        raise ValueError(f'lovasz_upsample_fwd: logits {tuple(logits.shape)}, labels {tuple(label_u8.shape)}, {k} slots')
+    if slot_weight is not None and tuple(_dense(slot_weight).shape) != (k,):
+        raise ValueError(f'lovasz_upsample_fwd: slot_weight {tuple(slot_weight.shape)} for {k} slots')
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f'lovasz_upsample_fwd: reduction {reduction!r}')
+    dev = logits.device
+    own = lse is None
+    if own:
+        lse = torch.empty(n, H, W, device=dev)
+    else:
+        assert _dense(lse).numel() == n * H * W
+    form = lovasz_form(logits, label_u8, lse, generic)
+    pi = int(bool(per_image))
+    segs, seg_len = (n * k, H * W) if pi else (k, n * H * W)
+    ws = lovasz_workspace(segs, seg_len, dev)
+    counters = torch.empty(3 + n * k, dtype=I64, device=dev)
+    cmap = torch.empty(n, k, H, W, device=dev)
+    sums = torch.empty(segs, dtype=F64, device=dev)
+    scale = torch.empty(n, k, device=dev)
+    out = torch.empty(3, device=dev)
+    hook = stage_hook if stage_hook is not None else (lambda name: None)
+    call('pfst_lovasz_keys', logits.data_ptr(), n, c, h, w, label_u8.data_ptr(), H, W, int(ignore_index), form, slot.data_ptr(), k, pi,
+         0 if own else lse.data_ptr(), lse.data_ptr() if own else 0, ws.data_ptr(), counters.data_ptr(), _stream())
+    hook('keys')
+    call('pfst_lovasz_sort_keys', n, H, W, k, pi, ws.data_ptr(), _stream())
+    hook('sort')
+    call('pfst_lovasz_grad', n, H, W, k, pi, counters.data_ptr(), _p(slot_weight), ws.data_ptr(), cmap.data_ptr(), _stream())
+    hook('grad')
+    call('pfst_lovasz_finalize', n, H, W, k, pi, int(bool(present)), int(reduction == 'sum'), counters.data_ptr(), _p(slot_weight),
+         float(loss_weight), ws.data_ptr(), sums.data_ptr(), scale.data_ptr(), out.data_ptr(), _stream())
+    hook('finalize')
+    res = dict(out=out, map=cmap, scale=scale, lse=lse, sums=sums, counters=counters, form=form)
+    if want_sorted:
+        nel = segs * seg_len
+        pad = (nel * 4 + 15) // 16 * 16 // 4                # the workspace's buffers are 16-byte aligned: keys A, then values A
+        flat = ws.view(I32)
+        res['keys'] = flat[:nel].view(segs, seg_len).clone()
+        res['vals'] = flat[pad:pad + nel].view(segs, seg_len).clone()
+    return res
+
+
+def lovasz_upsample_bwd(logits, label_u8, slot, cls, lse, cmap, scale, grad_scale, ignore_index=255, out=None, accumulate=False, generic=False):
+    """d logits of the Lovasz term (gather form, no atomics); `grad_scale` carries loss_weight and the step's gradient scale"""
+    n, c, h, w = logits.shape
+    H, W = label_u8.shape[-2:]
+    k = cls.numel()
+    if out is None:
+        assert not accumulate
+        out = torch.empty_like(logits)
+    assert tuple(_dense(cmap).shape) == (n, k, H, W) and tuple(_dense(scale).shape) == (n, k) and _dense(lse).numel() == n * H * W
+    assert tuple(_dense(slot, I32).shape) == (c,) and out.shape == logits.shape
+    form = lovasz_form(logits, label_u8, lse, generic)
+    work = torch.empty(n, H, W, device=logits.device) if form == 0 and c > 8 else None
+    call('pfst_lovasz_upsample_bwd', _dense(logits).data_ptr(), n, c, h, w, _dense(label_u8, U8).data_ptr(), H, W, int(ignore_index), form,
+         slot.data_ptr(), _dense(cls, I32).data_ptr(), k, lse.data_ptr(), cmap.data_ptr(), scale.data_ptr(), float(grad_scale), _p(work),
+         _dense(out).data_ptr(), int(accumulate), _stream())
     return out
 
 

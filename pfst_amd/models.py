@@ -375,6 +375,87 @@ class DiceLoss(nn.Module):
         return out
 
 
+class LossConfigError(ValueError, KeyError):
+    """a loss config whose keys contradict each other.  A ValueError like every refused option; also a KeyError, what a config that names
+    `type='LovaszLoss'` without `reduction='none'` has always failed with at build time (the registry's, before the term was built):
+    callers and tests that catch either keep working."""
+
+    __str__ = ValueError.__str__          # (KeyError's would quote the message)
+
+
+@LOSSES.register_module()
+class LovaszLoss(nn.Module):
+    """losses/lovasz_loss.py (the multi-class Lovasz-Softmax form) fused with the bilinear up-sampling of the logits (csrc/lovasz_loss.hip;
+    the algorithm: DESIGN.md section 8m).  Per class c of the class set, over the pixels whose label differs from the HEAD's ignore_index:
+    errors |fg - p_c|, their descending order, lovasz_grad of the sorted foreground flags, the dot product, times class_weight[c]; the mean over
+    the classes kept ('present': those with foreground among the valid pixels, 'all', or a list of class indices).  per_image: one value per
+    image, then `reduction` ('none' is logged as the mean of the N values, as _parse_losses takes it).  As executed by the reference the
+    head's `weight=` is swallowed (pixel weights have no effect) and a label outside [0, C) other than ignore_index is a valid pixel that is
+    foreground for no class (it is counted in #bad labels like everywhere).
+    Deviations: loss_type='binary' (the one-channel hinge) is not built; where no pixel is valid -- the batch, one image under per_image (it adds
+    0 and still counts in the divisor N), or 'present' with no class present -- the loss is 0 with a zero gradient (the reference returns an empty
+    tensor or raises); equal errors are ordered by ascending pixel index (n, y, x) where the reference's unstable sort leaves their gradient
+    arbitrary (the loss value does not depend on it); a list of classes must hold distinct indices in [0, C)."""
+
+    def __init__(self, loss_type='multi_class', classes='present', per_image=False, reduction='mean', class_weight=None, loss_weight=1.0,
+                 loss_name='loss_lovasz'):
+        super().__init__()
+        if loss_type not in ('binary', 'multi_class'):
+            raise ValueError("LovaszLoss: loss_type should be 'binary' or 'multi_class'")
+        if loss_type == 'binary':
+            raise NotImplementedError('LovaszLoss: the binary (one-channel hinge) form is not built, multi_class only')
+        if not (classes in ('all', 'present') or (isinstance(classes, (list, tuple)) and len(classes) > 0
+                                                  and all(isinstance(c, int) and not isinstance(c, bool) for c in classes))):
+            raise ValueError(f"LovaszLoss: classes must be 'all', 'present' or a list of ints, got {classes!r}")
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError(f"LovaszLoss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        if not per_image and reduction != 'none':
+            raise LossConfigError("LovaszLoss: reduction should be 'none' when per_image is False")  # lovasz_loss.py:269-271 asserts
+        self.classes = classes if isinstance(classes, str) else list(classes)
+        self.per_image, self.reduction = bool(per_image), reduction
+        self.class_weight = get_class_weight(class_weight)
+        self.loss_weight = loss_weight
+        self._loss_name = loss_name
+        self._tables = None
+
+    loss_name = CrossEntropyLoss.loss_name
+
+    def _class_tables(self, num_classes, dev):
+        """(slot, cls, class weights by slot | None) on the device, built at first use"""
+        if self._tables is None or self._tables[0].device != dev or self._tables[0].numel() != num_classes:
+            if self.class_weight is not None and len(self.class_weight) != num_classes:
+                raise ValueError(f'LovaszLoss: class_weight has {len(self.class_weight)} entries for {num_classes} classes')
+            slot, cls = ops.lovasz_class_tables(self.classes, num_classes, dev)
+            cw = None
+            if self.class_weight is not None:
+                order = range(num_classes) if isinstance(self.classes, str) else self.classes
+                cw = torch.tensor([float(self.class_weight[c]) for c in order], dtype=torch.float32, device=dev)
+            self._tables = (slot, cls, cw)
+        return self._tables
+
+    def fused(self, logits, label_u8, weight, tape, ignore_index=255, grad_scale=1.0, share=None):
+        """the interface of CrossEntropyLoss.fused; `weight` is ignored, `ignore_index` (the head's) selects the valid pixels.
+        -> device tensor [loss, acc_seg, #bad labels]"""
+        ld = logits.data
+        slot, cls, cw = self._class_tables(ld.shape[1], ld.device)
+        ign = 255 if ignore_index is None else ignore_index            # uint8 label maps: 255 = "no class index"
+        r = ops.lovasz_upsample_fwd(ld, label_u8, slot, cls, cw, ign, self.per_image, self.classes == 'present',
+                                    'sum' if self.reduction == 'sum' else 'mean', self.loss_weight,
+                                    lse=None if share is None else share.get('lse'))
+        if share is not None:
+            share['lse'] = r['lse']
+        if tape is not None:
+            scale = grad_scale * self.loss_weight
+            lse, cmap, blk = r['lse'], r['map'], r['scale']           # blk: the kept-class / per-image divisors, on the device
+
+            def bwd():
+                buf, accf = logits.grad_target()
+                ops.lovasz_upsample_bwd(ld, label_u8, slot, cls, lse, cmap, blk, scale, ign, out=buf, accumulate=accf)
+            tape.record(bwd, dict(op='lovasz', x=logits, out=None, label=label_u8, class_weight=self.class_weight, loss_weight=scale,
+                                  ignore_index=ign, classes=self.classes, per_image=self.per_image, reduction=self.reduction))
+        return r['out']
+
+
 @PIXEL_SAMPLERS.register_module()
 class OHEMPixelSampler:
     """core/seg/sampler/ohem_pixel_sampler.py on the device (csrc/ohem.hip): the 0 / 1 map of the hard pixels, from the
