@@ -98,6 +98,11 @@ int pfst_conv_wgrad(const float* x, long long x_bs, const float* dy, long long d
  * 24000 two instead of four workgroups fit per CU (the fp32-MFMA pipe stays saturated: -0.3 % on the step) and an HBM-bound kernel
  * of ANOTHER stream -- the BatchNorm-backward chain, when the host runs weight gradients on a side stream -- can be co-resident. */
 int pfst_conv_wgrad_set_lds_pad(int bytes);
+/* The split-K plan of the weight-gradient launchers (csrc/wgrad_launch.h), host arithmetic only -- no device is touched: a launch of
+ * `work` workgroups (tiles x images x groups) over P pixels is cut into *chunks pixel chunks of *chunk_len (a multiple of k_step; the last
+ * one may be shorter), so that whole rounds of `slots` resident workgroups fill the chip.  chunk_cap > 0: at most that many chunks.
+ * doubling != 0: the doubling rule of the generic bf16x6 weight gradient instead (slots, k_step and chunk_cap are ignored). */
+int pfst_wgrad_split_k(long long work, int P, int slots, int k_step, int chunk_cap, int doubling, int* chunks, int* chunk_len);
 /* db[c] += sum_{n,hw} dy[n][c][hw] */
 int pfst_bias_grad(const float* dy, long long dy_bs, float* db, int N, int C, int HW, pfst_stream_t stream);
 

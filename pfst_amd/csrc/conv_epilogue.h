@@ -3,6 +3,7 @@
 // row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) (output channel).
 #pragma once
 #include <type_traits>
+#include <utility>
 #include "common.h"
 #ifndef PFST_BNB_LOAD_AUX
 #define PFST_BNB_LOAD_AUX 0      // cache policy of the fused BatchNorm-backward epilogue's x / y loads (read once): A/B builds
@@ -10,6 +11,25 @@
 #include "../../include/pfst_hip.h"
 
 typedef float pfst_f32x16 __attribute__((ext_vector_type(16)));
+
+// source coordinate of output index o for tap t: (o*a + t*b + c0) / div, div in {1,2}; branch-free validity.  (a, b, c0, div) come from
+// conv_geometry (conv_launch.h): forward (stride, dil, -pad, 1), data gradient (1, -dil, pad, stride).
+__device__ __forceinline__ bool src_coord(int o, int t, int a, int b, int c0, int div, int lim, int& s) {
+  const int v = o * a + t * b + c0;
+  const int odd = v & (div - 1);
+  s = v >> (div >> 1);
+  return (odd == 0) & (s >= 0) & (s < lim);
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), always unrolled: the pinned instruction schedules of the pipelined K loops
+template <int... Is, class F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, Is...>, F&& f) {
+  (f(std::integral_constant<int, Is>()), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(std::make_integer_sequence<int, N>(), static_cast<F&&>(f));
+}
 
 // Fused BatchNorm-BACKWARD statistics (data-gradient launches).  When the tensor this launch writes is the COMPLETE gradient dL/dy
 // of a conv -> BN(train) -> [+res] -> ReLU layer's output y (the launch is the last writer into that gradient buffer), the epilogue

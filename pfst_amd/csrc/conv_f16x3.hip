@@ -17,7 +17,7 @@
 // on the bf16x6 or fp32-input MFMA kernels.
 #include "conv_epilogue.h"
 #include "amax.h"
-#include "det.h"
+#include "wgrad_launch.h"
 #include "weight_jobs.h"
 #include <math.h>
 #include <stdlib.h>
@@ -32,22 +32,6 @@ namespace {
 
 constexpr int BN = 128;
 constexpr int NP = 2;      // pieces: 0 = h (high 11 bits), 1 = l (next 11 bits)
-
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>()), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_seq(std::make_integer_sequence<int, N>(), static_cast<F&&>(f));
-}
-
-__device__ __forceinline__ bool src_coord(int o, int t, int a, int b, int c0, int div, int lim, int& s) {
-  const int v = o * a + t * b + c0;
-  const int odd = v & (div - 1);
-  s = v >> (div >> 1);
-  return (odd == 0) & (s >= 0) & (s < lim);
-}
 
 // ---- absolute maximum of a tensor into its slot group (amax.h)
 __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, i64 n, i64 plane_stride, int slot_stride,
@@ -1034,7 +1018,8 @@ extern "C" int pfst_conv_igemm_f16x3(const float* in, long long in_bs, const voi
   }
   PFST_CHECK_ARG(!bnb || (bnb->x && bnb->x_bs >= (i64)M * Ho * Wo && (!bnb->y || bnb->y_bs >= (i64)M * Ho * Wo)));
   PFST_CHECK_ARG(!bnb || !bnb->y_mask || (bnb->y && bnb->relu && ((i64)Ho * Wo) % 256 == 0));      // the gate bits of a residual layer's y
-  PFST_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && dil >= 1 && pad >= 0 && (mode == 0 || mode == 1));
+  ConvGeom g;
+  if (const int rc = conv_geometry(Hi, Wi, Ho, Wo, ksize, stride, dil, pad, mode, g)) return rc;
   PFST_CHECK_ARG(in_bs >= (i64)C * Hi * Wi && out_bs >= (i64)M * Ho * Wo && N <= 65535);
   // 32-bit buffer ranges and offsets (the out-of-range marker 0x80000000 is ADDED to them): one image of either operand and the weight
   // image must stay below 2 GB, as in pfst_wino_gemm_f16x3 / pfst_conv_wgrad_f16x3
@@ -1047,14 +1032,7 @@ extern "C" int pfst_conv_igemm_f16x3(const float* in, long long in_bs, const voi
   }
   const bool small = M <= 64;                       // 33 ... 64 output rows: the 64-row tile (one 32-row block per wave)
   PFST_CHECK_ARG(!small || !(bnb && bnb->x));
-  const int span = (ksize - 1) * dil;
-  if (mode == 0) {
-    PFST_CHECK_ARG(Ho == (Hi + 2 * pad - span - 1) / stride + 1 && Wo == (Wi + 2 * pad - span - 1) / stride + 1);
-  } else {
-    PFST_CHECK_ARG(Hi == (Ho + 2 * pad - span - 1) / stride + 1 && Wi == (Wo + 2 * pad - span - 1) / stride + 1);
-  }
-  int a, b, c, d;
-  if (mode == 0) { a = stride; b = dil; c = -pad; d = 1; } else { a = 1; b = -dil; c = pad; d = stride; }
+  const int a = g.a, b = g.b, c = g.c, d = g.d;
   const int stats_T = N * (int)cdiv((i64)Ho * Wo, BN) * 2;      // two pixel-waves per tile at every tile height (= pfst_conv_stats_slots for M > 64)
   const bool one = !small && ksize == 1 && stride == 1 && pad == 0;      // pixel-to-pixel: the tile-chain variant
   const bool big = one && M % 256 == 0;                              // 256-row tiles, 512 threads, one workgroup per CU (measured and not kept: the 128-row
@@ -1066,30 +1044,16 @@ extern "C" int pfst_conv_igemm_f16x3(const float* in, long long in_bs, const voi
   if (bnb && bnb->x) {
     // the fused sums use the epilogue's full-tile store path: whole row tiles, no bias, no forward statistics
     PFST_CHECK_ARG(M % 128 == 0 && !bias && !stats && bnb->coef && bnb->partials);
-#define PFST_LAUNCH_F16_BNB(MODE_, ONE_)                                                                                                    \
-    hipLaunchKernelGGL((conv_igemm_f16x3_bnb_kernel<MODE_, ONE_>), grid, dim3(256), 0, (hipStream_t)stream, in, (i64)in_bs, (const uint4*)wk4, bias, \
-                       out, (i64)out_bs, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, w_amax, in_amax, 1, N, chain, *bnb, gate)
-#define PFST_LAUNCH_F16_BNB_BIG(MODE_)                                                                                                      \
-    hipLaunchKernelGGL((conv_igemm_f16x3_bnb_kernel<MODE_, true, 256>), grid, dim3(512), 0, (hipStream_t)stream, in, (i64)in_bs, (const uint4*)wk4, bias, \
-                       out, (i64)out_bs, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, w_amax, in_amax, 1, N, chain, *bnb, gate)
-    if (big) {
-      if (!bnb->relu) PFST_LAUNCH_F16_BNB_BIG(3);
-      else if (bnb->y_mask) PFST_LAUNCH_F16_BNB_BIG(4);
-      else if (bnb->y) PFST_LAUNCH_F16_BNB_BIG(2);
-      else PFST_LAUNCH_F16_BNB_BIG(1);
-    } else if (one) {
-      if (!bnb->relu) PFST_LAUNCH_F16_BNB(3, true);
-      else if (bnb->y_mask) PFST_LAUNCH_F16_BNB(4, true);
-      else if (bnb->y) PFST_LAUNCH_F16_BNB(2, true);
-      else PFST_LAUNCH_F16_BNB(1, true);
-    } else {
-      if (!bnb->relu) PFST_LAUNCH_F16_BNB(3, false);
-      else if (bnb->y_mask) PFST_LAUNCH_F16_BNB(4, false);
-      else if (bnb->y) PFST_LAUNCH_F16_BNB(2, false);
-      else PFST_LAUNCH_F16_BNB(1, false);
-    }
+#define PFST_LAUNCH_F16_BNB(KERNEL_, THREADS_)                                                                                              \
+    hipLaunchKernelGGL(KERNEL_, grid, dim3(THREADS_), 0, (hipStream_t)stream, in, (i64)in_bs, (const uint4*)wk4, bias, out, (i64)out_bs, C, Hi, Wi, \
+                       M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, w_amax, in_amax, 1, N, chain, *bnb, gate)
+    with_bnb_mode<true>(*bnb, [&](auto mode) {
+      constexpr int MODE = decltype(mode)::value;
+      if (big) PFST_LAUNCH_F16_BNB((conv_igemm_f16x3_bnb_kernel<MODE, true, 256>), 512);
+      else if (one) PFST_LAUNCH_F16_BNB((conv_igemm_f16x3_bnb_kernel<MODE, true>), 256);
+      else PFST_LAUNCH_F16_BNB((conv_igemm_f16x3_bnb_kernel<MODE, false>), 256);
+    });
 #undef PFST_LAUNCH_F16_BNB
-#undef PFST_LAUNCH_F16_BNB_BIG
     PFST_CHECK_LAUNCH();
     return PFST_OK;
   }
@@ -1150,39 +1114,21 @@ int pfst_wgrad_f16x3_launch(const float* x, i64 x_bs, const float* dy, i64 dy_bs
   const bool big = M % 256 == 0;                                // 256 rows of dY per workgroup (512 threads, one workgroup per CU)
   const int bm = big ? 256 : 128;
   const int tiles = cdiv(J, 128) * cdiv(M, bm) * groups;
-  // split-K chunking: whole rounds of resident workgroups (2 per CU; the 256-row tile: 1)
-  const double slots = big ? 256.0 : 256.0 * 2;
-  int chunks = 1;
-  double best = -1.0;
-  for (int c = 1; c <= 64 && (c == 1 || P / c >= 512); ++c) {
-    const double rounds = (double)tiles * N * c / slots;
-    const double eff = rounds < 2.0 ? 0.45 * rounds : rounds / ceil(rounds);
-    if (eff > best + 0.02) { best = eff; chunks = c; }
-    if (eff >= 0.93) break;
-  }
-  int chunk_len = ((cdiv(P, chunks) + 15) / 16) * 16;
-  chunks = cdiv(P, chunk_len);
-  const int gx = cdiv(J, 128), gy = cdiv(M, bm), gz = N * groups * chunks;
+  const SplitK k = plan_split_k((i64)tiles * N, P, big ? 256 : 256 * 2, 16);      // resident workgroups: 2 per CU; the 256-row tile: 1
+  const int gx = cdiv(J, 128), gy = cdiv(M, bm), gz = N * groups * k.chunks;
   PFST_CHECK_ARG((i64)gx * gy * gz < (1ll << 31));
-  const i64 elems = (i64)M * J;
-  bool det_ok;
-  float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_DET(det_ok);
-  float* const dwk = ws ? ws : dw;
-  const i64 gsk = ws ? -elems : dw_gs;
+  return wgrad_launch(dw, (i64)M * J, groups, N * k.chunks, dw_gs, s, [&](float* dst, i64 group_stride, i64) {
 #define PFST_LAUNCH_WGRAD(KERNEL_, THREADS_)                                                                                               \
-  hipLaunchKernelGGL(KERNEL_, dim3(gx * gy * gz), dim3(THREADS_), 0, s, x, x_bs, dy, dy_bs, dwk, J, M, P, chunks, chunk_len, N, x_gs, dy_gs, gsk, \
-                     gx, gy, gz, x_amax, dy_amax, bnl4)
-  if (bnl && big) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false, 256, true>), 512);
-  else if (bnl) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false, 128, true>), 256);
-  else if (big && packed) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<true, 256>), 512);
-  else if (big) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false, 256>), 512);
-  else if (packed) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<true>), 256);
-  else PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false>), 256);
+  hipLaunchKernelGGL(KERNEL_, dim3(gx * gy * gz), dim3(THREADS_), 0, s, x, x_bs, dy, dy_bs, dst, J, M, P, k.chunks, k.chunk_len, N, x_gs, dy_gs, \
+                     group_stride, gx, gy, gz, x_amax, dy_amax, bnl4)
+    if (bnl && big) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false, 256, true>), 512);
+    else if (bnl) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false, 128, true>), 256);
+    else if (big && packed) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<true, 256>), 512);
+    else if (big) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false, 256>), 512);
+    else if (packed) PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<true>), 256);
+    else PFST_LAUNCH_WGRAD((conv_wgrad_f16x3_line_kernel<false>), 256);
 #undef PFST_LAUNCH_WGRAD
-  if (ws) wgrad_det_reduce(ws, dw, elems, groups, N * chunks, dw_gs, s);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
+  });
 }
 
 // dw[co][ci] += sum_{n,p} dy[n][co][p] x[n][ci][p]: the weight gradient of a stride-1 1x1 convolution (atomic fp32 adds)

@@ -14,7 +14,7 @@
 // Tiling, XCD-aware tile order and the epilogue (bias / accumulate / fused BN statistics) are those of conv_mfma.hip,
 // which keeps the generic path (Cin % 16 != 0: the 3- and 10-band stems).
 #include "conv_epilogue.h"
-#include "../../include/pfst_hip.h"
+#include "conv_launch.h"
 #include <stdlib.h>
 
 #ifdef PFST_CLOCK_STAMPS
@@ -29,13 +29,6 @@ extern "C" int pfst_debug_read_stamps(unsigned long long* host, int n) {
 namespace {
 
 constexpr int QBN = 128, QBK = 16, QNQ = 4;
-
-__device__ __forceinline__ bool src_coord_q(int o, int t, int a, int b, int c0, int div, int lim, int& s) {
-  const int v = o * a + t * b + c0;
-  const int odd = v & (div - 1);
-  s = v >> (div >> 1);
-  return (odd == 0) & (s >= 0) & (s < lim);
-}
 
 // BNB: the data-gradient launch that completes dL/dy of a BatchNorm layer also emits that layer's backward sums (conv_epilogue.h)
 template <int BM, int BNB = 0>
@@ -91,7 +84,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
   int ld_ty = 0, ld_tx = 0, ld_ci0 = 0;              // (tap, first channel) of the K-slice being prefetched
   auto set_tap = [&]() {
     int sy, sx;
-    const bool ok = pvalid & src_coord_q(oy, ld_ty, ca, cb, cc, cdivv, Hi, sy) & src_coord_q(ox, ld_tx, ca, cb, cc, cdivv, Wi, sx);
+    const bool ok = pvalid & src_coord(oy, ld_ty, ca, cb, cc, cdivv, Hi, sy) & src_coord(ox, ld_tx, ca, cb, cc, cdivv, Wi, sx);
     b_voff = ok ? 4u * ((unsigned)(kh * 8) * (unsigned)HiWi + (unsigned)(sy * Wi + sx)) : OOB;
   };
   auto setup_tile = [&](int tile) {
@@ -231,13 +224,10 @@ int launch_q(const float* in, i64 in_bs, const float* wq, const float* bias, flo
   if (bnb && bnb->x) {
     // the fused sums use the epilogue's full-tile store path: whole row tiles, no bias, one GEMM group
     PFST_CHECK_ARG(M % BM == 0 && !bias && !stats && groups == 1 && bnb->coef && bnb->partials);
-#define PFST_LAUNCH_BNB(MODE_)                                                                                                        \
-    hipLaunchKernelGGL((conv_igemm_q_kernel<BM, MODE_>), grid, dim3(256), lds_pad, s, in, in_bs, reinterpret_cast<const float4*>(wq), bias, out, \
-                       out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb)
-    if (!bnb->relu) PFST_LAUNCH_BNB(3);
-    else if (bnb->y) PFST_LAUNCH_BNB(2);
-    else PFST_LAUNCH_BNB(1);
-#undef PFST_LAUNCH_BNB
+    with_bnb_mode<false>(*bnb, [&](auto mode) {
+      hipLaunchKernelGGL((conv_igemm_q_kernel<BM, decltype(mode)::value>), grid, dim3(256), lds_pad, s, in, in_bs, reinterpret_cast<const float4*>(wq),
+                         bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb);
+    });
   } else {
     hipLaunchKernelGGL((conv_igemm_q_kernel<BM, 0>), grid, dim3(256), lds_pad, s, in, in_bs, reinterpret_cast<const float4*>(wq), bias, out,
                        out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, PfstBnbArgs());
@@ -251,7 +241,7 @@ int launch_q(const float* in, i64 in_bs, const float* wq, const float* bias, flo
 int pfst_igemm_q_launch(const float* in, i64 in_bs, const float* wq, const float* bias, float* out, i64 out_bs, int N, int C, int Hi,
                         int Wi, int M, int Ho, int Wo, int ks, int a, int b, int c, int d, int acc, float* stats, int stats_T, int groups,
                         hipStream_t s, const PfstBnbArgs* bnb) {
-  if (M > 64) return launch_q<128>(in, in_bs, wq, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, groups, bnb, s);
-  if (M > 32) return launch_q<64>(in, in_bs, wq, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, groups, bnb, s);
-  return launch_q<32>(in, in_bs, wq, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, groups, bnb, s);
+  return with_row_tile(M, [&](auto bm) {
+    return launch_q<decltype(bm)::value>(in, in_bs, wq, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, groups, bnb, s);
+  });
 }

@@ -18,7 +18,7 @@
 //   sub-tile as 32x32 MFMA accumulators; K advances 16 per step through a double-buffered LDS
 //   tile with register-staged prefetch (one barrier per step).
 #include "conv_epilogue.h"
-#include "det.h"
+#include "wgrad_launch.h"
 #include "../../include/pfst_hip.h"
 #include <stdlib.h>
 
@@ -28,14 +28,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace {
 
 constexpr int BK_MIN = 16;  // K granularity of the wave-uniform-tap fast path (Cin % 16 == 0)
-
-// source coordinate of output index o for tap t: (o*a + t*b + c0) / div, div in {1,2}; branch-free validity
-__device__ __forceinline__ bool src_coord(int o, int t, int a, int b, int c0, int div, int lim, int& s) {
-  const int v = o * a + t * b + c0;
-  const int odd = v & (div - 1);
-  s = v >> (div >> 1);
-  return (odd == 0) & (s >= 0) & (s < lim);
-}
 
 template <int BM>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(
@@ -369,38 +361,19 @@ int launch_wgrad_k(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* 
                    int Ho, int Wo, int stride, int dil, int pad, hipStream_t s) {
   const int P = Ho * Wo, J = Cin * T;
   const int tiles = cdiv(J, WBJ) * cdiv(M, BM);
-  // Split the pixel (K) range (chunks of >= 512 pixels, fp32 atomics combine) so that the launch fills the chip in
-  // whole "rounds": `slots` blocks are resident at once (LDS-limited: 4 per CU at WBK=16, 2 at WBK=32), and e.g.
-  // 1152 blocks on 1024 slots leave 7/8 of the CUs idle for the last ninth of the work (measured -10 % on the 3x3
-  // layers).  Take the smallest split whose last round is >= 90 % full, else the best one.
-  const double slots = 256.0 * (WBK == 16 ? 4 : 2);
-  int chunks = 1;
-  double best = -1.0;
-  for (int c = 1; c <= 64 && (c == 1 || P / c >= 512); ++c) {
-    const double rounds = (double)tiles * N * c / slots;
-    const double eff = rounds < 2.0 ? 0.45 * rounds : rounds / ceil(rounds);    // want >= 2 rounds: 1x1 layers measured best there
-    if (eff > best + 0.02) { best = eff; chunks = c; }
-    if (eff >= 0.93) break;
-  }
-  while ((i64)N * chunks > 65535 && chunks > 1) --chunks;       // gridDim.z limit
-  int chunk_len = ((cdiv(P, chunks) + WBK - 1) / WBK) * WBK;
-  chunks = cdiv(P, chunk_len);
-  dim3 grid(cdiv(J, WBJ), cdiv(M, BM), N * chunks);
+  // `slots` workgroups are resident at once (LDS-limited: 4 per CU at WBK=16, 2 at WBK=32); N * chunks is gridDim.z (<= 65535)
+  const SplitK k = plan_split_k((i64)tiles * N, P, 256 * (WBK == 16 ? 4 : 2), WBK, 65535 / N);
+  dim3 grid(cdiv(J, WBJ), cdiv(M, BM), N * k.chunks);
   const size_t lds = (size_t)2 * (BM + WBJ) * (WBK + 1) * sizeof(float) + (size_t)WBJ * 2 * sizeof(int);
   static bool attr_set = false;
   if (!attr_set) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<BM, T, WBK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  const i64 elems = (i64)M * J;
-  bool det_ok;
-  float* const ws = wgrad_det_scratch(elems, (i64)N * chunks, s, det_ok);          // deterministic mode (det.h)
-  PFST_CHECK_DET(det_ok);
-  hipLaunchKernelGGL((conv_wgrad_kernel<BM, T, WBK>), grid, dim3(256), lds, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho, Wo,
-                     stride, dil, pad, chunks, chunk_len, ws ? elems : (i64)0);
-  if (ws) wgrad_det_reduce(ws, dw, elems, 1, N * chunks, 0, s);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
+  return wgrad_launch(dw, (i64)M * J, 1, N * k.chunks, 0, s, [&](float* dst, i64, i64 slice_stride) {
+    hipLaunchKernelGGL((conv_wgrad_kernel<BM, T, WBK>), grid, dim3(256), lds, s, x, x_bs, dy, dy_bs, dst, Cin, Hi, Wi, M, Ho, Wo, stride, dil, pad,
+                       k.chunks, k.chunk_len, slice_stride);
+  });
 }
 
 template <int BM, int T>
@@ -432,47 +405,47 @@ extern "C" int pfst_conv_igemm(const float* in, long long in_bs, const float* wk
                                int mode, int accumulate, float* stats, const pfst_bnb_fuse_t* bnb, pfst_stream_t stream) {
   PFST_CHECK_ARG(in && wk && out && N > 0 && C > 0 && M > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
   PFST_CHECK_ARG(!bnb || ((C % BK_MIN) == 0 && bnb->x && bnb->x_bs >= (i64)M * Ho * Wo && (!bnb->y || bnb->y_bs >= (i64)M * Ho * Wo)));
-  PFST_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && dil >= 1 && pad >= 0 && (mode == 0 || mode == 1));
+  ConvGeom g;
+  if (const int rc = conv_geometry(Hi, Wi, Ho, Wo, ksize, stride, dil, pad, mode, g)) return rc;
   PFST_CHECK_ARG(in_bs >= (i64)C * Hi * Wi && out_bs >= (i64)M * Ho * Wo && N <= 65535);
   // 32-bit byte offsets inside one image / one weight tensor (buffer descriptors): fail loudly beyond 2 GiB
   PFST_CHECK_ARG((i64)C * Hi * Wi * 4 < (1ll << 31) && (i64)M * Ho * Wo * 4 < (1ll << 31) && (i64)C * ksize * ksize * M * 4 < (1ll << 31));
-  const int span = (ksize - 1) * dil;
-  if (mode == 0) {
-    PFST_CHECK_ARG(Ho == (Hi + 2 * pad - span - 1) / stride + 1 && Wo == (Wi + 2 * pad - span - 1) / stride + 1);
-  } else {  // dgrad: `in` is dy (Hi x Wi = forward output), `out` is dx (Ho x Wo = forward input)
-    PFST_CHECK_ARG(Hi == (Ho + 2 * pad - span - 1) / stride + 1 && Wi == (Wo + 2 * pad - span - 1) / stride + 1);
-  }
-  int a, b, c, d;
-  if (mode == 0) { a = stride; b = dil; c = -pad; d = 1; } else { a = 1; b = -dil; c = pad; d = stride; }
   hipStream_t s = (hipStream_t)stream;
   const int stats_T = N * pfst_conv_stats_slots(M, Ho, Wo);
   const bool generic = (C % BK_MIN) != 0;
   if (!generic)      // Cin % 16 == 0: K-quad kernel (conv_igemm_q.hip), weights packed [K/4][M][4]
-    return pfst_igemm_q_launch(in, in_bs, wk, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, 1, s, bnb);
-  if (M > 64) return launch_igemm_generic<128>(in, in_bs, wk, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, s);
-  if (M > 32) return launch_igemm_generic<64>(in, in_bs, wk, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, s);
-  return launch_igemm_generic<32>(in, in_bs, wk, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, s);
+    return pfst_igemm_q_launch(in, in_bs, wk, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, g.a, g.b, g.c, g.d, accumulate, stats, stats_T, 1, s, bnb);
+  return with_row_tile(M, [&](auto bm) {
+    return launch_igemm_generic<decltype(bm)::value>(in, in_bs, wk, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, g.a, g.b, g.c, g.d, accumulate,
+                                                     stats, stats_T, s);
+  });
 }
 
 extern "C" int pfst_conv_wgrad(const float* x, long long x_bs, const float* dy, long long dy_bs, float* dw,
                                int N, int Cin, int Hi, int Wi, int Cout, int Ho, int Wo, int ksize, int stride, int dil, int pad,
                                pfst_stream_t stream) {
   PFST_CHECK_ARG(x && dy && dw && N > 0 && Cin > 0 && Cout > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
-  PFST_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && dil >= 1 && pad >= 0);
-  const int span = (ksize - 1) * dil;
-  PFST_CHECK_ARG(Ho == (Hi + 2 * pad - span - 1) / stride + 1 && Wo == (Wi + 2 * pad - span - 1) / stride + 1);
+  ConvGeom g;                     // the forward map: the kernels rebuild it from (stride, dil, pad)
+  if (const int rc = conv_geometry(Hi, Wi, Ho, Wo, ksize, stride, dil, pad, 0, g)) return rc;
   PFST_CHECK_ARG(x_bs >= (i64)Cin * Hi * Wi && dy_bs >= (i64)Cout * Ho * Wo && N <= 65535);
   PFST_CHECK_ARG((i64)Cin * Hi * Wi * 4 < (1ll << 31) && (i64)Cout * Ho * Wo * 4 < (1ll << 31));     // 32-bit offsets per image
   hipStream_t s = (hipStream_t)stream;
   if (pfst_wgrad_q_eligible(x, x_bs, dy, dy_bs, Hi, Wi, Ho, Wo, ksize, stride, dil))       // K-quad fast path (conv_wgrad_q.hip)
     return pfst_wgrad_q_launch(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, ksize, dil, pad, 1, 0, 0, 0, s);
-#define PFST_WGRAD(BM_)                                                                                          \
-  return ksize == 3 ? launch_wgrad<BM_, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s) \
-                    : launch_wgrad<BM_, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s)
-  if (Cout > 64) { PFST_WGRAD(128); }
-  if (Cout > 32) { PFST_WGRAD(64); }
-  PFST_WGRAD(32);
-#undef PFST_WGRAD
+  return with_row_tile(Cout, [&](auto bm) {
+    constexpr int BM = decltype(bm)::value;
+    return ksize == 3 ? launch_wgrad<BM, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s)
+                      : launch_wgrad<BM, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s);
+  });
+}
+
+// The split-K planner of the weight-gradient launchers (wgrad_launch.h) as a host-only call: touches no device
+extern "C" int pfst_wgrad_split_k(long long work, int P, int slots, int k_step, int chunk_cap, int doubling, int* chunks, int* chunk_len) {
+  PFST_CHECK_ARG(work > 0 && P > 0 && chunks && chunk_len && (doubling || (slots > 0 && k_step > 0 && chunk_cap >= 0)));
+  const SplitK k = doubling ? plan_split_k_doubling(work, P) : plan_split_k(work, P, slots, k_step, chunk_cap);
+  *chunks = k.chunks;
+  *chunk_len = k.chunk_len;
+  return PFST_OK;
 }
 
 extern "C" int pfst_bias_grad(const float* dy, long long dy_bs, float* db, int N, int C, int HW, pfst_stream_t stream) {

@@ -11,10 +11,7 @@
 // pfst_conv_pack_weight_split into the exact LDS image [k16-group][piece][k-half][row][8 x bf16]; activations are split
 // in registers on their way from HBM to LDS (fp32 NCHW stays the storage format everywhere).
 #include "conv_epilogue.h"
-#include "det.h"
-#include <math.h>
-#include <type_traits>
-#include <utility>
+#include "wgrad_launch.h"
 #include <stdlib.h>
 #include "../../include/pfst_hip.h"
 
@@ -25,13 +22,6 @@ namespace {
 
 constexpr int BN = 128;
 constexpr int NP = 3;  // pieces
-
-__device__ __forceinline__ bool src_coord(int o, int t, int a, int b, int c0, int div, int lim, int& s) {
-  const int v = o * a + t * b + c0;
-  const int odd = v & (div - 1);
-  s = v >> (div >> 1);
-  return (odd == 0) & (s >= 0) & (s < lim);
-}
 
 __device__ __forceinline__ unsigned short bf16_bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
 __device__ __forceinline__ float bf16_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
@@ -54,11 +44,9 @@ __device__ __forceinline__ void split8(const float (&v)[8], uint4& p0, uint4& p1
 
 // BNB != 0: the data-gradient launch also emits the BatchNorm-backward sums of the layer that owns `out` (conv_epilogue.h); on the bf16
 // matrix pipe the epilogue's VALU work co-issues with the other waves' MFMAs
-// DIAG != 0: the timing-ablation instantiations of round 2 (profiles/r02_split_phase_stamps.txt; results WRONG by construction).  No entry point
-// launches them any more (the PFST_SPLIT_DIAG dispatch and tools/split_ablation.py were removed in round 5); instantiate by hand to repeat it:
-// 1 no split + LDS store, 2 no global loads, 3 no MFMAs, 4 no LDS fragment reads, 5 no in-loop barrier,
-// 6 s_memtime stamps around the four phases of a K-step, summed per wave into the `stats` buffer as 6 (of 8) x u32 (not an output value)
-template <int BM, int BNB = 0, int DIAG = 0>
+// (The timing-ablation and phase-stamp instantiations of this loop, which produced profiles/r02_split_phase_stamps.txt, are in the history before
+// this commit.)
+template <int BM, int BNB = 0>
 __global__ __launch_bounds__(256) void conv_igemm_split_kernel(
     const float* __restrict__ in, i64 in_bs, const uint4* __restrict__ wk6, const float* __restrict__ bias,
     float* __restrict__ out, i64 out_bs, int C, int Hi, int Wi, int M, int Ho, int Wo, int ks,
@@ -162,116 +150,34 @@ __global__ __launch_bounds__(256) void conv_igemm_split_kernel(
   __syncthreads();
 
   const int l31 = lane & 31, lh = lane >> 5;
-  unsigned long long tprev = 0;
-  unsigned ph[6] = {0, 0, 0, 0, 0, 0};
-  if (DIAG == 6) tprev = __builtin_amdgcn_s_memtime();
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
-    if (DIAG != 2) {
-      if (kt + 1 < KT) load_tile(kt + 1);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(breg[i]));
-#pragma unroll
-      for (int i = 0; i < A_N; ++i) asm volatile("" : "+v"(areg[i].x), "+v"(areg[i].y), "+v"(areg[i].z), "+v"(areg[i].w));
-    }
-    if (DIAG == 6) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      ph[4] += (unsigned)(t - tprev);          // global loads issued
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    if (kt + 1 < KT) load_tile(kt + 1);
     bf16x8 af[TM][NP], bf[TN][NP];
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl) {
-      if (DIAG != 4) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) af[i][pl] = __builtin_bit_cast(bf16x8, As[cur][(pl * 2 + lh) * BM + wm0 + i * 32 + l31]);
+      for (int i = 0; i < TM; ++i) af[i][pl] = __builtin_bit_cast(bf16x8, As[cur][(pl * 2 + lh) * BM + wm0 + i * 32 + l31]);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j][pl] = __builtin_bit_cast(bf16x8, Bs[cur][(pl * 2 + lh) * BN + wn0 + j * 32 + l31]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) { bf16x8 t = __builtin_bit_cast(bf16x8, areg[0]); asm volatile("" : "+v"(t)); af[i][pl] = t; }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) { bf16x8 t = __builtin_bit_cast(bf16x8, areg[0]); asm volatile("" : "+v"(t)); bf[j][pl] = t; }
-      }
+      for (int j = 0; j < TN; ++j) bf[j][pl] = __builtin_bit_cast(bf16x8, Bs[cur][(pl * 2 + lh) * BN + wn0 + j * 32 + l31]);
     }
     // smallest terms first: (2,0) (1,1) (0,2) | (1,0) (0,1) | (0,0).  This loop (now used for contractions below 512 and the 64- / 32-row
     // tiles) leaves the order of everything else to the compiler: all MFMAs back to back, then the split and the LDS stores.  Its matrix
-    // pipe is 0.54-0.58 busy; the phase stamps (DIAG 6) show why, and conv_igemm_split_pipe_body / _pair_body below are the answer.
+    // pipe is 0.54-0.58 busy; the phase stamps quoted below show why, and conv_igemm_split_pipe_body / _pair_body are the answer.
     constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
     constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
-    if (DIAG == 6) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      ph[0] += (unsigned)(t - tprev);
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], acc[i][j], 0, 0, 0);
+    if (kt + 1 < KT) {
+      split_tile();
+      store_tile(cur ^ 1);
     }
-    if (DIAG != 3) {
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], acc[i][j], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int pl = 0; pl < NP; ++pl) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(af[i][pl]));
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(bf[j][pl]));
-      }
-    }
-    if (DIAG == 6) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      ph[1] += (unsigned)(t - tprev);
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (DIAG != 1) {
-      if (DIAG == 6) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        ph[5] += (unsigned)(t - tprev);          // global loads landed
-        tprev = t;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (kt + 1 < KT) {
-        split_tile();
-        store_tile(cur ^ 1);
-      }
-      if (DIAG == 6) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        ph[2] += (unsigned)(t - tprev);
-        tprev = t;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(breg[i]));
-#pragma unroll
-      for (int i = 0; i < A_N; ++i) asm volatile("" ::"v"(areg[i].x), "v"(areg[i].y), "v"(areg[i].z), "v"(areg[i].w));
-    }
-    if (DIAG != 5) __syncthreads();
-    if (DIAG == 6) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      ph[3] += (unsigned)(t - tprev);
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  if (DIAG == 6) {
-    if (lane == 0 && stats) {
-      unsigned* dbg = reinterpret_cast<unsigned*>(stats) + ((((i64)n * gridDim.x + blockIdx.x) * 4 + wid) * 8);
-      dbg[0] = ph[0]; dbg[1] = ph[1]; dbg[2] = ph[2]; dbg[3] = ph[3]; dbg[4] = ph[4]; dbg[5] = ph[5];
-    }
-    stats = nullptr;
+    __syncthreads();
   }
 
   if (BNB != 0) {
@@ -285,21 +191,13 @@ __global__ __launch_bounds__(256) void conv_igemm_split_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The same 128 x 128 tile with a software-pipelined K-step.  In-kernel stamps on the kernel above (tools/split_ablation.py, DIAG 6,
-// three waves per SIMD) per wave and K-step: 581 cycles to ISSUE the 11 global loads, 228 until the fragments landed, 1080 for the 24
+// The same 128 x 128 tile with a software-pipelined K-step.  In-kernel s_memtime stamps around the phases of the kernel above
+// (profiles/r02_split_phase_stamps.txt, three waves per SIMD) per wave and K-step: 581 cycles to ISSUE the 11 global loads, 228 until the fragments landed, 1080 for the 24
 // MFMAs (768 alone), 10 waiting for the global loads, 1363 for the 44-instruction split + 6 LDS stores, 232 at the barrier.  Beside
 // ANOTHER wave's back-to-back MFMAs a wave gets roughly one vector instruction per MFMA slot issued; inside its OWN MFMA stream a wave
 // hides up to five (MI355X guide, 'single-issue instructions hidden per MFMA gap').  So every wave here carries its own loads,
 // fragment reads, split arithmetic and LDS stores in the gaps of its own 24 MFMAs (sched_group_barrier), and the K loop is cut into
 // branch-free blocks: the tap switch happens between them, not inside.
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>()), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {       // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), always unrolled
-  static_for_seq(std::make_integer_sequence<int, N>(), static_cast<F&&>(f));
-}
 
 // The in-register split as 44 single VALU instructions pinned in place (volatile asm): plain arithmetic is sunk to the LDS stores by the
 // compiler and packed into v_pk_add_f32, which is slow beside MFMAs.  K = 0..43 on the eight values v[0..8): two pairs in lockstep
@@ -329,9 +227,7 @@ __device__ __forceinline__ void split_op(const float (&v)[8], SplitState& s) {
   }
 }
 __device__ __forceinline__ uint4 split_piece(const SplitState& s, int pl) { return make_uint4(s.hp[pl][0], s.hp[pl][1], s.hp[pl][2], s.hp[pl][3]); }
-// SHAPE16: timing experiment only (WRONG results): every 32x32x16 MFMA replaced by two 16x16x32 MFMAs on the same operand registers,
-// to see which clock the chip holds for that shape (MI355X guide, DVFS give-back item 7)
-template <int BNB, bool SHAPE16 = false>
+template <int BNB>
 __device__ __forceinline__ void conv_igemm_split_pipe_body(
     const float* __restrict__ in, i64 in_bs, const uint4* __restrict__ wk6, const float* __restrict__ bias,
     float* __restrict__ out, i64 out_bs, int C, int Hi, int Wi, int M, int Ho, int Wo, int ks,
@@ -440,16 +336,7 @@ __device__ __forceinline__ void conv_igemm_split_pipe_body(
     static_for<24>([&](auto mc) {
       constexpr int m = decltype(mc)::value;
       constexpr int t = m >> 2, i = (m >> 1) & 1, j = m & 1;
-      if constexpr (SHAPE16) {
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        f32x4 lo = __builtin_shufflevector(acc[i][j], acc[i][j], 0, 1, 2, 3), hi = __builtin_shufflevector(acc[i][j], acc[i][j], 4, 5, 6, 7);
-        lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][PA[t]], bf[j][PB[t]], lo, 0, 0, 0);
-        hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][PA[t]], bf[j][PB[t]], hi, 0, 0, 0);
-        acc[i][j][0] = lo[0]; acc[i][j][1] = lo[1]; acc[i][j][2] = lo[2]; acc[i][j][3] = lo[3];
-        acc[i][j][4] = hi[0]; acc[i][j][5] = hi[1]; acc[i][j][6] = hi[2]; acc[i][j][7] = hi[3];
-      } else {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], acc[i][j], 0, 0, 0);
-      }
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], acc[i][j], 0, 0, 0);
       if constexpr (m < 8) read_frag(4 + m);
       if constexpr (LOAD) {
         if constexpr (m < 8) breg[m] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, b_voff, b_soff + m * b_chan, 0));
@@ -1174,35 +1061,17 @@ template <int BM>
 int launch_wgrad_split_q(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, int N, int J, int M, int P, int groups,
                          i64 x_gs, i64 dy_gs, i64 dw_gs, hipStream_t s) {
   const int tiles = cdiv(J, 128) * cdiv(M, BM) * groups;
-  // split-K chunking: whole rounds of resident workgroups (49 KB of LDS: 3 per CU)
-  const double slots = 256.0 * 3;
-  int chunks = 1;
-  double best = -1.0;
-  for (int c = 1; c <= 64 && (c == 1 || P / c >= 512); ++c) {
-    const double rounds = (double)tiles * N * c / slots;
-    const double eff = rounds < 2.0 ? 0.45 * rounds : rounds / ceil(rounds);
-    if (eff > best + 0.02) { best = eff; chunks = c; }
-    if (eff >= 0.93) break;
-  }
-  int chunk_len = ((cdiv(P, chunks) + 15) / 16) * 16;
-  chunks = cdiv(P, chunk_len);
-  const int gx = cdiv(J, 128), gy = cdiv(M, BM), gz = N * groups * chunks;
+  const SplitK k = plan_split_k((i64)tiles * N, P, 256 * 3, 16);       // resident workgroups: 49 KB of LDS, 3 per CU
+  const int gx = cdiv(J, 128), gy = cdiv(M, BM), gz = N * groups * k.chunks;
   PFST_CHECK_ARG((i64)gx * gy * gz < (1ll << 31));
-  const i64 elems = (i64)M * J;
-  bool det_ok;
-  float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_DET(det_ok);
-  float* const dwk = ws ? ws : dw;
-  const i64 gsk = ws ? -elems : dw_gs;
-  if (BM == 128)
-    hipLaunchKernelGGL(conv_wgrad_split_q_pipe_kernel, dim3(gx * gy * gz), dim3(256), 0, s, x, x_bs, dy, dy_bs, dwk, J, M, P, chunks, chunk_len,
-                       N, x_gs, dy_gs, gsk, gx, gy, gz, 1);
-  else
-    hipLaunchKernelGGL((conv_wgrad_split_q_kernel<BM>), dim3(gx * gy * gz), dim3(256), 0, s, x, x_bs, dy, dy_bs, dwk, J, M, P, chunks, chunk_len,
-                       N, x_gs, dy_gs, gsk, gx, gy, gz, 1);
-  if (ws) wgrad_det_reduce(ws, dw, elems, groups, N * chunks, dw_gs, s);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
+  return wgrad_launch(dw, (i64)M * J, groups, N * k.chunks, dw_gs, s, [&](float* dst, i64 group_stride, i64) {
+    if (BM == 128)
+      hipLaunchKernelGGL(conv_wgrad_split_q_pipe_kernel, dim3(gx * gy * gz), dim3(256), 0, s, x, x_bs, dy, dy_bs, dst, J, M, P, k.chunks, k.chunk_len,
+                         N, x_gs, dy_gs, group_stride, gx, gy, gz, 1);
+    else
+      hipLaunchKernelGGL((conv_wgrad_split_q_kernel<BM>), dim3(gx * gy * gz), dim3(256), 0, s, x, x_bs, dy, dy_bs, dst, J, M, P, k.chunks,
+                         k.chunk_len, N, x_gs, dy_gs, group_stride, gx, gy, gz, 1);
+  });
 }
 
 template <int BM, int T>
@@ -1210,20 +1079,12 @@ int launch_wgrad_split(const float* x, i64 x_bs, const float* dy, i64 dy_bs, flo
                        int Ho, int Wo, int stride, int dil, int pad, hipStream_t s) {
   const int P = Ho * Wo, J = Cin * T;
   const int tiles = cdiv(J, 128) * cdiv(M, BM);
-  int chunks = 1;
-  while ((i64)tiles * N * chunks < 1024 && P / (chunks * 2) >= 512) chunks *= 2;
-  int chunk_len = ((cdiv(P, chunks) + 15) / 16) * 16;
-  chunks = cdiv(P, chunk_len);
-  dim3 grid(cdiv(J, 128), cdiv(M, BM), N * chunks);
-  const i64 elems = (i64)M * J;
-  bool det_ok;
-  float* const ws = wgrad_det_scratch(elems, (i64)N * chunks, s, det_ok);          // deterministic mode (det.h)
-  PFST_CHECK_DET(det_ok);
-  hipLaunchKernelGGL((conv_wgrad_split_kernel<BM, T>), grid, dim3(256), 0, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho, Wo, stride,
-                     dil, pad, chunks, chunk_len, ws ? elems : (i64)0);
-  if (ws) wgrad_det_reduce(ws, dw, elems, 1, N * chunks, 0, s);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
+  const SplitK k = plan_split_k_doubling((i64)tiles * N, P);
+  dim3 grid(cdiv(J, 128), cdiv(M, BM), N * k.chunks);
+  return wgrad_launch(dw, (i64)M * J, 1, N * k.chunks, 0, s, [&](float* dst, i64, i64 slice_stride) {
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<BM, T>), grid, dim3(256), 0, s, x, x_bs, dy, dy_bs, dst, Cin, Hi, Wi, M, Ho, Wo, stride, dil, pad,
+                       k.chunks, k.chunk_len, slice_stride);
+  });
 }
 
 template <int BM>
@@ -1238,13 +1099,10 @@ int launch_split(const float* in, i64 in_bs, const void* wk6, const float* bias,
   if (BM == 128 && pipe && C % 32 == 0) {
     if (bnb && bnb->x) {
       PFST_CHECK_ARG(M % BM == 0 && !bias && !stats && groups == 1 && bnb->coef && bnb->partials);
-#define PFST_LAUNCH_PAIR_BNB(MODE_)                                                                                                        \
-      hipLaunchKernelGGL((conv_igemm_split_pair_bnb_kernel<MODE_>), grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C, \
-                         Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb)
-      if (!bnb->relu) PFST_LAUNCH_PAIR_BNB(3);
-      else if (bnb->y) PFST_LAUNCH_PAIR_BNB(2);
-      else PFST_LAUNCH_PAIR_BNB(1);
-#undef PFST_LAUNCH_PAIR_BNB
+      with_bnb_mode<false>(*bnb, [&](auto mode) {
+        hipLaunchKernelGGL((conv_igemm_split_pair_bnb_kernel<decltype(mode)::value>), grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out,
+                           out_bs, C, Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb);
+      });
     } else {
       hipLaunchKernelGGL(conv_igemm_split_pair_kernel, grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C, Hi, Wi, M, Ho,
                          Wo, ks, a, b, c, d, acc, stats, stats_T);
@@ -1254,17 +1112,15 @@ int launch_split(const float* in, i64 in_bs, const void* wk6, const float* bias,
   }
   if (bnb && bnb->x) {
     PFST_CHECK_ARG(M % BM == 0 && !bias && !stats && groups == 1 && bnb->coef && bnb->partials);
-#define PFST_LAUNCH_SPLIT_BNB(MODE_)                                                                                              \
-    if (BM == 128 && pipe)                                                                                                         \
-      hipLaunchKernelGGL((conv_igemm_split_pipe_bnb_kernel<MODE_>), grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C, \
-                         Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb);                                            \
-    else                                                                                                                           \
-      hipLaunchKernelGGL((conv_igemm_split_kernel<BM, MODE_>), grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C,  \
-                         Hi, Wi, M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb)
-    if (!bnb->relu) PFST_LAUNCH_SPLIT_BNB(3);
-    else if (bnb->y) PFST_LAUNCH_SPLIT_BNB(2);
-    else PFST_LAUNCH_SPLIT_BNB(1);
-#undef PFST_LAUNCH_SPLIT_BNB
+    with_bnb_mode<false>(*bnb, [&](auto mode) {
+      constexpr int MODE = decltype(mode)::value;
+      if (BM == 128 && pipe)
+        hipLaunchKernelGGL((conv_igemm_split_pipe_bnb_kernel<MODE>), grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C, Hi, Wi,
+                           M, Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb);
+      else
+        hipLaunchKernelGGL((conv_igemm_split_kernel<BM, MODE>), grid, dim3(256), 0, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C, Hi, Wi, M,
+                           Ho, Wo, ks, a, b, c, d, acc, stats, stats_T, *bnb);
+    });
   } else {
     if (BM == 128 && pipe)
       hipLaunchKernelGGL(conv_igemm_split_pipe_kernel, grid, dim3(256), lds_pad, s, in, in_bs, (const uint4*)wk6, bias, out, out_bs, C, Hi, Wi,
@@ -1295,45 +1151,36 @@ extern "C" int pfst_conv_igemm_split(const float* in, long long in_bs, const voi
                                      int mode, int accumulate, float* stats, const pfst_bnb_fuse_t* bnb, pfst_stream_t stream) {
   PFST_CHECK_ARG(in && wk6 && out && N > 0 && C > 0 && M > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
   PFST_CHECK_ARG(!bnb || (bnb->x && bnb->x_bs >= (i64)M * Ho * Wo && (!bnb->y || bnb->y_bs >= (i64)M * Ho * Wo)));
-  PFST_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && dil >= 1 && pad >= 0 && (mode == 0 || mode == 1));
+  ConvGeom g;
+  if (const int rc = conv_geometry(Hi, Wi, Ho, Wo, ksize, stride, dil, pad, mode, g)) return rc;
   PFST_CHECK_ARG(in_bs >= (i64)C * Hi * Wi && out_bs >= (i64)M * Ho * Wo && N <= 65535);
   if (C % 16 != 0) {
     pfst_set_error(__FILE__, __LINE__, "split kernel needs C % 16 == 0 (use pfst_conv_igemm)");
     return PFST_ERR_UNSUPPORTED;
   }
-  const int span = (ksize - 1) * dil;
-  if (mode == 0) {
-    PFST_CHECK_ARG(Ho == (Hi + 2 * pad - span - 1) / stride + 1 && Wo == (Wi + 2 * pad - span - 1) / stride + 1);
-  } else {
-    PFST_CHECK_ARG(Hi == (Ho + 2 * pad - span - 1) / stride + 1 && Wi == (Wo + 2 * pad - span - 1) / stride + 1);
-  }
-  int a, b, c, d;
-  if (mode == 0) { a = stride; b = dil; c = -pad; d = 1; } else { a = 1; b = -dil; c = pad; d = stride; }
   hipStream_t s = (hipStream_t)stream;
   const int stats_T = N * pfst_conv_stats_slots(M, Ho, Wo);
-  if (M > 64) return launch_split<128>(in, in_bs, wk6, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, 1, s, bnb);
-  if (M > 32) return launch_split<64>(in, in_bs, wk6, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, 1, s, bnb);
-  return launch_split<32>(in, in_bs, wk6, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, a, b, c, d, accumulate, stats, stats_T, 1, s, bnb);
+  return with_row_tile(M, [&](auto bm) {
+    return launch_split<decltype(bm)::value>(in, in_bs, wk6, bias, out, out_bs, N, C, Hi, Wi, M, Ho, Wo, ksize, g.a, g.b, g.c, g.d, accumulate, stats,
+                                             stats_T, 1, s, bnb);
+  });
 }
 
 extern "C" int pfst_conv_wgrad_split(const float* x, long long x_bs, const float* dy, long long dy_bs, float* dw,
                                      int N, int Cin, int Hi, int Wi, int Cout, int Ho, int Wo, int ksize, int stride, int dil, int pad,
                                      pfst_stream_t stream) {
   PFST_CHECK_ARG(x && dy && dw && N > 0 && Cin > 0 && Cout > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
-  PFST_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && dil >= 1 && pad >= 0);
-  const int span = (ksize - 1) * dil;
-  PFST_CHECK_ARG(Ho == (Hi + 2 * pad - span - 1) / stride + 1 && Wo == (Wi + 2 * pad - span - 1) / stride + 1);
+  ConvGeom g;                     // the forward map: the kernels rebuild it from (stride, dil, pad)
+  if (const int rc = conv_geometry(Hi, Wi, Ho, Wo, ksize, stride, dil, pad, 0, g)) return rc;
   PFST_CHECK_ARG(x_bs >= (i64)Cin * Hi * Wi && dy_bs >= (i64)Cout * Ho * Wo);
   hipStream_t s = (hipStream_t)stream;
   if (pfst_wgrad_split_q_eligible(x, x_bs, dy, dy_bs, Hi, Wi, Ho, Wo, ksize, stride))
     return pfst_wgrad_split_q_launch(x, x_bs, dy, dy_bs, dw, N, Cin, Cout, Ho * Wo, 1, 0, 0, 0, s);
-#define PFST_WGS(BM_)                                                                                                  \
-  return ksize == 3 ? launch_wgrad_split<BM_, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s) \
-                    : launch_wgrad_split<BM_, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s)
-  if (Cout > 64) { PFST_WGS(128); }
-  if (Cout > 32) { PFST_WGS(64); }
-  PFST_WGS(32);
-#undef PFST_WGS
+  return with_row_tile(Cout, [&](auto bm) {
+    constexpr int BM = decltype(bm)::value;
+    return ksize == 3 ? launch_wgrad_split<BM, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s)
+                      : launch_wgrad_split<BM, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, stride, dil, pad, s);
+  });
 }
 
 // internal: K-quad split weight gradient of 1x1 / grouped transform-domain products (used by pfst_conv_wgrad_split and pfst_wino_wgrad)
@@ -1346,9 +1193,9 @@ bool pfst_wgrad_split_q_eligible(const float* x, i64 x_bs, const float* dy, i64 
 int pfst_wgrad_split_q_launch(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, int N, int Cin, int Cout, int P, int groups,
                               i64 x_gs, i64 dy_gs, i64 dw_gs, hipStream_t s) {
   PFST_CHECK_ARG((i64)Cin * P * 4 < (1ll << 31) && (i64)Cout * P * 4 < (1ll << 31));
-  if (Cout > 64) return launch_wgrad_split_q<128>(x, x_bs, dy, dy_bs, dw, N, Cin, Cout, P, groups, x_gs, dy_gs, dw_gs, s);
-  if (Cout > 32) return launch_wgrad_split_q<64>(x, x_bs, dy, dy_bs, dw, N, Cin, Cout, P, groups, x_gs, dy_gs, dw_gs, s);
-  return launch_wgrad_split_q<32>(x, x_bs, dy, dy_bs, dw, N, Cin, Cout, P, groups, x_gs, dy_gs, dw_gs, s);
+  return with_row_tile(Cout, [&](auto bm) {
+    return launch_wgrad_split_q<decltype(bm)::value>(x, x_bs, dy, dy_bs, dw, N, Cin, Cout, P, groups, x_gs, dy_gs, dw_gs, s);
+  });
 }
 
 // ---- Winograd on the bf16x6 GEMM (conv_winograd.hip supplies the transforms): the (m+2)^2 transform-domain products as ONE
@@ -1358,9 +1205,9 @@ extern "C" int pfst_wino_gemm_split(const float* V, const void* U6, float* Mbuf,
   const int nx = (m + 2) * (m + 2);
   PFST_CHECK_ARG((i64)K * T * 4 < (1ll << 31) && (i64)M * T * 4 < (1ll << 31) && (i64)K * M * 6 < (1ll << 31));
   hipStream_t s = (hipStream_t)stream;
-  if (M > 64) return launch_split<128>(V, (i64)K * T, U6, nullptr, Mbuf, (i64)M * T, N, K, 1, T, M, 1, T, 1, 1, 1, 0, 1, 0, nullptr, 0, nx, s);
-  if (M > 32) return launch_split<64>(V, (i64)K * T, U6, nullptr, Mbuf, (i64)M * T, N, K, 1, T, M, 1, T, 1, 1, 1, 0, 1, 0, nullptr, 0, nx, s);
-  return launch_split<32>(V, (i64)K * T, U6, nullptr, Mbuf, (i64)M * T, N, K, 1, T, M, 1, T, 1, 1, 1, 0, 1, 0, nullptr, 0, nx, s);
+  return with_row_tile(M, [&](auto bm) {
+    return launch_split<decltype(bm)::value>(V, (i64)K * T, U6, nullptr, Mbuf, (i64)M * T, N, K, 1, T, M, 1, T, 1, 1, 1, 0, 1, 0, nullptr, 0, nx, s);
+  });
 }
 
 // plain[(m+2)^2][Cout][Cin] transform-domain filters (pfst_wino_filter_plain: normal and flipped) -> split-packed sets of 6*Cout*Cin bytes

@@ -12,7 +12,7 @@
 // Split-K over images and pixel chunks, fp32 atomics into the flat gradient arena -- as conv_wgrad_kernel (conv_mfma.hip),
 // which remains the generic path (stride 2, ragged widths).
 #include "common.h"
-#include "det.h"
+#include "wgrad_launch.h"
 #include "amax.h"
 #include "../../include/pfst_hip.h"
 #include <stdlib.h>
@@ -488,39 +488,17 @@ int launch_q(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, in
              int Ho, int Wo, int dil, int pad, int groups, i64 x_gs, i64 dy_gs, i64 dw_gs, hipStream_t s) {
   const int P = Ho * Wo, J = Cin * T;
   const int tiles = cdiv(J, QBJ) * cdiv(M, BM) * groups;
-  // split-K chunking: whole rounds of resident blocks (see launch_wgrad_k in conv_mfma.hip); 32 KB LDS at WBK = 16, 64 KB at 32
-  const double slots = 256.0 * (WBK == 16 ? 4 : 2);
-  int chunks = 1;
-  double best = -1.0;
-  for (int c = 1; c <= 64 && (c == 1 || P / c >= 512); ++c) {
-    const double rounds = (double)tiles * N * c / slots;
-    const double eff = rounds < 2.0 ? 0.45 * rounds : rounds / ceil(rounds);
-    if (eff > best + 0.02) { best = eff; chunks = c; }
-    if (eff >= 0.93) break;
-  }
-  int chunk_len = ((cdiv(P, chunks) + WBK - 1) / WBK) * WBK;
-  chunks = cdiv(P, chunk_len);
+  // resident workgroups: 32 KB of LDS at WBK = 16 (4 per CU), 64 KB at 32 (2 per CU)
+  const SplitK k = plan_split_k((i64)tiles * N, P, 256 * (WBK == 16 ? 4 : 2), WBK);
   constexpr int xcd_env = 1;
-  const int gx = cdiv(J, QBJ), gy = cdiv(M, BM), gz = N * groups * chunks;
+  const int gx = cdiv(J, QBJ), gy = cdiv(M, BM), gz = N * groups * k.chunks;
   PFST_CHECK_ARG((i64)gx * gy * gz < (1ll << 31));
-  dim3 grid(gx * gy * gz);
-  // occupancy cap (pfst_conv_wgrad_set_lds_pad): unused dynamic LDS, so that fewer workgroups fit per CU and a concurrently running
-  // HBM-bound kernel of another stream finds registers and wave slots
-  const i64 elems = (i64)M * J;
-  bool det_ok;
-  float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_DET(det_ok);
-  hipLaunchKernelGGL((conv_wgrad_q_kernel<BM, T, WBK>), grid, dim3(256), g_wgrad_lds_pad, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho, Wo,
-                     dil, pad, chunks, chunk_len, N, x_gs, dy_gs, ws ? -elems : dw_gs, gx, gy, gz, xcd_env);
-  if (ws) wgrad_det_reduce(ws, dw, elems, groups, N * chunks, dw_gs, s);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
-}
-
-template <int BM, int T>
-int launch_q_bk(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, int N, int Cin, int Hi, int Wi, int M,
-                int Ho, int Wo, int dil, int pad, int groups, i64 x_gs, i64 dy_gs, i64 dw_gs, hipStream_t s) {
-  return launch_q<BM, T, 16>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, M, Ho, Wo, dil, pad, groups, x_gs, dy_gs, dw_gs, s);
+  // g_wgrad_lds_pad, the occupancy cap (pfst_conv_wgrad_set_lds_pad): unused dynamic LDS, so that fewer workgroups fit per CU and a
+  // concurrently running HBM-bound kernel of another stream finds registers and wave slots
+  return wgrad_launch(dw, (i64)M * J, groups, N * k.chunks, dw_gs, s, [&](float* dst, i64 group_stride, i64) {
+    hipLaunchKernelGGL((conv_wgrad_q_kernel<BM, T, WBK>), dim3(gx * gy * gz), dim3(256), g_wgrad_lds_pad, s, x, x_bs, dy, dy_bs, dst, Cin, Hi, Wi, M, Ho,
+                       Wo, dil, pad, k.chunks, k.chunk_len, N, x_gs, dy_gs, group_stride, gx, gy, gz, xcd_env);
+  });
 }
 
 template <int BM, int T>
@@ -529,29 +507,14 @@ int launch_q16(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, 
   constexpr int WBK = 16;
   const int P = Ho * Wo, J = Cin * T;
   const int tiles = cdiv(J, QBJ) * cdiv(M, BM);
-  const double slots = 256.0 * 4;                // as launch_q at WBK = 16 (same LDS footprint)
-  int chunks = 1;
-  double best = -1.0;
-  for (int c = 1; c <= 64 && (c == 1 || P / c >= 512); ++c) {
-    const double rounds = (double)tiles * N * c / slots;
-    const double eff = rounds < 2.0 ? 0.45 * rounds : rounds / ceil(rounds);
-    if (eff > best + 0.02) { best = eff; chunks = c; }
-    if (eff >= 0.93) break;
-  }
-  int chunk_len = ((cdiv(P, chunks) + WBK - 1) / WBK) * WBK;
-  chunks = cdiv(P, chunk_len);
+  const SplitK k = plan_split_k((i64)tiles * N, P, 256 * 4, WBK);      // as launch_q at WBK = 16 (same LDS footprint)
   constexpr int xcd_env = 1;
-  const int gx = cdiv(J, QBJ), gy = cdiv(M, BM), gz = N * chunks;
+  const int gx = cdiv(J, QBJ), gy = cdiv(M, BM), gz = N * k.chunks;
   PFST_CHECK_ARG((i64)gx * gy * gz < (1ll << 31));
-  const i64 elems = (i64)M * J;
-  bool det_ok;
-  float* const ws = wgrad_det_scratch(elems, gz, s, det_ok);          // deterministic mode (det.h): one scratch tile-set per grid slice
-  PFST_CHECK_DET(det_ok);
-  hipLaunchKernelGGL((conv_wgrad_q16_kernel<BM, T>), dim3(gx * gy * gz), dim3(256), g_wgrad_lds_pad, s, x, x_bs, dy, dy_bs, ws ? ws : dw, Cin, Hi, Wi, M, Ho,
-                     Wo, dil, pad, chunks, chunk_len, N, (i64)0, (i64)0, ws ? -elems : (i64)0, gx, gy, gz, xcd_env, x_amax, dy_amax);
-  if (ws) wgrad_det_reduce(ws, dw, elems, 1, N * chunks, 0, s);
-  PFST_CHECK_LAUNCH();
-  return PFST_OK;
+  return wgrad_launch(dw, (i64)M * J, 1, N * k.chunks, 0, s, [&](float* dst, i64 group_stride, i64) {
+    hipLaunchKernelGGL((conv_wgrad_q16_kernel<BM, T>), dim3(gx * gy * gz), dim3(256), g_wgrad_lds_pad, s, x, x_bs, dy, dy_bs, dst, Cin, Hi, Wi, M, Ho, Wo,
+                       dil, pad, k.chunks, k.chunk_len, N, (i64)0, (i64)0, group_stride, gx, gy, gz, xcd_env, x_amax, dy_amax);
+  });
 }
 
 }  // namespace
@@ -569,13 +532,11 @@ extern "C" int pfst_conv_wgrad_f16x3_q(const float* x, long long x_bs, const flo
   }
   hipStream_t s = (hipStream_t)stream;
   const int pad = ksize == 3 ? dil : 0;
-#define PFST_WGQ16(BM_)                                                                                                         \
-  return ksize == 3 ? launch_q16<BM_, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, H, W, Cout, H, W, dil, pad, x_amax, dy_amax, s)         \
-                    : launch_q16<BM_, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, H, W, Cout, H, W, dil, pad, x_amax, dy_amax, s)
-  if (Cout > 64) { PFST_WGQ16(128); }
-  if (Cout > 32) { PFST_WGQ16(64); }
-  PFST_WGQ16(32);
-#undef PFST_WGQ16
+  return with_row_tile(Cout, [&](auto bm) {
+    constexpr int BM = decltype(bm)::value;
+    return ksize == 3 ? launch_q16<BM, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, H, W, Cout, H, W, dil, pad, x_amax, dy_amax, s)
+                      : launch_q16<BM, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, H, W, Cout, H, W, dil, pad, x_amax, dy_amax, s);
+  });
 }
 
 // true if the quad path applies (the caller has validated the geometry already)
@@ -589,13 +550,11 @@ bool pfst_wgrad_q_eligible(const float* x, i64 x_bs, const float* dy, i64 dy_bs,
 
 int pfst_wgrad_q_launch(const float* x, i64 x_bs, const float* dy, i64 dy_bs, float* dw, int N, int Cin, int Hi, int Wi, int Cout,
                         int Ho, int Wo, int ksize, int dil, int pad, int groups, i64 x_gs, i64 dy_gs, i64 dw_gs, hipStream_t s) {
-#define PFST_WGQ(BM_)                                                                                                                        \
-  return ksize == 3 ? launch_q_bk<BM_, 9>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, dil, pad, groups, x_gs, dy_gs, dw_gs, s)      \
-                    : launch_q_bk<BM_, 1>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, dil, pad, groups, x_gs, dy_gs, dw_gs, s)
-  if (Cout > 64) { PFST_WGQ(128); }
-  if (Cout > 32) { PFST_WGQ(64); }
-  PFST_WGQ(32);
-#undef PFST_WGQ
+  return with_row_tile(Cout, [&](auto bm) {
+    constexpr int BM = decltype(bm)::value;
+    return ksize == 3 ? launch_q<BM, 9, 16>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, dil, pad, groups, x_gs, dy_gs, dw_gs, s)
+                      : launch_q<BM, 1, 16>(x, x_bs, dy, dy_bs, dw, N, Cin, Hi, Wi, Cout, Ho, Wo, dil, pad, groups, x_gs, dy_gs, dw_gs, s);
+  });
 }
 
 extern "C" int pfst_conv_wgrad_set_lds_pad(int bytes) {

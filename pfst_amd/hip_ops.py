@@ -503,6 +503,15 @@ def set_wgrad_lds_pad(nbytes):
     call('pfst_conv_wgrad_set_lds_pad', int(nbytes))
 
 
+def wgrad_split_k(work, p, slots=0, k_step=0, chunk_cap=0, doubling=False):
+    """(chunks, chunk_len) of a weight-gradient launch of `work` workgroups over `p` pixels: the library's own split-K planner
+    (pfst_wgrad_split_k; host arithmetic, no device)"""
+    chunks, chunk_len = ctypes.c_int(0), ctypes.c_int(0)
+    call('pfst_wgrad_split_k', int(work), int(p), int(slots), int(k_step), int(chunk_cap), int(bool(doubling)), ctypes.addressof(chunks),
+         ctypes.addressof(chunk_len))
+    return chunks.value, chunk_len.value
+
+
 def wino_tiles(h, w, dil, m=None):
     return lib().pfst_wino_tiles(h, w, dil, _wino_m(m)[0])
 

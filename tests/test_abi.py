@@ -26,6 +26,26 @@ def test_argument_validation_without_gpu():
     assert L.pfst_conv_igemm(None, 0, None, None, None, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, None, None, None) == -1
 
 
+def test_conv_geometry_refusals_name_the_condition():
+    """one geometry rule (csrc/conv_launch.h) behind the five forward / data-gradient / weight-gradient entry points: a wrong output size or
+    kernel size is PFST_ERR_ARG, and the message is the violated condition"""
+    L = _lib.lib()
+    p = 256          # any non-null address: refused before anything is launched
+    # (Hi, Wi, Ho, Wo, ksize, stride, dil, pad, mode) -> what the message must contain
+    cases = [((8, 8, 9, 8, 3, 1, 1, 1, 0), b'Ho == (Hi + 2 * pad - span - 1) / stride + 1'),
+             ((8, 8, 4, 4, 3, 2, 1, 1, 1), b'Hi == (Ho + 2 * pad - span - 1) / stride + 1'),      # data gradient: 8 = out of a 15 / 16 input
+             ((8, 8, 8, 8, 5, 1, 1, 2, 0), b'ksize == 1 || ksize == 3')]
+    for (Hi, Wi, Ho, Wo, k, s, d, pad, mode), msg in cases:
+        assert L.pfst_conv_igemm(p, 16 * Hi * Wi, p, None, p, 16 * Ho * Wo, 1, 16, Hi, Wi, 16, Ho, Wo, k, s, d, pad, mode, 0, None, None, None) == -1
+        assert msg in L.pfst_last_error(), L.pfst_last_error()
+        assert L.pfst_conv_igemm_split(p, 16 * Hi * Wi, p, None, p, 16 * Ho * Wo, 1, 16, Hi, Wi, 16, Ho, Wo, k, s, d, pad, mode, 0, None, None, None) == -1
+        assert msg in L.pfst_last_error(), L.pfst_last_error()
+        if mode == 0:
+            for fn in (L.pfst_conv_wgrad, L.pfst_conv_wgrad_split):
+                assert fn(p, 16 * Hi * Wi, p, 16 * Ho * Wo, p, 1, 16, Hi, Wi, 16, Ho, Wo, k, s, d, pad, None) == -1
+                assert msg in L.pfst_last_error(), L.pfst_last_error()
+
+
 def test_f16x3_chain_grid_policy():
     """pfst_f16x3_chain_grid (host logic, no GPU): every tile is covered by chains of at most 8, never fewer workgroups than resident slots
     when there are that many tiles, no chain for launches that cannot chain, and the last round of workgroups is never mostly empty when a

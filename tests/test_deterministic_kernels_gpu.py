@@ -8,10 +8,10 @@ slices and a ragged last one.  Every case checks, in deterministic mode:
   2. accumulation: an output that starts out nonzero ends as prefill + gradient (every reduce kernel ends in `+=`);
   3. two launches bit-identical, and a launch on a second stream (run after the first, then synchronised) bit-identical to them;
   4. the default (atomic) mode within 1e-6 relative of it;
-  5. that the slice structure it claims is really reached (the split-K chunk choice and split_for restated below: if a heuristic changes,
-     this fails instead of quietly covering a single slice)."""
+  5. that the slice structure it claims is really reached: the split-K plan is asked of the library's own planner (ops.wgrad_split_k, held to
+     the recorded table by tests/test_wgrad_split_k_cpu.py) with the arguments the launcher passes, and must be the one the case states;
+     split_for is restated below.  If a heuristic changes, this fails instead of quietly covering a single slice."""
 import contextlib
-import math
 
 import pytest
 import torch
@@ -36,32 +36,6 @@ def rows_tile(m):
     return 128 if m > 64 else 64 if m > 32 else 32
 
 
-def wgrad_chunks(P, tiles, n, slots, k_step):
-    """-> (chunks, chunk_len): the split-K choice of csrc/conv_mfma.hip launch_wgrad_k, conv_wgrad_q.hip launch_q / launch_q16,
-    conv_split.hip launch_wgrad_split_q and conv_f16x3.hip pfst_wgrad_f16x3_launch -- the smallest split whose last round of resident
-    workgroups is >= 93 % full, else the best one; chunks of >= 512 pixels, whole K-steps"""
-    chunks, best, c = 1, -1.0, 1
-    while c <= 64 and (c == 1 or P // c >= 512):
-        rounds = tiles * n * c / slots
-        eff = 0.45 * rounds if rounds < 2.0 else rounds / math.ceil(rounds)
-        if eff > best + 0.02:
-            best, chunks = eff, c
-        if eff >= 0.93:
-            break
-        c += 1
-    chunk_len = cdiv(cdiv(P, chunks), k_step) * k_step
-    return cdiv(P, chunk_len), chunk_len
-
-
-def wgrad_split_chunks(P, tiles, n):
-    """conv_split.hip launch_wgrad_split (the bf16x6 kernel of strided / 3x3 layers): double the split while fewer than 1024 workgroups"""
-    chunks = 1
-    while tiles * n * chunks < 1024 and P // (chunks * 2) >= 512:
-        chunks *= 2
-    chunk_len = cdiv(cdiv(P, chunks), 16) * 16
-    return cdiv(P, chunk_len), chunk_len
-
-
 def bn_splits(hw, c, n):
     """bn.hip split_for: ~2048 workgroups, at least 1024 elements of a plane per split, chunks of whole float4s -> (splits, chunk)"""
     splits = min(2048 // (c * n), (hw + 1023) // 1024)
@@ -70,7 +44,9 @@ def bn_splits(hw, c, n):
     return cdiv(hw, chunk), chunk
 
 
-def assert_slices(chunks, chunk_len, P, ragged=True):
+def assert_slices(chunks, chunk_len, P, ragged=True, want=None):
+    """want: the (chunks, chunk_len) the case states"""
+    assert want is None or (chunks, chunk_len) == want, f'the planner gives {chunks} chunks of {chunk_len} over {P} pixels, the case states {want}'
     assert chunks > 1, f'a single pixel chunk ({P} pixels): the multi-slice path is not reached'
     if ragged:
         assert P % chunk_len != 0, f'{chunks} chunks of {chunk_len} cover {P} pixels exactly: no ragged last chunk'
@@ -137,13 +113,14 @@ def conv_operands(n, ci, co, H, W, k, s, d, p, seed=1):
 
 
 # ------------------------------------------------------------------------------------------------------------------- split-K weight gradients
-# (n, cin, cout, H, W, k, stride, dil, pad): chunks from wgrad_chunks in the comment
+# (n, cin, cout, H, W, k, stride, dil, pad): the split-K plan in the comment and, as (chunks, chunk_len), in WGRAD_PLANS
 WGRAD_CASES = [
     (3, 16, 16, 64, 80, 3, 1, 1, 1),       # K-quad 3x3 (W % 16 == 0): 9 chunks of 576 over 5120 pixels
     (3, 16, 192, 70, 68, 1, 1, 1, 0),      # K-quad 1x1: 9 chunks of 544 over 4760, two row tiles
     (3, 16, 16, 141, 129, 3, 2, 1, 1),     # generic kernel, stride 2: 9 chunks of 528 over 71 x 65
     (4, 16, 16, 80, 45, 3, 1, 1, 1),       # generic kernel, odd width: 7 chunks of 528 over 3600
 ]
+WGRAD_PLANS = dict(zip(WGRAD_CASES, [(9, 576), (9, 544), (9, 528), (7, 528)]))
 
 
 @pytest.mark.parametrize('case', WGRAD_CASES)
@@ -153,35 +130,36 @@ def test_conv_wgrad(ops, case):
     quad = s == 1 and ops.wgrad_q_operands_ok(x, dy) and ((k == 1 and P % 4 == 0) or (k == 3 and W % 16 == 0 and d <= 8))
     tiles = cdiv(ci * k * k, 128) * cdiv(co, rows_tile(co))
     if quad:        # conv_wgrad_q.hip launch_q: 16-deep K-steps, 4 workgroups per CU
-        ch, cl = wgrad_chunks(P, tiles, n, 256 * 4, 16)
-    else:           # conv_mfma.hip launch_wgrad_k: 16-deep steps (4 per CU) for 3x3, 32 (2 per CU) for 1x1
-        ch, cl = wgrad_chunks(P, tiles, n, 256 * (4 if k == 3 else 2), 16 if k == 3 else 32)
+        ch, cl = ops.wgrad_split_k(tiles * n, P, 256 * 4, 16)
+    else:           # conv_mfma.hip launch_wgrad_k: 16-deep steps (4 per CU) for 3x3, 32 (2 per CU) for 1x1; N * chunks is gridDim.z
+        ch, cl = ops.wgrad_split_k(tiles * n, P, 256 * (4 if k == 3 else 2), 16 if k == 3 else 32, chunk_cap=65535 // n)
     assert quad == (case in WGRAD_CASES[:2])
-    assert_slices(ch, cl, P)
+    assert_slices(ch, cl, P, want=WGRAD_PLANS[case])
     check_det(ops, lambda o: [ops.conv_wgrad_(o[0], x, dy, k, s, d, p)], [('dw', ref, 5e-5, True)], f'wgrad {"quad" if quad else "generic"}')
 
 
 @pytest.mark.parametrize('case', [(3, 16, 192, 70, 52, 1, 1, 1, 0), (1, 16, 32, 50, 47, 3, 1, 1, 1)])
 def test_conv_wgrad_split(ops, case):
-    """bf16x6: 1x1 on the K-quad split kernel (launch_wgrad_split_q, 7 chunks), 3x3 on launch_wgrad_split (4 chunks of 592 over 2350)"""
+    """bf16x6: 1x1 on the K-quad split kernel (launch_wgrad_split_q, 7 chunks of 528 over 3640), 3x3 on launch_wgrad_split (the doubling rule:
+    4 chunks of 592 over 2350)"""
     n, ci, co, H, W, k, s, d, p = case
     x, dy, ref, P = conv_operands(*case)
     tiles = cdiv(ci * k * k, 128) * cdiv(co, rows_tile(co))
-    ch, cl = wgrad_chunks(P, tiles, n, 256 * 3, 16) if k == 1 else wgrad_split_chunks(P, tiles, n)
-    assert_slices(ch, cl, P)
+    ch, cl = ops.wgrad_split_k(tiles * n, P, 256 * 3, 16) if k == 1 else ops.wgrad_split_k(tiles * n, P, doubling=True)
+    assert_slices(ch, cl, P, want=(7, 528) if k == 1 else (4, 592))
     check_det(ops, lambda o: [ops.conv_wgrad_split_(o[0], x, dy, k, s, d, p)], [('dw', ref, 3e-6, True)], f'split wgrad {k}x{k}')
 
 
 @pytest.mark.parametrize('bnl', [False, True])
 @pytest.mark.parametrize('case', [(2, 16, 256, 70, 52), (3, 16, 96, 70, 68)])
 def test_conv_wgrad_f16x3(ops, case, bnl):
-    """the whole-line f16x3 1x1 weight gradient: the 256-row tile (M % 256 == 0: 7 chunks) and the 128-row one (9 chunks); bnl: x is the
-    PRE-normalisation tensor, normalised on load"""
+    """the whole-line f16x3 1x1 weight gradient: the 256-row tile (M % 256 == 0: 7 chunks of 528 over 3640) and the 128-row one (9 chunks of
+    544 over 4760); bnl: x is the PRE-normalisation tensor, normalised on load"""
     n, ci, co, H, W = case
     P = H * W
     big = co % 256 == 0
-    ch, cl = wgrad_chunks(P, cdiv(ci, 128) * cdiv(co, 256 if big else 128), n, 256 if big else 512, 16)
-    assert_slices(ch, cl, P)
+    ch, cl = ops.wgrad_split_k(cdiv(ci, 128) * cdiv(co, 256 if big else 128) * n, P, 256 if big else 512, 16)
+    assert_slices(ch, cl, P, want=(7, 528) if big else (9, 544))
     dy = torch.randn(n, co, H, W, generator=g(4)).to(DEV)
     if bnl:
         pre = (torch.randn(n, ci, H, W, generator=g(1)) * 1.5).to(DEV)
@@ -205,8 +183,8 @@ def test_conv_wgrad_f16q(ops, dil):
     case = (3, 16, 16, 64, 80, 3, 1, dil, dil)
     n, ci, co, H, W, k = case[:6]
     x, dy, ref, P = conv_operands(*case)
-    ch, cl = wgrad_chunks(P, cdiv(ci * 9, 128) * cdiv(co, rows_tile(co)), n, 256 * 4, 16)
-    assert_slices(ch, cl, P)
+    ch, cl = ops.wgrad_split_k(cdiv(ci * 9, 128) * cdiv(co, rows_tile(co)) * n, P, 256 * 4, 16)
+    assert_slices(ch, cl, P, want=(9, 576))
     xa, da = ops.absmax(x), ops.absmax(dy)
     check_det(ops, lambda o: [ops.conv_wgrad_f16q_(o[0], x, dy, xa, da, 3, dil)], [('dw', ref, 3e-6, True)], f'f16x3 quad wgrad dil={dil}')
 
@@ -216,14 +194,15 @@ def test_conv_wgrad_f16q(ops, dil):
 def test_wino_wgrad(ops, m, split):
     """the grouped transform-domain products of the Winograd weight gradient: (m+2)^2 groups of N * chunks slices each, dU of group xi at
     xi * Cout * Cin (dw_gs) -- fp32 K-quad (split 0), bf16x6 (1), f16x3 on pre-split operands (2).  2 x 16 -> 96 channels at 160 x 160:
-    T = 6400 (m = 2) / 1600 (m = 4) tiles per image, 3 ... 12 chunks with a ragged last one."""
+    T = 6400 (m = 2) / 1600 (m = 4) tiles per image, 3 ... 12 chunks with a ragged last one: at m = 2, 11 chunks of 592 (split 0 and 1) and
+    12 of 544 (split 2); at m = 4, 3 chunks of 544."""
     n, ci, co, H, W, d = 2, 16, 96, 160, 160, 1
     nx, T = (m + 2) ** 2, ops.wino_tiles(H, W, d, m)
     if split == 2:          # pfst_wgrad_f16x3_launch (packed operands); co % 256 != 0: the 128-row tile, 2 per CU
-        ch, cl = wgrad_chunks(T, cdiv(ci, 128) * cdiv(co, 128) * nx, n, 512, 16)
+        ch, cl = ops.wgrad_split_k(cdiv(ci, 128) * cdiv(co, 128) * nx * n, T, 512, 16)
     else:                   # pfst_wgrad_q_launch (1x1 over the tile index) / pfst_wgrad_split_q_launch
-        ch, cl = wgrad_chunks(T, cdiv(ci, 128) * cdiv(co, rows_tile(co)) * nx, n, 1024 if split == 0 else 768, 16)
-    assert_slices(ch, cl, T)
+        ch, cl = ops.wgrad_split_k(cdiv(ci, 128) * cdiv(co, rows_tile(co)) * nx * n, T, 1024 if split == 0 else 768, 16)
+    assert_slices(ch, cl, T, want=(3, 544) if m == 4 else (12, 544) if split == 2 else (11, 592))
     x = torch.randn(n, ci, H, W, generator=g(1)).to(DEV)
     dy = torch.randn(n, co, H, W, generator=g(4)).to(DEV)
     ref = torch.nn.grad.conv2d_weight(x.double().cpu(), (co, ci, 3, 3), dy.double().cpu(), 1, d, d)
@@ -510,7 +489,7 @@ def test_det_scratch_regrowth(ops):
     n, ci, co, H, W = 2, 128, 256, 48, 64
     xl, dyl, ref_l, P = conv_operands(n, ci, co, H, W, 3, 1, 1, 1)
     assert ops.wgrad_q_operands_ok(xl, dyl)
-    ch, cl = wgrad_chunks(P, cdiv(ci * 9, 128) * cdiv(co, 128), n, 256 * 4, 16)
+    ch, cl = ops.wgrad_split_k(cdiv(ci * 9, 128) * cdiv(co, 128) * n, P, 256 * 4, 16)
     assert 4 * co * ci * 9 * n * ch > 8 << 20, 'the large launch must outgrow the first scratch allocation'
     streams = [torch.cuda.Stream() for _ in range(9)]
     assert len({s.cuda_stream for s in streams}) == 9

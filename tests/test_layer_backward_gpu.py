@@ -82,7 +82,7 @@ def test_every_backward_link_as_wired_at_1024():
     from pfst_amd import hip_ops as ops
     from pfst_amd import layers
     from pfst_amd._lib import lib
-    from test_deterministic_kernels_gpu import cdiv, wgrad_chunks
+    from test_deterministic_kernels_gpu import cdiv
 
     b, S = 2, 1024
     info = _every_backward_link_as_wired(True, True, 'f16x3', S=S, ref_dev='cuda')
@@ -101,7 +101,7 @@ def test_every_backward_link_as_wired_at_1024():
     chunks = {}
     for kind, n, ci, co, P, groups in info['wgrad']:
         big = co % 256 == 0
-        ch, _ = wgrad_chunks(P, cdiv(ci, 128) * cdiv(co, 256 if big else 128) * groups, n, 256 if big else 512, 16)
+        ch, _ = ops.wgrad_split_k(cdiv(ci, 128) * cdiv(co, 256 if big else 128) * groups * n, P, 256 if big else 512, 16)
         chunks.setdefault((kind, ci, co, P if kind == '1x1' else None), set()).add(ch)      # Winograd: P = tiles per plane
     for k, v in sorted(chunks.items(), key=str):
         print(f'   weight gradient {k}: {sorted(v)} K chunks')
