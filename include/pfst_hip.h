@@ -686,6 +686,23 @@ int pfst_lovasz_upsample_bwd(const float* logits, int N, int C, int h, int w, co
                              const float* coef_map, const float* scale, float grad_scale, float* work, float* dlogits,
                              int accumulate, pfst_stream_t stream);
 
+/* ---- EntropyLoss on low-resolution logits (losses/entropy_loss.py:27-42), csrc/entropy_loss.hip ----
+ * logits[N][C][HW] dense, p = softmax_c(logits) = exp(z - max) / sum, one pixel per thread, no resize.
+ *   kind 0 (entropy, MinEnt):  loss =  weight / (N HW) * sum_px -sum_c p_c log2(p_c + 1e-30) / log2(C)
+ *   kind 1 (max_square):       loss = -weight / (2 N C HW) * sum_px sum_c p_c^2
+ * 2 <= C <= 255 (C = 1: log2(1) = 0, the reference's division by zero, PFST_ERR_ARG).  form: 0 = by C (C <= 8: the logits of a pixel in
+ * registers, else a loop over the classes), 1 = the loop at any C (tests compare the two on one shape; same operations, same bits).
+ * workspace: pfst_softmax_entropy_workspace_bytes bytes, 8-byte aligned, any contents: N * ceil(HW / 256) fp64 partials, one STORED per
+ * workgroup; a single workgroup adds them in a fixed order and writes out[0].  No atomics: bit-identical run to run in every mode. */
+int pfst_softmax_entropy_workspace_bytes(int N, long long HW, long long* bytes);
+int pfst_softmax_entropy_fwd(const float* logits, int N, int C, long long HW, int kind, int form, double weight, double* workspace,
+                             float* out, pfst_stream_t stream);
+/* dlogits (+)= grad_scale * p_j (g_j - sum_c p_c g_c) with p formed again from the logits (nothing is kept from the forward pass) and
+ * g_c = dloss/dp_c:  kind 0: -(log2(p_c + 1e-30) + p_c / ((p_c + 1e-30) ln 2)) / log2(C) * weight / (N HW);  kind 1: -p_c weight / (N C HW).
+ * accumulate: 0 writes, 1 adds (the value that 0 writes, exactly).  dlogits[N][C][HW] dense; it may not overlap logits */
+int pfst_softmax_entropy_bwd(const float* logits, int N, int C, long long HW, int kind, int form, double weight, float grad_scale,
+                             float* dlogits, int accumulate, pfst_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

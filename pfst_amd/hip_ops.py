@@ -1566,6 +1566,48 @@ def lovasz_upsample_bwd(logits, label_u8, slot, cls, lse, cmap, scale, grad_scal
     return out
 
 
+ENTROPY_KINDS = {'entropy': 0, 'max_square': 1}
+
+
+def _entropy_args(logits, kind):
+    """logits [N, C, h, w]: dense, at any offset of its storage (data_ptr carries it); a strided view is refused, as by the other loss wrappers"""
+    _chk(logits, F32, 4)
+    if not logits.is_contiguous():
+        raise ValueError(f'softmax_entropy: logits must be dense NCHW (shape {tuple(logits.shape)}, strides {logits.stride()}); '
+                         'pass .contiguous()')
+    if kind not in ENTROPY_KINDS:
+        raise ValueError(f'softmax_entropy: kind must be one of {tuple(ENTROPY_KINDS)}, got {kind!r}')
+    n, c, h, w = logits.shape
+    return n, c, h * w, ENTROPY_KINDS[kind]
+
+
+def softmax_entropy(logits, kind, weight, generic=False):
+    """EntropyLoss of low-resolution logits [N, C, h, w] (pfst_softmax_entropy_fwd): kind 'entropy' = weight * mean_px of the normalised
+    entropy of softmax_c, 'max_square' = -weight * mean(p^2) / 2.  Per-workgroup fp64 partials + one ordered sum, no atomics: bit-identical
+    run to run in every mode.  generic=True forces the class-loop kernels at C <= 8 (tests).  -> float32 [1] on the device"""
+    n, c, hw, k = _entropy_args(logits, kind)
+    nbytes = ctypes.c_longlong(0)
+    call('pfst_softmax_entropy_workspace_bytes', n, hw, ctypes.addressof(nbytes))
+    work = torch.empty(nbytes.value // 8, dtype=F64, device=logits.device)
+    out = torch.empty(1, device=logits.device)
+    call('pfst_softmax_entropy_fwd', logits.data_ptr(), n, c, hw, k, int(bool(generic)), float(weight), work.data_ptr(), out.data_ptr(),
+         _stream())
+    return out
+
+
+def softmax_entropy_bwd_(dlogits, logits, kind, weight, grad_scale=1.0, accumulate=True, generic=False):
+    """dlogits (+)= grad_scale * d softmax_entropy(logits, kind, weight) / d logits, the probabilities formed again from the logits.
+    accumulate=False writes every element of dlogits.  Both tensors dense (an offset view is fine), same shape, not overlapping"""
+    n, c, hw, k = _entropy_args(logits, kind)
+    _chk(dlogits, F32, 4)
+    if not dlogits.is_contiguous() or dlogits.shape != logits.shape:
+        raise ValueError(f'softmax_entropy_bwd_: dlogits must be dense with the logits\' shape {tuple(logits.shape)}, got shape '
+                         f'{tuple(dlogits.shape)} strides {dlogits.stride()}')
+    call('pfst_softmax_entropy_bwd', logits.data_ptr(), n, c, hw, k, int(bool(generic)), float(weight), float(grad_scale), dlogits.data_ptr(),
+         int(bool(accumulate)), _stream())
+    return dlogits
+
+
 def pseudo_label(logits, size, threshold, want_i64=True, want_conf=False, want_prob=False):
     """-> (label int64 [N,H,W] | None, label uint8 [N,H,W], count uint64-as-int64 [1][, conf float [N,H,W]][, max prob float [N,H,W]])"""
     _dense(logits)

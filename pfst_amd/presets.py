@@ -59,6 +59,17 @@ def uda_cfg(num_classes=6, in_channels=3, dropout=0.1, blur=True, color_jitter_p
         model=model_cfg(num_classes, in_channels, dropout), max_iters=max_iters)
 
 
+def dacs_uda_cfg(num_classes=6, in_channels=3, dropout=0.1, blur=True, color_jitter_probability=0.2, pseudo_threshold=0.968,
+                 max_iters=40000):
+    """The DACS self-training baseline with the values of the reference's configs/_base_/uda/dacs.py:7-22: uda_cfg's arguments without
+    the PFGSTLoss ones, no auxiliary losses"""
+    return dict(
+        type='DACS', alpha=0.99, pseudo_threshold=pseudo_threshold, pseudo_weight_ignore_top=0, pseudo_weight_ignore_bottom=0,
+        imnet_feature_dist_lambda=0, imnet_feature_dist_classes=None, imnet_feature_dist_scale_min_ratio=None, mix='class', blur=blur,
+        color_jitter_strength=0.2, color_jitter_probability=color_jitter_probability, debug_img_interval=1000, print_grad_magnitude=False,
+        model=model_cfg(num_classes, in_channels, dropout), max_iters=max_iters)
+
+
 OPTIMIZER = dict(type='AdamW', lr=6e-5, betas=(0.9, 0.999), weight_decay=0.01)
 LR_CONFIG = dict(policy='poly', warmup='linear', warmup_iters=1500, warmup_ratio=1e-6, power=1.0, min_lr=0.0, by_epoch=False)
 

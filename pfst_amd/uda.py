@@ -1,7 +1,8 @@
 """PFGST self-training wrapper and PFGSTLoss on the HIP path, behind the reference's plugin API:
-`UDA.build(cfg.uda)` -> object with `train_step(data_batch, optimizer) -> {log_vars, num_samples, states}`.
+`UDA.build(cfg.uda)` -> object with `train_step(data_batch, optimizer) -> {log_vars, num_samples, states}`; the self-training baselines
+on the same step: DACS (no auxiliary losses, the mix pasted onto the plain target image) and EntropyLoss (MinEnt, max-squares).
 
-Reference: rsiseg/models/uda/pfgst.py:53-368, uda_decorator.py:13-103, losses/pfgst_loss.py:12-234,
+Reference: rsiseg/models/uda/pfgst.py:53-368, dacs.py:50-272, uda_decorator.py:13-103, losses/pfgst_loss.py:12-234, losses/entropy_loss.py,
 utils/dacs_transforms.py:12-144, segmentors/base.py:177-222.
 
 Differences from the reference that are deliberate:
@@ -145,6 +146,46 @@ class PFGSTLoss(nn.Module):
             # with torch ops because it is off the hot path (PFGST.return_vis_states)
             out['vis|density_sim_feat'] = (tensors.get('img_trg'), 1 - ema_sim.mean(dim=1, keepdim=True), all9.bool())
         return out
+
+
+@LOSSES.register_module()
+class EntropyLoss(nn.Module):
+    """Entropy minimisation (MinEnt, loss_type='entropy') and the max-squares loss (loss_type='max_square') on the student's logits of the
+    mixed pass: rsiseg/models/losses/entropy_loss.py, the reference's signature.  An auxiliary loss of PFGST (`uda.aux_losses`), reading the
+    same `tensors` dict as PFGSTLoss; hip_ops.softmax_entropy: two launches forward, one backward, no probability map kept.  What the
+    reference finds out in forward is refused here at construction: an unknown loss_type (its ValueError), weights without the key that the
+    type reads (its KeyError / TypeError)."""
+    WEIGHT_KEYS = {'entropy': 'loss_ent', 'max_square': 'loss_max_square'}
+
+    def __init__(self, loss_type='entropy', weights=None, **kwards):
+        super().__init__()
+        if loss_type not in self.WEIGHT_KEYS:
+            raise ValueError(f'EntropyLoss: loss_type must be one of {tuple(self.WEIGHT_KEYS)}, got {loss_type!r}')
+        key = self.WEIGHT_KEYS[loss_type]
+        if not isinstance(weights, dict) or key not in weights:
+            raise KeyError(f'EntropyLoss(loss_type={loss_type!r}) reads weights[{key!r}]: weights must be a dict with that key, got {weights!r}')
+        self.loss_type = loss_type
+        self._loss_name = f'loss_{loss_type}'
+        self.weights = dict(weights)
+        self.key = key
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+    def forward(self, tensors, tape=None):
+        """tensors: logits_trg (Var, student logits of the mixed pass) -> {'loss_ent' | 'loss_max_square': one-element device tensor}"""
+        lt = tensors['logits_trg']
+        kind, weight = self.loss_type, float(self.weights[self.key])
+        loss = ops.softmax_entropy(lt.data, kind, weight)
+        if tape is not None:
+            def bwd():
+                buf, acc = lt.grad_target()
+                ops.softmax_entropy_bwd_(buf, lt.data, kind, weight, accumulate=acc)
+            # tagged like every closure of the network (PFGSTLoss above): it writes or adds to dL/dlogits_trg, into which the mixed pass's
+            # CE backward accumulates afterwards
+            tape.record(bwd, tag=dict(op='entropy_loss', out=None, module=self, logits_trg=lt))
+        return OrderedDict([(self.key, loss)])
 
 
 def get_module(module):
@@ -585,3 +626,26 @@ class PFGST(UDADecorator):
             vis_states['vis|seg_mask_mix'] = (mixed_img, vis_mix, arg(mixed_logits.data).float())
         self.local_iter += 1
         return log_vars, vis_states
+
+
+@UDA.register_module()
+class DACS(PFGST):
+    """The self-training baseline of the PFST tables (rsiseg/models/uda/dacs.py, configs/_base_/uda/dacs.py): PFGST's step without auxiliary
+    losses, the class mix pasted onto `target_img` (dacs.py:253) instead of its strongly augmented copy, the same colour jitter and blur
+    behind it.  It IS that step -- EMA teacher, arenas, `local_iter` extra state, stream schedule, early log read, test hooks -- called with
+    `target_img` in the place of `target_img_strong_aug`; the reference's two backward calls (source, then mixed: dacs.py:210,268) add up
+    to the one sweep here.  A `target_img_strong_aug` entry of the batch (the loaders add one whenever the pipeline has the step) is ignored;
+    `debug_img_interval` is accepted and ignored (no plotting).  `train_step` returns log_vars and num_samples, as dacs.py:147-149."""
+
+    def __init__(self, **cfg):
+        if cfg.get('aux_losses') is not None:
+            raise NotImplementedError('DACS has no auxiliary losses (rsiseg/models/uda/dacs.py): use type=\'PFGST\' with aux_losses')
+        super().__init__(**cfg)
+
+    def train_step(self, data_batch, optimizer, **kwargs):
+        out = super().train_step(data_batch, optimizer, **kwargs)
+        out.pop('states')
+        return out
+
+    def forward_train(self, img, img_metas, gt_semantic_seg, target_img, target_img_metas, target_img_strong_aug=None):
+        return super().forward_train(img, img_metas, gt_semantic_seg, target_img, target_img_metas, target_img)

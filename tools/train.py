@@ -14,7 +14,11 @@ builds a bare EncoderDecoder (registry.build_train_model) whose own train_step r
 `--supervised` drops the `uda` section of a config or preset (a UDADataset in data.train is replaced by its `source` entry; a preset takes
 schedule_40k's SGD + poly schedule); `--supervised --model pspnet|deeplabv3|fcn` swaps in the reference's comparison models (PSPNet,
 DeepLabV3, FCN: presets.baseline_model_cfg) on the same backbone, `--synthetic` included.  Checkpoints of such a run have bare keys: tools/test.py reads them without key revision, and
-`--init-student-from CKPT` starts a self-training run (a `uda` config) with them in both the student and the EMA teacher."""
+`--init-student-from CKPT` starts a self-training run (a `uda` config) with them in both the student and the EMA teacher.
+
+Self-training baselines: `--uda dacs` swaps the `uda` section for DACS (rsiseg/models/uda/dacs.py), `--synthetic` included; MinEnt and
+max-squares are PFGST with an EntropyLoss among its auxiliary losses, e.g.
+`--cfg-options "uda.aux_losses=[{'type':'EntropyLoss','loss_type':'entropy','weights':{'loss_ent':W}}]"` (W: yours to choose, README)."""
 import argparse
 import os
 import sys
@@ -33,6 +37,9 @@ def parse_args(argv=None):
     p.add_argument('--model', choices=['pspnet', 'deeplabv3', 'fcn'],
                    help='with --supervised: replace cfg.model by the comparison model of that name (presets.baseline_model_cfg: PSPHead / ASPPHead / '
                         'two-layer FCNHead on the same backbone and auxiliary head), keeping num_classes, in_channels and the backbone depth')
+    p.add_argument('--uda', choices=['dacs'],
+                   help='replace the `uda` section of the config or preset by the DACS self-training baseline (presets.dacs_uda_cfg: the values of '
+                        "the reference's configs/_base_/uda/dacs.py, no auxiliary losses), keeping strong_aug_denorm_type, a property of the data")
     p.add_argument('--resume-from')
     p.add_argument('--no-validate', action='store_true')
     g = p.add_mutually_exclusive_group()
@@ -94,6 +101,19 @@ def load_cfg(args):
         new['pretrained'] = old.get('pretrained')
         cfg.model = new
         if args.cfg_options:                                  # options addressed at the new model's keys apply to it
+            cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
+    if args.uda:
+        if args.supervised or 'uda' not in cfg:
+            raise ValueError('--uda swaps the self-training wrapper of a config with a `uda` section: it cannot be combined with --supervised '
+                             'or a supervised config')
+        from pfst_amd.presets import dacs_uda_cfg
+        old = cfg.uda
+        new = dacs_uda_cfg()
+        new.pop('model'), new.pop('max_iters')                # build_train_model hands both in (cfg.model, cfg.runner.max_iters)
+        if 'strong_aug_denorm_type' in old:
+            new['strong_aug_denorm_type'] = old['strong_aug_denorm_type']
+        cfg.uda = new
+        if args.cfg_options:                                  # options addressed at the new section's keys apply to it
             cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
     if args.max_iters:
         cfg.runner['max_iters'] = args.max_iters
