@@ -703,6 +703,39 @@ int pfst_softmax_entropy_fwd(const float* logits, int N, int C, long long HW, in
 int pfst_softmax_entropy_bwd(const float* logits, int N, int C, long long HW, int kind, int form, double weight, float grad_scale,
                              float* dlogits, int accumulate, pfst_stream_t stream);
 
+/* ---- adversarial baseline (ADVENT): the per-class entropy map, csrc/entropy_loss.hip (losses/adv_loss.py:47-50, 77-81, 96-97) ----
+ * ent[n][c][px] = -p_c log2(p_c + 1e-30) / log2(C), p = softmax_c(logits) as above: C channels at the logits' own resolution, NOT summed
+ * over the classes.  logits, ent, grad_ent, dlogits: [N][C][HW] dense; 2 <= C <= 255; form as pfst_softmax_entropy_fwd.  One pixel per
+ * thread, the class walk of the EntropyLoss kernels (csrc/entropy_walk.h), nothing kept between forward and backward. */
+int pfst_entropy_map(const float* logits, int N, int C, long long HW, int form, float* ent, pfst_stream_t stream);
+/* dlogits (+)= p_j (G_j - sum_c p_c G_c), G_c = grad_ent[c] * -(log2(p_c + 1e-30) + p_c / ((p_c + 1e-30) ln 2)) / log2(C): through the
+ * entropy term and the softmax.  accumulate: 0 writes every element, 1 adds (the value that 0 writes, exactly) */
+int pfst_entropy_map_bwd(const float* logits, const float* grad_ent, int N, int C, long long HW, int form, float* dlogits, int accumulate,
+                         pfst_stream_t stream);
+
+/* ---- adversarial baseline: the discriminator's convolutions, csrc/adv_conv.hip (discriminators/fc_discriminator.py:8-19) ----
+ * Conv2d(kernel 4, stride 2, padding 1, bias): x[N][Cin][Hi][Wi] -> y[N][Cout][Ho][Wo], Ho = Hi / 2, Wo = Wi / 2 (floor; Hi, Wi >= 2),
+ * w[Cout][Cin][4][4] in torch's layout (nothing is packed), all tensors dense fp32; N <= 16383, Cout <= 65535.  Implicit GEMMs on the
+ * fp32-input MFMA, except the forward pass with Cout = 1: a reduction per output pixel (csrc/adv_tail.hip).
+ *   y = act(b + conv(x, w)),  act(v) = v > 0 ? v : slope * v when act = 1 (LeakyReLU fused into the epilogue), the identity when act = 0.
+ *   bias may be NULL. */
+int pfst_adv_conv_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Hi, int Wi, int Cout, int act,
+                      float slope, pfst_stream_t stream);
+/* dx (+)= gate * conv_transpose(dy, w): four 2x2 sub-convolutions by the parity of the input row and column; every element of dx is written.
+ * x_gate (or NULL): x itself when x is the LeakyReLU output of the layer below -- gate = x > 0 ? 1 : slope, what torch's in-place
+ * LeakyReLU differentiates (slope > 0: x > 0 iff its pre-activation was) -- so that dx is the gradient of that layer's PRE-activation. */
+int pfst_adv_conv_dgrad(const float* dy, const float* w, const float* x_gate, float* dx, int N, int Cin, int Hi, int Wi, int Cout, float slope,
+                        int accumulate, pfst_stream_t stream);
+/* dw[Cout][Cin][4][4] += sum_{n, pixels} dy x, db[Cout] += sum_{n, pixels} dy (db may be NULL).  Split over images and pixel chunks
+ * (pfst_wgrad_split_k); fp32 atomics, or per-slice scratch and an ordered sum under pfst_set_deterministic(1). */
+int pfst_adv_conv_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int Cin, int Hi, int Wi, int Cout, pfst_stream_t stream);
+/* The tail, csrc/adv_tail.hip (fc_discriminator.py:18 AdaptiveAvgPool2d(1), adv_loss.py:58-63 l1_loss): y[N][HW] is the last layer's one-channel plane.
+ *   d[n] = mean_i y[n][i] (fp64 sums in a fixed order),  loss[0] = weight * mean_n |d[n] - label|,
+ *   gy[n][i] = grad_scale * weight * sign(d[n] - label) / (N HW)  (sign(0) = 0, as torch's).  One workgroup, no atomics.
+ * d, loss, gy: each may be NULL (at least one is not). */
+int pfst_adv_tail(const float* y, int N, int HW, float label, double weight, float grad_scale, float* d, float* loss, float* gy,
+                  pfst_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,9 @@
 //   kind 0 (entropy):    e = -sum_c p_c log2(p_c + 1e-30) / log2(C)      loss =  weight * sum_px e / (N h w)
 //   kind 1 (max_square): s =  sum_c p_c^2                                loss = -weight * sum_px s / (2 N C h w)
 //
+// The same file holds the per-class entropy MAP of the adversarial baseline (adv_loss.py:47-50) and its adjoint: the same
+// class walk (entropy_walk.h), not summed over the classes.
+//
 // One pixel per thread, no up-sampling, nothing kept between forward and backward: the backward forms p again from the logits.  A workgroup
 // reduces its 256 per-pixel values (fp32 each, added in fp64) by wave shuffles and LDS and STORES one fp64 partial; a single workgroup adds
 // the partials in a fixed order.  No atomics anywhere: the result has the same bits run to run in every mode.
@@ -14,89 +17,18 @@
 // `accumulate` adds exactly the value that a plain store writes.
 #include <limits.h>
 #include "common.h"
+#include "entropy_walk.h"
 #include "../../include/pfst_hip.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int REG_C = 8;                              // classes the register form holds per thread
-constexpr float ENT_EPS = 1e-30f;                     // entropy_loss.py:29
-constexpr float INV_LN2 = 1.44269504088896340736f;
-
 // a pixel's term of the forward sum from one class
 template <int KIND>
 __device__ __forceinline__ float fwd_term(float pc, float acc) {
   return KIND == 0 ? __builtin_fmaf(pc, log2f(pc + ENT_EPS), acc) : __builtin_fmaf(pc, pc, acc);
 }
-// g_c = dL/dp_c as autograd forms it for the reference expression; k = weight / (N h w log2 C) (entropy), weight / (N C h w) (max_square)
-template <int KIND>
-__device__ __forceinline__ float seed(float pc, float k) {
-  if (KIND == 0) {
-    const float q = pc + ENT_EPS;
-    return -(log2f(q) + (pc / q) * INV_LN2) * k;
-  }
-  return -pc * k;
-}
-
-// The class walk of one pixel.  REG: the logits are read once into registers (class arrays indexed by compile-time constants only) and
-// turned into the probabilities in place; else the classes are read again in every pass (the second and later reads hit the cache) and
-// every pass forms exp(z - max) / sum again.  Both forms: the maximum, the sum of exponentials and the class terms in class order, by the
-// same operations on the same values -- the same bits.  zp: the pixel's class-0 logit, hw: the class stride.
-template <bool REG>
-struct PxLogits {
-  const float* __restrict__ zp;
-  i64 hw;
-  int C;
-  float mx, se;
-  float z[REG_C];
-  // f(c, z_c) for c = 0 .. C-1
-  template <class F>
-  __device__ __forceinline__ void each_logit(F&& f) const {
-    if (REG) {
-#pragma unroll
-      for (int c = 0; c < REG_C; ++c)
-        if (c < C) f(c, z[c]);
-    } else {
-      for (int c = 0; c < C; ++c) f(c, zp[c * hw]);
-    }
-  }
-  // p_c = exp(z_c - max) / sum: a division, as torch's softmax
-  __device__ __forceinline__ void softmax() {
-    if (REG) {
-#pragma unroll
-      for (int c = 0; c < REG_C; ++c) z[c] = c < C ? zp[c * hw] : -INFINITY;
-    }
-    float m = -INFINITY, s = 0.f;
-    each_logit([&](int, float zc) { m = zc > m ? zc : m; });
-    if (REG) {
-#pragma unroll
-      for (int c = 0; c < REG_C; ++c)
-        if (c < C) z[c] = expf(z[c] - m);
-#pragma unroll
-      for (int c = 0; c < REG_C; ++c)
-        if (c < C) s = s + z[c];
-#pragma unroll
-      for (int c = 0; c < REG_C; ++c)
-        if (c < C) z[c] = z[c] / s;
-    } else {
-      each_logit([&](int, float zc) { s = s + expf(zc - m); });
-    }
-    mx = m;
-    se = s;
-  }
-  // f(c, p_c) for c = 0 .. C-1, after softmax()
-  template <class F>
-  __device__ __forceinline__ void each(F&& f) const {
-    if (REG) {
-#pragma unroll
-      for (int c = 0; c < REG_C; ++c)
-        if (c < C) f(c, z[c]);
-    } else {
-      for (int c = 0; c < C; ++c) f(c, expf(zp[c * hw] - mx) / se);
-    }
-  }
-};
 
 // grid: (ceil(HW / 256), N); partial[n * gridDim.x + blockIdx.x] = the workgroup's sum of per-pixel values (e resp. s above, unscaled
 // but for 1 / log2 C)
@@ -146,6 +78,43 @@ __global__ __launch_bounds__(256) void entropy_bwd_kernel(const float* __restric
   px.each([&](int c, float pc) {
     const float gc = REG ? g[c] : seed<KIND>(pc, k);
     const float d = grad_scale * (pc * (gc - s));
+    dp[c * HW] = accumulate ? dp[c * HW] + d : d;
+  });
+}
+
+// The per-class entropy map that the adversarial baseline's discriminator reads (adv_loss.py:47-50): e_c = -p_c log2(p_c + 1e-30) / log2(C),
+// not summed over the classes.                                                                             grid: (ceil(HW / 256), N)
+template <bool REG>
+__global__ __launch_bounds__(256) void entropy_map_fwd_kernel(const float* __restrict__ logits, int C, i64 HW, float inv_log2c,
+                                                              float* __restrict__ ent) {
+  const i64 n = blockIdx.y, p = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  PxLogits<REG> px{logits + n * C * HW + p, HW, C};
+  px.softmax();
+  float* ep = ent + n * C * HW + p;
+  px.each([&](int c, float pc) { ep[c * HW] = -(pc * log2f(pc + ENT_EPS)) * inv_log2c; });
+}
+
+// Its adjoint: with G_c = g_e[c] * de_c/dp_c (seed<0> with k = 1 / log2 C), dz_j (+)= p_j * (G_j - sum_c p_c G_c)
+template <bool REG>
+__global__ __launch_bounds__(256) void entropy_map_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ gent, int C, i64 HW,
+                                                              float inv_log2c, float* __restrict__ dlogits, int accumulate) {
+  const i64 n = blockIdx.y, p = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  PxLogits<REG> px{logits + n * C * HW + p, HW, C};
+  px.softmax();
+  const float* gp = gent + n * C * HW + p;
+  float s = 0.f;
+  float g[REG_C];                // the register form keeps G; the class loop forms it again
+  px.each([&](int c, float pc) {
+    const float gc = gp[c * HW] * seed<0>(pc, inv_log2c);
+    if (REG) g[c] = gc;
+    s = __builtin_fmaf(pc, gc, s);
+  });
+  float* dp = dlogits + n * C * HW + p;
+  px.each([&](int c, float pc) {
+    const float gc = REG ? g[c] : gp[c * HW] * seed<0>(pc, inv_log2c);
+    const float d = pc * (gc - s);
     dp[c * HW] = accumulate ? dp[c * HW] + d : d;
   });
 }
@@ -202,3 +171,28 @@ extern "C" int pfst_softmax_entropy_bwd(const float* logits, int N, int C, long 
   return PFST_OK;
 }
 #undef PFST_ENT_DISPATCH
+
+extern "C" int pfst_entropy_map(const float* logits, int N, int C, long long HW, int form, float* ent, pfst_stream_t stream) {
+  PFST_CHECK_ARG(shape_ok(logits, N, C, HW, 0, form) && ent);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(cdiv(HW, 256), N);
+  const float inv_log2c = (float)(1.0 / log2((double)C));
+  if (form == 0 && C <= REG_C) hipLaunchKernelGGL(entropy_map_fwd_kernel<true>, grid, dim3(256), 0, s, logits, C, (i64)HW, inv_log2c, ent);
+  else hipLaunchKernelGGL(entropy_map_fwd_kernel<false>, grid, dim3(256), 0, s, logits, C, (i64)HW, inv_log2c, ent);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_entropy_map_bwd(const float* logits, const float* grad_ent, int N, int C, long long HW, int form, float* dlogits,
+                                    int accumulate, pfst_stream_t stream) {
+  PFST_CHECK_ARG(shape_ok(logits, N, C, HW, 0, form) && grad_ent && dlogits && (accumulate == 0 || accumulate == 1));
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(cdiv(HW, 256), N);
+  const float inv_log2c = (float)(1.0 / log2((double)C));
+  if (form == 0 && C <= REG_C)
+    hipLaunchKernelGGL(entropy_map_bwd_kernel<true>, grid, dim3(256), 0, s, logits, grad_ent, C, (i64)HW, inv_log2c, dlogits, accumulate);
+  else
+    hipLaunchKernelGGL(entropy_map_bwd_kernel<false>, grid, dim3(256), 0, s, logits, grad_ent, C, (i64)HW, inv_log2c, dlogits, accumulate);
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}

@@ -1608,6 +1608,102 @@ def softmax_entropy_bwd_(dlogits, logits, kind, weight, grad_scale=1.0, accumula
     return dlogits
 
 
+# ---------------------------------------------------------------- adversarial baseline (ADVENT): entropy map, 4x4 / stride-2 convolutions, L1 tail
+def _same_dense(name, t, like):
+    _chk(t, F32, 4)
+    if not t.is_contiguous() or t.shape != like.shape:
+        raise ValueError(f'{name} must be dense with shape {tuple(like.shape)}, got shape {tuple(t.shape)} strides {t.stride()}')
+    return t
+
+
+def entropy_map(logits, generic=False, out=None):
+    """pfst_entropy_map: logits [N, C, h, w] -> ent [N, C, h, w], ent_c = -p_c log2(p_c + 1e-30) / log2(C) with p = softmax_c(logits): the
+    discriminator's input (adv_loss.py:47-50), not summed over the classes"""
+    n, c, hw, _ = _entropy_args(logits, 'entropy')
+    out = torch.empty_like(logits) if out is None else _same_dense('entropy_map: out', out, logits)
+    call('pfst_entropy_map', logits.data_ptr(), n, c, hw, int(bool(generic)), out.data_ptr(), _stream())
+    return out
+
+
+def entropy_map_bwd_(dlogits, logits, grad_ent, accumulate=True, generic=False):
+    """dlogits (+)= the gradient of entropy_map(logits) contracted with grad_ent, through the entropy term and the softmax; the probabilities
+    are formed again from the logits.  accumulate=False writes every element"""
+    n, c, hw, _ = _entropy_args(logits, 'entropy')
+    _same_dense('entropy_map_bwd_: grad_ent', grad_ent, logits)
+    _same_dense('entropy_map_bwd_: dlogits', dlogits, logits)
+    call('pfst_entropy_map_bwd', logits.data_ptr(), grad_ent.data_ptr(), n, c, hw, int(bool(generic)), dlogits.data_ptr(), int(bool(accumulate)),
+         _stream())
+    return dlogits
+
+
+def _adv_conv_shapes(name, x, w):
+    _dense(x)
+    _dense(w)
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (x.shape[1], 4, 4) or x.shape[2] < 2 or x.shape[3] < 2:
+        raise ValueError(f'{name}: x [N, Cin, H >= 2, W >= 2] and w [Cout, Cin, 4, 4], got {tuple(x.shape)} and {tuple(w.shape)}')
+    n, cin, h, wd = x.shape
+    return n, cin, h, wd, w.shape[0]
+
+
+def adv_conv(x, w, bias=None, slope=None, out=None):
+    """pfst_adv_conv_fwd: Conv2d(kernel 4, stride 2, padding 1) of x [N, Cin, H, W] with w [Cout, Cin, 4, 4] (+ bias), then LeakyReLU(slope)
+    in the epilogue unless slope is None -> y [N, Cout, H // 2, W // 2]"""
+    n, cin, h, wd, cout = _adv_conv_shapes('adv_conv', x, w)
+    if bias is not None and (_dense(bias).dim() != 1 or bias.numel() != cout):
+        raise ValueError(f'adv_conv: bias {tuple(bias.shape)} for {cout} output channels')
+    shape = (n, cout, h // 2, wd // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device)
+    elif tuple(_dense(out).shape) != shape:
+        raise ValueError(f'adv_conv: out {tuple(out.shape)}, expected {shape}')
+    call('pfst_adv_conv_fwd', x.data_ptr(), w.data_ptr(), _p(bias), out.data_ptr(), n, cin, h, wd, cout, int(slope is not None),
+         float(slope or 0.0), _stream())
+    return out
+
+
+def adv_conv_dgrad_(dx, dy, w, x_gate=None, slope=0.0, accumulate=False):
+    """pfst_adv_conv_dgrad: dx [N, Cin, H, W] (+)= the data gradient of adv_conv for dy [N, Cout, H // 2, W // 2]; x_gate (the layer's input x
+    where x is a LeakyReLU output): multiplied by x > 0 ? 1 : slope, i.e. dx is the gradient of the pre-activation below"""
+    n, cin, h, wd, cout = _adv_conv_shapes('adv_conv_dgrad_', dx, w)
+    if tuple(_dense(dy).shape) != (n, cout, h // 2, wd // 2):
+        raise ValueError(f'adv_conv_dgrad_: dy {tuple(dy.shape)}, expected {(n, cout, h // 2, wd // 2)}')
+    if x_gate is not None:
+        _same_dense('adv_conv_dgrad_: x_gate', x_gate, dx)
+    call('pfst_adv_conv_dgrad', dy.data_ptr(), w.data_ptr(), _p(x_gate), dx.data_ptr(), n, cin, h, wd, cout, float(slope), int(bool(accumulate)),
+         _stream())
+    return dx
+
+
+ADV_WGRAD_LAUNCHES = 0          # counts adv_conv_wgrad_ calls (the frozen-discriminator pass of the adversarial step must launch none)
+
+
+def adv_conv_wgrad_(dw, db, x, dy):
+    """pfst_adv_conv_wgrad: dw [Cout, Cin, 4, 4] += and db [Cout] += (db may be None) the weight / bias gradients of adv_conv(x, w) for dy"""
+    global ADV_WGRAD_LAUNCHES
+    n, cin, h, wd, cout = _adv_conv_shapes('adv_conv_wgrad_', x, dw)
+    if tuple(_dense(dy).shape) != (n, cout, h // 2, wd // 2):
+        raise ValueError(f'adv_conv_wgrad_: dy {tuple(dy.shape)}, expected {(n, cout, h // 2, wd // 2)}')
+    if db is not None and (_dense(db).dim() != 1 or db.numel() != cout):
+        raise ValueError(f'adv_conv_wgrad_: db {tuple(db.shape)} for {cout} output channels')
+    ADV_WGRAD_LAUNCHES += 1
+    call('pfst_adv_conv_wgrad', x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _p(db), n, cin, h, wd, cout, _stream())
+    return dw
+
+
+def adv_tail(y, label, weight, grad_scale=1.0, want_grad=True):
+    """pfst_adv_tail: y [N, 1, h, w], the discriminator's last plane -> (d [N] = the plane means, loss [1] = weight * mean_n |d_n - label|,
+    gy like y = grad_scale * dloss/dy, or None)"""
+    _dense(y)
+    if y.dim() != 4 or y.shape[1] != 1:
+        raise ValueError(f'adv_tail: y must be [N, 1, h, w], got {tuple(y.shape)}')
+    n, hw = y.shape[0], y.shape[2] * y.shape[3]
+    d = torch.empty(n, device=y.device)
+    loss = torch.empty(1, device=y.device)
+    gy = torch.empty_like(y) if want_grad else None
+    call('pfst_adv_tail', y.data_ptr(), n, hw, float(label), float(weight), float(grad_scale), d.data_ptr(), loss.data_ptr(), _p(gy), _stream())
+    return d, loss, gy
+
+
 def pseudo_label(logits, size, threshold, want_i64=True, want_conf=False, want_prob=False):
     """-> (label int64 [N,H,W] | None, label uint8 [N,H,W], count uint64-as-int64 [1][, conf float [N,H,W]][, max prob float [N,H,W]])"""
     _dense(logits)

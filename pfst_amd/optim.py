@@ -152,6 +152,44 @@ def build_optimizer(model, cfg):
     return AdamW(params, **cfg)
 
 
+class OptimizerDict(dict):
+    """{name: optimizer} as mmcv's build_optimizers returns for a GAN-style model, plus what the runner drives a single optimizer through:
+    `param_groups` (the groups of every optimizer, in key order -- the same dict objects, so a learning rate written there lands in its
+    optimizer), `zero_grad`, and `state_dict` / `load_state_dict` as {name: state}"""
+
+    @property
+    def param_groups(self):
+        return [g for opt in self.values() for g in opt.param_groups]
+
+    def zero_grad(self, set_to_none=False):
+        for opt in self.values():
+            opt.zero_grad(set_to_none)
+
+    def state_dict(self):
+        return {k: opt.state_dict() for k, opt in self.items()}
+
+    def load_state_dict(self, sd):
+        if set(sd) != set(self):
+            raise KeyError(f'optimizer state for {sorted(sd)}, this run has {sorted(self)}')
+        for k, opt in self.items():
+            opt.load_state_dict(sd[k])
+
+
+def build_optimizers(model, cfg):
+    """mmcv.runner.build_optimizers: a cfg whose values are all dicts and which has no `type` key of its own -- e.g.
+    dict(generator=dict(type='AdamW', ...), discriminator=dict(type='AdamW', ...)) -- builds one optimizer per key over getattr(model, key)
+    and returns them as an OptimizerDict; any other cfg is build_optimizer's"""
+    if 'type' not in cfg and len(cfg) > 0 and all(isinstance(v, dict) for v in cfg.values()):
+        out = OptimizerDict()
+        for key, sub in cfg.items():
+            part = getattr(model, key, None)
+            if part is None:
+                raise AttributeError(f'optimizer[{key!r}]: {type(model).__name__} has no sub-module `{key}`')
+            out[key] = build_optimizer(part, sub)
+        return out
+    return build_optimizer(model, cfg)
+
+
 def poly_lr(base_lr, it, max_iters, power=1.0, min_lr=0.0, warmup_iters=1500, warmup_ratio=1e-6):
     """mmcv PolyLrUpdaterHook + linear warm-up (adamw_40k.py:8-16), by iteration."""
     coeff = (1 - it / max_iters) ** power

@@ -70,6 +70,29 @@ def dacs_uda_cfg(num_classes=6, in_channels=3, dropout=0.1, blur=True, color_jit
         model=model_cfg(num_classes, in_channels, dropout), max_iters=max_iters)
 
 
+# Adversarial baseline (ADVENT).  The reference ships the model (DomainAdaptorAdv, FCDiscriminator, AdvLoss) but NO config for it: these
+# defaults are the ADVENT paper's (Vu et al., CVPR 2019: lambda_adv = 0.001 on the generator's adversarial term, the discriminator's two
+# terms halved, Adam with lr 1e-4 and betas (0.9, 0.99) for the discriminator), not numbers of the reference.  The project builds AdamW and
+# SGD only: the discriminator takes AdamW with weight_decay = 0, which is torch.optim.Adam's update without weight decay.
+ADVENT_WEIGHTS = dict(loss_gen=0.001, loss_disc_src=0.5, loss_disc_trg=0.5)
+ADVENT_DISC_OPTIMIZER = dict(type='AdamW', lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0)
+
+
+def advent_cfg(model, generator_optimizer=None, ndf=64, weights=None):
+    """-> dict(model=..., optimizer=...) of the adversarial baseline around a segmentor cfg `model` (e.g. model_cfg()): the segmentor turned
+    into a DomainAdaptorAdv with an FCDiscriminator on the per-class entropy maps and the two AdvLoss lists; optimizer = one entry per
+    sub-network (optim.build_optimizers): the generator keeps `generator_optimizer` (default: the PFST recipe's AdamW)"""
+    w = dict(ADVENT_WEIGHTS, **(weights or {}))
+    m = copy.deepcopy(dict(model))
+    m['type'] = 'DomainAdaptorAdv'
+    m['discriminator'] = dict(type='FCDiscriminator', num_in_channels=m['decode_head']['num_classes'], ndf=ndf)
+    m['disc_losses'] = [dict(type='AdvLoss', loss_type='advent', net_type='disc',
+                             weights=dict(loss_disc_src=w['loss_disc_src'], loss_disc_trg=w['loss_disc_trg']))]
+    m['gen_losses'] = [dict(type='AdvLoss', loss_type='advent', net_type='gen', weights=dict(loss_gen=w['loss_gen']))]
+    return dict(model=m, optimizer=dict(generator=copy.deepcopy(dict(generator_optimizer or OPTIMIZER)),
+                                        discriminator=dict(ADVENT_DISC_OPTIMIZER)))
+
+
 OPTIMIZER = dict(type='AdamW', lr=6e-5, betas=(0.9, 0.999), weight_decay=0.01)
 LR_CONFIG = dict(policy='poly', warmup='linear', warmup_iters=1500, warmup_ratio=1e-6, power=1.0, min_lr=0.0, by_epoch=False)
 

@@ -42,14 +42,14 @@ _REGISTERED = False
 
 def _register_builtin_types():
     """import the modules whose decorators register the reference's type names (PFGST, PFGSTLoss, EncoderDecoder, ResNetV1c, the
-    heads, CrossEntropyLoss), on the first lookup: `import pfst_amd` stays cheap for processes that never build a model -- the data
+    heads, CrossEntropyLoss, DomainAdaptorAdv, FCDiscriminator, AdvLoss), on the first lookup: `import pfst_amd` stays cheap for processes that never build a model -- the data
     loader's worker processes un-pickle pfst_amd.data / pfst_amd.pipeline objects and need neither the kernels' front end nor the
     model code"""
     global _REGISTERED
     if not _REGISTERED:
         _REGISTERED = True              # set first: the modules' own decorators re-enter the registry while they import
         try:
-            from . import models, uda  # noqa: F401
+            from . import adversarial, models, uda  # noqa: F401
         except BaseException:
             _REGISTERED = False         # a failed import (libpfst_hip.so missing, ...) must surface on EVERY lookup, not only the first
             raise
@@ -70,6 +70,11 @@ def build_head(cfg):
 
 def build_loss(cfg):
     return LOSSES.build(cfg)
+
+
+def build_discriminator(cfg):
+    """rsiseg/models/builder.py: the discriminator of an adversarial segmentor (DomainAdaptorAdv)"""
+    return DISCRIMINATORS.build(cfg)
 
 
 def build_pixel_sampler(cfg, **default_args):

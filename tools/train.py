@@ -18,7 +18,12 @@ DeepLabV3, FCN: presets.baseline_model_cfg) on the same backbone, `--synthetic` 
 
 Self-training baselines: `--uda dacs` swaps the `uda` section for DACS (rsiseg/models/uda/dacs.py), `--synthetic` included; MinEnt and
 max-squares are PFGST with an EntropyLoss among its auxiliary losses, e.g.
-`--cfg-options "uda.aux_losses=[{'type':'EntropyLoss','loss_type':'entropy','weights':{'loss_ent':W}}]"` (W: yours to choose, README)."""
+`--cfg-options "uda.aux_losses=[{'type':'EntropyLoss','loss_type':'entropy','weights':{'loss_ent':W}}]"` (W: yours to choose, README).
+
+Adversarial baseline: `--adversarial advent` drops the `uda` section and turns cfg.model into a DomainAdaptorAdv with an FCDiscriminator on
+the entropy maps (presets.advent_cfg; optimizer = one entry per sub-network), `--synthetic` included.  The reference ships no config for
+this model: the loss weights and the discriminator's optimizer are the ADVENT paper's (README).  It is a flag of its own because `--uda`
+names a self-training wrapper kept in the `uda` section, which this model does not have (`--uda advent` stays an unknown choice)."""
 import argparse
 import os
 import sys
@@ -40,6 +45,9 @@ def parse_args(argv=None):
     p.add_argument('--uda', choices=['dacs'],
                    help='replace the `uda` section of the config or preset by the DACS self-training baseline (presets.dacs_uda_cfg: the values of '
                         "the reference's configs/_base_/uda/dacs.py, no auxiliary losses), keeping strong_aug_denorm_type, a property of the data")
+    p.add_argument('--adversarial', choices=['advent'],
+                   help='drop the `uda` section of the config or preset and train cfg.model adversarially (presets.advent_cfg: DomainAdaptorAdv + '
+                        'FCDiscriminator on the entropy maps, one optimizer each); --uda names a self-training wrapper and keeps refusing this name')
     p.add_argument('--resume-from')
     p.add_argument('--no-validate', action='store_true')
     g = p.add_mutually_exclusive_group()
@@ -106,6 +114,8 @@ def load_cfg(args):
         if args.supervised or 'uda' not in cfg:
             raise ValueError('--uda swaps the self-training wrapper of a config with a `uda` section: it cannot be combined with --supervised '
                              'or a supervised config')
+        if args.adversarial:
+            raise ValueError('--uda and --adversarial each replace the `uda` section: pass one of them')
         from pfst_amd.presets import dacs_uda_cfg
         old = cfg.uda
         new = dacs_uda_cfg()
@@ -115,6 +125,30 @@ def load_cfg(args):
         cfg.uda = new
         if args.cfg_options:                                  # options addressed at the new section's keys apply to it
             cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
+    if args.adversarial:
+        if args.supervised or 'uda' not in cfg:
+            raise ValueError('--adversarial replaces the self-training wrapper of a config with a `uda` section: it cannot be combined with '
+                             '--supervised or a supervised config')
+        # no teacher, no mixing: the `uda` wrapper goes, the segmentor itself becomes the adversarial model and brings two optimizers
+        from pfst_amd.presets import advent_cfg
+        if cfg.model.get('type', 'EncoderDecoder') != 'EncoderDecoder':
+            raise ValueError(f"--adversarial advent wraps an EncoderDecoder model cfg, got type {cfg.model.get('type')!r}")
+        # the config's single optimizer becomes the generator's.  Options addressed at the sections that exist only after this rewrite
+        # (optimizer.generator.*, optimizer.discriminator.*) were merged into it above as stray sub-dicts: they are taken out here and land
+        # where they belong in the merge below
+        gen_opt = {k: v for k, v in dict(cfg.get('optimizer') or {}).items()
+                   if not (k in ('generator', 'discriminator') and isinstance(v, dict))}
+        if 'type' not in gen_opt:
+            raise ValueError('--adversarial advent takes the generator\'s optimizer from the config\'s `optimizer` section, which must be one '
+                             f'optimizer with a `type`; got keys {sorted(gen_opt)}')
+        new = advent_cfg(cfg.model.to_dict() if hasattr(cfg.model, 'to_dict') else dict(cfg.model), generator_optimizer=gen_opt)
+        cfg.pop('uda')
+        cfg.model, cfg.optimizer = new['model'], new['optimizer']
+        if args.cfg_options:                                  # options addressed at the new sections' keys apply to them
+            # (an option of the single optimizer, e.g. optimizer.weight_decay, went into the generator's section above: not merged again)
+            sub = ('optimizer.generator', 'optimizer.discriminator')
+            cfg.merge_from_dict({k: v for k, v in parse_cfg_options(args.cfg_options).items()
+                                 if not (k + '.').startswith('optimizer.') or k in sub or k.startswith(tuple(s + '.' for s in sub))})
     if args.max_iters:
         cfg.runner['max_iters'] = args.max_iters
     if args.supervised:
@@ -136,7 +170,7 @@ def main(argv=None):
     from pfst_amd import dist as pdist
     from pfst_amd.data import build_dataset, build_loader, synthetic_loader
     from pfst_amd.evaluation import build_eval_fn
-    from pfst_amd.optim import build_optimizer
+    from pfst_amd.optim import build_optimizers
     from pfst_amd.registry import build_train_model
     from pfst_amd.runner import IterBasedRunner, find_latest_checkpoint, init_random_seed, init_student_from, set_random_seed
 
@@ -155,7 +189,8 @@ def main(argv=None):
     seed = seed + rank if args.diff_seed else seed
     set_random_seed(seed, args.deterministic)
 
-    supervised = 'uda' not in cfg
+    adversarial = cfg.model.get('type') == 'DomainAdaptorAdv'          # no `uda` wrapper either, but it reads the source / target batch
+    supervised = 'uda' not in cfg and not adversarial
     if args.init_student_from and supervised:
         raise SystemExit('--init-student-from fills the student and the teacher of a `uda` wrapper; a supervised run takes --load-from')
     load_from = args.load_from or cfg.get('load_from')
@@ -172,7 +207,7 @@ def main(argv=None):
     model = build_train_model(cfg)
     model.init_weights()
     model.to(dev)
-    optimizer = build_optimizer(model, cfg.optimizer)
+    optimizer = build_optimizers(model, cfg.optimizer)
     nc = cfg.model.decode_head.num_classes
     eval_fn = None
     data_cfg = cfg.get('data') or {}
