@@ -14,7 +14,9 @@ __global__ void ema_kernel(float* __restrict__ t, const float* __restrict__ s, i
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 a = reinterpret_cast<float4*>(t)[i];
     const float4 b = reinterpret_cast<const float4*>(s)[i];
-    // reference arithmetic: alpha*ema + (1-alpha)*param, two roundings of the products then the sum
+    // the reference's expression alpha*ema + (1-alpha)*param; as compiled (contraction is on) each element is ONE rounded product one_m*b and
+    // ONE fused multiply-add alpha*a + that (v_mul_f32, v_fmac_f32), and one_m = 1 - alpha is formed in fp32 from the rounded alpha (at 0.999
+    // it is 1.3e-5 relative away from the rounded double 1 - alpha).  Bound and measurement: tests/test_optimizer_edges_gpu.py, part C
     a.x = alpha * a.x + one_m * b.x; a.y = alpha * a.y + one_m * b.y;
     a.z = alpha * a.z + one_m * b.z; a.w = alpha * a.w + one_m * b.w;
     reinterpret_cast<float4*>(t)[i] = a;

@@ -58,14 +58,17 @@ class AdamW(torch.optim.Optimizer):
 
     def state_dict(self):
         sd = super().state_dict()
+        # attached arenas in first-step order, then what load_state_dict() left waiting for arenas that have not stepped yet (step() takes
+        # those from the front): a checkpoint written between a resume and the first step keeps the moments and the step count
         sd['pfst_flat'] = [dict(m=st['m'].cpu(), v=st['v'].cpu(), step=st['step']) for st in self._flat.values()]
+        sd['pfst_flat'] += [dict(st) for st in getattr(self, '_pending_flat', None) or []]
         return sd
 
     def load_state_dict(self, sd):
         sd = dict(sd)
         flat = sd.pop('pfst_flat', [])
         super().load_state_dict(sd)
-        self._pending_flat = flat       # attached to the arenas on the first step() after the model is on the GPU
+        self._pending_flat = list(flat)       # attached to the arenas on the first step() after the model is on the GPU
 
 
 class SGD(torch.optim.Optimizer):
@@ -126,14 +129,16 @@ class SGD(torch.optim.Optimizer):
 
     def state_dict(self):
         sd = super().state_dict()
+        # as AdamW.state_dict: the attached arenas, then the loaded entries no step() has attached yet
         sd['pfst_flat'] = [dict(buf=None if st['buf'] is None else st['buf'].cpu(), stepped=st['stepped']) for st in self._flat.values()]
+        sd['pfst_flat'] += [dict(st) for st in getattr(self, '_pending_flat', None) or []]
         return sd
 
     def load_state_dict(self, sd):
         sd = dict(sd)
         flat = sd.pop('pfst_flat', [])
         super().load_state_dict(sd)
-        self._pending_flat = flat       # attached to the arenas on the first step() after the model is on the GPU
+        self._pending_flat = list(flat)       # attached to the arenas on the first step() after the model is on the GPU
 
 
 def build_optimizer(model, cfg):

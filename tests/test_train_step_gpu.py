@@ -68,7 +68,7 @@ def test_two_train_steps_match_reference_golden_and_oracle(conv_math):
         if it > 0:
             # Start every compared step from IDENTICAL state: AdamW's first steps move each weight by ~lr*sign(g), so
             # the 2-3 % fp32 gradient noise (see below) turns into O(10 %) logit differences after one update of this
-            # random-init network.  The optimiser arithmetic itself is pinned in test_hip_ops.py::test_ema_adamw_flat.
+            # random-init network.  The optimiser arithmetic itself is pinned in test_optimizer_edges_gpu.py (fp64 trajectories).
             from collections import OrderedDict
             sync = OrderedDict(('model.' + k, v.detach()) for k, v in oracle.student.items())
             sync.update(('ema_model.' + k, v.detach()) for k, v in oracle.teacher.items())
