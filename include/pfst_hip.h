@@ -356,6 +356,28 @@ int pfst_pyramid_expand(const float* const* grids, int N, int C, int H, int W, i
  * y_amax as above */
 int pfst_copy_planes(const float* x, long long x_bs, float* y, long long y_bs, int N, long long CHW, int accumulate, float* y_amax,
                      pfst_stream_t stream);
+/* ---- the top-down path of a feature pyramid (csrc/fpn.hip): UPerHead's merges and multi-level concat (uper_head.py:108-132).  Bilinear,
+ * align_corners=False, any Hc x Wc -> Hf x Wf with Hf >= Hc, Wf >= Wc; dense planes with batch strides; no atomics, fixed summation order.
+ * Every value is bit-identical to what pfst_resize_bilinear / pfst_resize_bilinear_bwd give for the same planes. */
+#define PFST_FPN_MAX_LEVELS 3
+/* out[n][c] = lat[n][c] + resize(coarse[n][c] -> Hf x Wf): the resize's value and ONE rounded fp32 add.  out is a buffer of its own (not lat, not
+ * coarse).  y_amax: NULL, or the slot group that receives max |out|.  Adjoint: d_lat = d_out, d_coarse (+)= pfst_resize_bilinear_bwd(d_out). */
+int pfst_topdown_merge(const float* lat, long long lat_bs, const float* coarse, long long coarse_bs, float* out, long long out_bs, int N, int C,
+                       int Hc, int Wc, int Hf, int Wf, float* y_amax, pfst_stream_t stream);
+/* y[n][chan_off[k] + c] = resize(srcs[k][n][c] -> Hf x Wf) for K <= PFST_FPN_MAX_LEVELS levels in one launch.  srcs: HOST array of K device
+ * pointers; src_bs / src_h / src_w / chan_off: HOST arrays of K (batch stride, grid, first channel of the level's slice of y; the slices must
+ * not overlap).  y_amax: NULL, or the slot group that receives max |y| over everything written. */
+int pfst_fpn_resize_concat(const float* const* srcs, const long long* src_bs, const int* src_h, const int* src_w, const int* chan_off, int K,
+                           float* y, long long y_bs, int N, int C, int Hf, int Wf, float* y_amax, pfst_stream_t stream);
+/* its adjoint as a gather: d_srcs[k][n][c] = (accumulate[k] ? d_srcs[k] : 0) + resize^T(dy[n][chan_off[k] + c]) for every level in one launch */
+int pfst_fpn_resize_concat_bwd(const float* dy, long long dy_bs, float* const* d_srcs, const long long* src_bs, const int* src_h, const int* src_w,
+                               const int* chan_off, const int* accumulate, int K, int N, int C, int Hf, int Wf, pfst_stream_t stream);
+/* the form a launch of the three takes for these operands (alignment, sizes), as the launchers decide it.  merge: 0 one pixel per thread, 1 four
+ * pixels and 16-byte accesses, 2 the exact-1/2 walk; concat: 0 / 1 likewise; concat_bwd, per level: 0 the generic gather, 1 x2 on 2 x 2 blocks */
+int pfst_topdown_merge_route(const float* lat, long long lat_bs, const float* coarse, long long coarse_bs, const float* out, long long out_bs,
+                             int Hc, int Wc, int Hf, int Wf);
+int pfst_fpn_resize_concat_route(const float* y, long long y_bs, int Hf, int Wf);
+int pfst_fpn_resize_concat_bwd_route(const float* dy_plane, long long dy_bs, const float* d_src, long long src_bs, int Hc, int Wc, int Hf, int Wf);
 /* F.interpolate(mode='nearest') by an integer factor on [NC][h][w] maps and its adjoint (pfgst_loss.py:57-58) */
 int pfst_upsample_nearest(const float* x, float* y, int NC, int h, int w, int factor, pfst_stream_t stream);
 int pfst_upsample_nearest_bwd(const float* dy, float* dx, int NC, int h, int w, int factor, pfst_stream_t stream);

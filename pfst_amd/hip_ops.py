@@ -1028,6 +1028,92 @@ def copy_planes(x, out, accumulate=False, amax=None):
     return out
 
 
+# ---------------------------------------------------------------- feature-pyramid top-down path (csrc/fpn.hip)
+FPN_MAX_LEVELS = 3          # PFST_FPN_MAX_LEVELS
+MERGE_ROUTES = ('pixel', 'quad', 'half')          # pfst_topdown_merge_route: one pixel per thread, four with 16-byte accesses, the exact-1/2 walk
+
+
+def _i64s(vals):
+    return (ctypes.c_longlong * len(vals))(*[int(v) for v in vals])
+
+
+def _merge_shapes(lat, coarse):
+    n, c, hf, wf = lat.shape
+    if coarse.dim() != 4 or tuple(coarse.shape[:2]) != (n, c) or coarse.shape[2] > hf or coarse.shape[3] > wf:
+        raise ValueError(f'topdown_merge: coarse {tuple(coarse.shape)} under lateral {tuple(lat.shape)} (same N, C; a grid no finer)')
+    return n, c, coarse.shape[2], coarse.shape[3], hf, wf
+
+
+def topdown_merge(lat, coarse, out=None, amax=None):
+    """out = lat + F.interpolate(coarse, lat.shape[2:], mode='bilinear', align_corners=False) in one pass: the value of resize_bilinear and one
+    fp32 add, bit for bit.  lat, coarse, out: dense-plane NCHW views; out (default: a new tensor) must not be lat -- the lateral layer's backward
+    still reads it.  amax: the slot group that receives max |out|.  Adjoint: d_lat = d_out, d_coarse (+)= resize_bilinear_bwd(d_out)."""
+    n, c, hc, wc, hf, wf = _merge_shapes(lat, coarse)
+    if out is None:
+        out = torch.empty(n, c, hf, wf, device=lat.device)
+    if tuple(out.shape) != tuple(lat.shape):
+        raise ValueError(f'topdown_merge: out {tuple(out.shape)} for lateral {tuple(lat.shape)}')
+    call('pfst_topdown_merge', lat.data_ptr(), _bs(lat), coarse.data_ptr(), _bs(coarse), out.data_ptr(), _bs(out), n, c, hc, wc, hf, wf, _p(amax),
+         _stream())
+    return out
+
+
+def topdown_merge_route(lat, coarse, out):
+    """the form pfst_topdown_merge takes for these operands, one of MERGE_ROUTES (no launch)"""
+    _, _, hc, wc, hf, wf = _merge_shapes(lat, coarse)
+    return MERGE_ROUTES[lib().pfst_topdown_merge_route(lat.data_ptr(), _bs(lat), coarse.data_ptr(), _bs(coarse), out.data_ptr(), _bs(out), hc, wc, hf, wf)]
+
+
+def _fpn_levels(name, wide, levels, chan_off):
+    """checks of the K level tensors against the wide buffer -> (N, C, Hf, Wf, chan_off)"""
+    n, cw, hf, wf = wide.shape
+    k = len(levels)
+    if not 1 <= k <= FPN_MAX_LEVELS:
+        raise NotImplementedError(f'{name}: 1 to {FPN_MAX_LEVELS} levels per launch, got {k}')
+    c = levels[0].shape[1]
+    chan_off = [i * c for i in range(k)] if chan_off is None else [int(o) for o in chan_off]
+    if len(chan_off) != k or any(o < 0 or o + c > cw for o in chan_off):
+        raise ValueError(f'{name}: channel offsets {chan_off} of {c}-channel slices in {cw} channels')
+    for t in levels:
+        if t.dim() != 4 or tuple(t.shape[:2]) != (n, c) or t.shape[2] > hf or t.shape[3] > wf:
+            raise ValueError(f'{name}: level {tuple(t.shape)} for a buffer {tuple(wide.shape)} (N = {n}, C = {c}; grids no finer than the buffer)')
+    return n, c, hf, wf, chan_off
+
+
+def fpn_resize_concat(srcs, out, chan_off=None, amax=None):
+    """out[:, chan_off[k]:chan_off[k] + C] = F.interpolate(srcs[k], out.shape[2:], mode='bilinear', align_corners=False) for up to three maps in
+    ONE launch, each bit-identical to resize_bilinear(srcs[k], out=that slice).  out: a dense-plane NCHW view (the concat buffer, or its tail);
+    chan_off: default k C.  amax: the slot group that receives max |.| over everything written."""
+    n, c, hf, wf, chan_off = _fpn_levels('fpn_resize_concat', out, srcs, chan_off)
+    call('pfst_fpn_resize_concat', _ptr_array(srcs), _i64s([_bs(s) for s in srcs]), _pyr_ints([s.shape[2] for s in srcs]),
+         _pyr_ints([s.shape[3] for s in srcs]), _pyr_ints(chan_off), len(srcs), out.data_ptr(), _bs(out), n, c, hf, wf, _p(amax), _stream())
+    return out
+
+
+def fpn_resize_concat_route(out):
+    """1: the concat launch moves `out` in 16-byte accesses, 0: pixel by pixel"""
+    return lib().pfst_fpn_resize_concat_route(out.data_ptr(), _bs(out), out.shape[2], out.shape[3])
+
+
+def fpn_resize_concat_bwd(dy, outs, chan_off=None, accumulate=False):
+    """the adjoint of fpn_resize_concat in one launch: outs[k] = (accumulate[k] ? outs[k] : 0) + resize_bilinear_bwd(dy[:, chan_off[k]:chan_off[k] + C]),
+    each bit-identical to resize_bilinear_bwd on that slice.  accumulate: one flag, or one per level"""
+    n, c, hf, wf, chan_off = _fpn_levels('fpn_resize_concat_bwd', dy, outs, chan_off)
+    acc = [bool(accumulate)] * len(outs) if isinstance(accumulate, (bool, int)) else [bool(a) for a in accumulate]
+    if len(acc) != len(outs):
+        raise ValueError(f'fpn_resize_concat_bwd: {len(acc)} accumulate flags for {len(outs)} levels')
+    call('pfst_fpn_resize_concat_bwd', dy.data_ptr(), _bs(dy), _ptr_array(outs), _i64s([_bs(o) for o in outs]), _pyr_ints([o.shape[2] for o in outs]),
+         _pyr_ints([o.shape[3] for o in outs]), _pyr_ints(chan_off), _pyr_ints(acc), len(outs), n, c, hf, wf, _stream())
+    return outs
+
+
+def fpn_resize_concat_bwd_routes(dy, outs, chan_off=None):
+    """per level: 1 the x2 gather on 2 x 2 blocks, 0 the generic gather"""
+    _, c, hf, wf, chan_off = _fpn_levels('fpn_resize_concat_bwd', dy, outs, chan_off)
+    return [lib().pfst_fpn_resize_concat_bwd_route(dy[:, o:o + c].data_ptr(), _bs(dy), t.data_ptr(), _bs(t), t.shape[2], t.shape[3], hf, wf)
+            for o, t in zip(chan_off, outs)]
+
+
 def upsample_nearest(x, factor):
     _dense(x)
     n, c, h, w = x.shape

@@ -766,6 +766,32 @@ class ASPPHead(BaseDecodeHead):
         return (logits, feats) if return_features else logits
 
 
+def _ppm_forward(x, ci, ch, scales, psp_modules, bottleneck, tape):
+    """the pyramid pooling module and its 3x3 bottleneck over x [N, ci, H, W] (psp_head.py:9-50, :86-93; uper_head.py:77-85) -> the bottleneck's
+    output Var.  Shared by PSPHead and UPerHead: [x, resize(ConvModule(AdaptiveAvgPool2d(s)(x))) for s in scales] in one concat buffer"""
+    cat = _concat_var(x, ci + len(scales) * ch, tape)
+    x.claim_first_use()              # dL/dx is completed by the pyramid's adjoint below, which fuses nothing
+    ops.copy_planes(x.data, cat.data[:, 0:ci], amax=cat.amax)
+    pooled = [Var(p, tape is not None) for p in ops.pyramid_pool(x.data, scales)]
+    if tape is not None:
+        # recorded before the small layers, so it runs after them: dL/dx = the identity slice's gradient + the adjoint of every pooling,
+        # written once
+        def bwd_pool():
+            buf, acc = x.grad_target()
+            ops.pyramid_pool_bwd([p.grad for p in pooled], scales, buf, accumulate=acc, add=cat.grad[:, 0:ci])
+            for p in pooled:
+                p.free_grad()
+        tape.record(bwd_pool)
+    outs = [psp_modules[k][1](pooled[k], tape) for k in range(len(scales))]
+    ops.pyramid_upsample([o.data for o in outs], scales, cat.data[:, ci:], amax=cat.amax)
+    if tape is not None:
+        def bwd_up():
+            for o, g in zip(outs, ops.pyramid_upsample_bwd(cat.grad[:, ci:], scales)):
+                o._grad = g
+        tape.record(bwd_up)
+    return bottleneck(cat, tape)
+
+
 @HEADS.register_module()
 class PSPHead(BaseDecodeHead):
     """psp_head.py (PSPNet): [x, resize(ConvModule(AdaptiveAvgPool2d(s)(x))) for s in pool_scales] -> 3x3 bottleneck -> cls_seg.  The pyramid
@@ -783,29 +809,86 @@ class PSPHead(BaseDecodeHead):
         self.bottleneck = ConvModule(ci + len(self.pool_scales) * ch, ch, 3, padding=1)
 
     def forward(self, inputs, return_features=False, tape=None, training=True):
-        x = inputs[self.in_index]
-        ci, ch, scales = self.in_channels, self.channels, self.pool_scales
-        cat = _concat_var(x, ci + len(scales) * ch, tape)
-        x.claim_first_use()              # dL/dx is completed by the pyramid's adjoint below, which fuses nothing
-        ops.copy_planes(x.data, cat.data[:, 0:ci], amax=cat.amax)
-        pooled = [Var(p, tape is not None) for p in ops.pyramid_pool(x.data, scales)]
+        feats = _ppm_forward(inputs[self.in_index], self.in_channels, self.channels, self.pool_scales, self.psp_modules, self.bottleneck, tape)
+        logits = self.cls_seg(feats, tape, training)
+        return (logits, feats) if return_features else logits
+
+
+@HEADS.register_module()
+class UPerHead(BaseDecodeHead):
+    """uper_head.py (UPerNet): 1x1 laterals on levels 0 .. L-2, the pyramid pooling module and its bottleneck on the last level (PSPHead's
+    code path, _ppm_forward), the top-down merges lateral + resize(coarser), a 3x3 fpn_conv per merged level, every level resized to level
+    0's grid and concatenated, fpn_bottleneck, cls_seg.  The module names and their construction order are the reference's (its checkpoints
+    load key for key).  `in_channels` / `in_index` are lists: the head selects its levels itself (the reference's 'multiple_select'; the
+    `input_transform` argument stays refused like for every head).  The merges and the concat are csrc/fpn.hip: one
+    pass per merge that also publishes max |.| of the merged map, one launch for the three resized slices.  fpn_convs[0] writes straight into
+    slice 0.  Returns the fpn_bottleneck output as the decoded features (pre-dropout, as ASPPHead)."""
+
+    def __init__(self, pool_scales=(1, 2, 3, 6), **kwargs):
+        super().__init__(**kwargs)
+        assert isinstance(pool_scales, (list, tuple))
+        ci, idx = self.in_channels, self.in_index
+        if not (isinstance(ci, (list, tuple)) and isinstance(idx, (list, tuple)) and len(ci) == len(idx) and len(ci) >= 2
+                and all(isinstance(c, int) and c > 0 for c in ci) and all(isinstance(i, int) for i in idx)):
+            raise TypeError(f'UPerHead: in_channels and in_index are lists of equal length >= 2 (one entry per level), got {ci!r} and {idx!r}')
+        if len(ci) - 1 > ops.FPN_MAX_LEVELS:
+            raise NotImplementedError(f'UPerHead: up to {ops.FPN_MAX_LEVELS + 1} levels (one concat launch), got {len(ci)}')
+        self.in_channels, self.in_index = list(ci), list(idx)
+        self.pool_scales = ops.check_pool_scales(pool_scales)          # NotImplementedError beyond six scales of 1 .. 8
+        ch = self.channels
+        self.psp_modules = nn.ModuleList([nn.Sequential(nn.Identity(), ConvModule(ci[-1], ch, 1)) for _ in self.pool_scales])
+        self.bottleneck = ConvModule(ci[-1] + len(self.pool_scales) * ch, ch, 3, padding=1)
+        self.lateral_convs, self.fpn_convs = nn.ModuleList(), nn.ModuleList()
+        for c in ci[:-1]:          # (the top level has neither: its lateral is the PPM's bottleneck)
+            self.lateral_convs.append(ConvModule(c, ch, 1))
+            self.fpn_convs.append(ConvModule(ch, ch, 3, padding=1))
+        self.fpn_bottleneck = ConvModule(len(ci) * ch, ch, 3, padding=1)
+
+    def forward(self, inputs, return_features=False, tape=None, training=True):
+        xs = [inputs[i] for i in self.in_index]
+        ch, nl = self.channels, len(xs)
+        dev = xs[0].data.device
+        f16 = layers_mod.CONV_MATH == 'f16x3'
+        lats = [self.lateral_convs[i](xs[i], tape) for i in range(nl - 1)]
+        top = _ppm_forward(xs[-1], self.in_channels[-1], ch, self.pool_scales, self.psp_modules, self.bottleneck, tape)
+        # top-down, from the top level: merged[i] = lats[i] + resize(merged[i + 1]) in a buffer of its own (the lateral layer's backward reads
+        # its ReLU output).  Recorded before the fpn_convs, so in backward a merge runs AFTER the fpn_conv of its output level: it finds
+        # dL/dmerged[i] complete (fpn_convs[i]'s data gradient, plus the merge below for i > 0), hands that buffer to the lateral as its
+        # gradient and adds its adjoint resize to the level above -- each merge is the last writer of its coarser operand, hence the claim
+        merged = [None] * (nl - 1) + [top]
+        for i in range(nl - 2, -1, -1):
+            lat, coarse = lats[i], merged[i + 1]
+            coarse.claim_first_use()
+            m = Var(None, tape is not None)
+            if f16:
+                m.amax = ops.amax_slots(dev)          # fpn_convs[i]'s f16x3 scale: published by the merge, no pass of its own
+            m.data = ops.topdown_merge(lat.data, coarse.data, amax=m.amax)
+            merged[i] = m
+            if tape is not None:
+                def bwd_merge(m=m, lat=lat, coarse=coarse):
+                    g = m.grad
+                    buf, acc = coarse.grad_target()
+                    ops.resize_bilinear_bwd(g, coarse.data.shape[-2:], out=buf, accumulate=acc)
+                    lat._grad = g
+                    m.free_grad()
+                tape.record(bwd_merge)
+        h, w = merged[0].data.shape[-2:]
+        cat = _concat_var(merged[0], nl * ch, tape)
+        sl = layers_mod.folds_into_concat(self.fpn_bottleneck.conv, h, w, tape is not None)
+        if sl:
+            cat.coef_table = torch.empty(nl * ch, 4, device=dev)
+            cat.coef_table[ch:] = layers_mod.identity_coef_row(dev)          # the resized slices hold final, non-negative values
+        self.fpn_convs[0](merged[0], tape, out=cat.slice(0, ch), defer=sl)
+        outs = [self.fpn_convs[i](merged[i], tape) for i in range(1, nl - 1)] + [top]
+        ops.fpn_resize_concat([o.data for o in outs], cat.data[:, ch:], amax=cat.amax)
         if tape is not None:
-            # recorded before the small layers, so it runs after them: dL/dx = the identity slice's gradient + the adjoint of every pooling,
-            # written once
-            def bwd_pool():
-                buf, acc = x.grad_target()
-                ops.pyramid_pool_bwd([p.grad for p in pooled], scales, buf, accumulate=acc, add=cat.grad[:, 0:ci])
-                for p in pooled:
-                    p.free_grad()
-            tape.record(bwd_pool)
-        outs = [self.psp_modules[k][1](pooled[k], tape) for k in range(len(scales))]
-        ops.pyramid_upsample([o.data for o in outs], scales, cat.data[:, ci:], amax=cat.amax)
-        if tape is not None:
-            def bwd_up():
-                for o, g in zip(outs, ops.pyramid_upsample_bwd(cat.grad[:, ci:], scales)):
-                    o._grad = g
-            tape.record(bwd_up)
-        feats = self.bottleneck(cat, tape)
+            def bwd_concat():
+                targets = [o.grad_target() for o in outs]
+                ops.fpn_resize_concat_bwd(cat.grad[:, ch:], [t[0] for t in targets], accumulate=[t[1] for t in targets])
+            tape.record(bwd_concat)
+        if sl:
+            cat.lazy = (cat.data, cat.coef_table, None)
+        feats = self.fpn_bottleneck(cat, tape)
         logits = self.cls_seg(feats, tape, training)
         return (logits, feats) if return_features else logits
 

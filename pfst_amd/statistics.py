@@ -110,6 +110,8 @@ def feature_dilation(cfg, feature, dilation, downscale):
     ds = 1 if downscale is None else int(round(1.0 / downscale))
     loss_stride = _feature_stride(backbone, 0) * ds                        # the decode head's logits live on the c1 (level 0) grid
     level = model['decode_head'].get('in_index', -1) if feature == 'decoded' else int(feature)
+    if isinstance(level, (list, tuple)):                                   # a multi-level head (UPerHead) decodes on the grid of its first level
+        level = int(level[0])
     level = level % len(tuple(backbone.get('out_indices', (0, 1, 2, 3))))
     fs = _feature_stride(backbone, level)
     if fs % loss_stride != 0:

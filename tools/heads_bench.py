@@ -5,10 +5,16 @@ device ops in the same process (four adaptive_avg_pool2d; four interpolate + cat
 timed region), (b) the resize halves through the library's generic pfst_resize_bilinear / _bwd, one launch per scale, and (c) the bytes each
 launch must move at the measured copy rate.  Variants alternate inside every round; per variant the median, minimum and maximum over the
 rounds of the mean of --inner back-to-back runs between two device events.  Then a supervised step (EncoderDecoder.train_step under SGD) of
-the three comparison models and the flagship at 8 x 1024^2, alternating blocks, host clock between device synchronisations.  One JSON line
-(and --out FILE).
+the comparison models (--models, default all: pspnet, deeplabv3, fcn, upernet) and the flagship at 8 x 1024^2, alternating blocks, host clock
+between device synchronisations, with the peak device allocation of each.  One JSON line (and --out FILE).
 
-  python tools/heads_bench.py [--tiles 8] [--grid 128] [--rounds 7] [--inner 5] [--steps 12] [--no-step] [--no-ops] [--out FILE]"""
+The feature-pyramid kernels of UPerHead (csrc/fpn.hip) at its grids for that tile -- 512 channels, 256^2 / 128^2 / 64^2 /
+32^2 maps -- each beside the composition of library ops it replaces, alternated in the same way: topdown_merge against resize_bilinear into a
+temporary + axpy_ + absmax, fpn_resize_concat against one resize_bilinear(out=slice) per level + absmax of the slices,
+fpn_resize_concat_bwd against one resize_bilinear_bwd per level; achieved bytes per second from the bytes the shapes say must move.
+
+  python tools/heads_bench.py [--tiles 8] [--grid 128] [--rounds 7] [--inner 5] [--steps 12] [--models a,b] [--no-step] [--no-ops] [--no-fpn]
+                              [--out FILE]"""
 import argparse
 import json
 import os
@@ -106,6 +112,61 @@ def ops_bench(args):
     return res
 
 
+def fpn_bench(args):
+    import torch
+    from pfst_amd import hip_ops as ops
+    N, CH, G0 = args.tiles, 512, args.size // 4
+    grids = [G0 >> i for i in range(4)]
+    torch.manual_seed(0)
+    res = dict(tiles=N, channels=CH, grids=grids, rounds=args.rounds, inner=args.inner)
+
+    def rate(r, ours, others, moved):
+        verdict(r, ours, others, moved)
+        r['achieved_TB_s'] = round(moved / (r[ours]['median_ms'] * 1e-3) / 1e12, 3)
+        for o in others:
+            r[f'not_slower_than_{o}_beyond_spread'] = r[ours]['median_ms'] <= r[o]['median_ms'] or r[ours]['min_ms'] <= r[o]['max_ms']
+        return r
+    # ---- the three merges: lateral + resize(coarser), max |out| published
+    for i in (2, 1, 0):
+        hf, hc = grids[i], grids[i + 1]
+        lat = torch.randn(N, CH, hf, hf, device='cuda')
+        coarse = torch.randn(N, CH, hc, hc, device='cuda')
+        out, tmp = torch.empty_like(lat), torch.empty_like(lat)
+        slots = ops.amax_slots(lat.device, 2)
+
+        def composed():
+            ops.resize_bilinear(coarse, (hf, hf), out=tmp)
+            ops.axpy_(tmp, lat)
+            ops.absmax(tmp, out=slots[:ops.AMAX_SUB])
+        res[f'merge_{hc}_to_{hf}'] = rate(alternate(dict(fused=lambda: ops.topdown_merge(lat, coarse, out=out, amax=slots[ops.AMAX_SUB:]),
+                                                         composed=composed), args.rounds, args.inner),
+                                          'fused', ['composed'], 4 * N * CH * (2 * hf * hf + hc * hc))
+        del lat, coarse, out, tmp
+    # ---- the three coarser levels into their slices of the concat, and back
+    hf = grids[0]
+    srcs = [torch.randn(N, CH, g, g, device='cuda').relu_() for g in grids[1:]]
+    cat = torch.empty(N, 4 * CH, hf, hf, device='cuda')
+    up = cat[:, CH:]
+    slots = ops.amax_slots(cat.device, 2)
+    moved = 4 * N * CH * (3 * hf * hf + sum(g * g for g in grids[1:]))
+
+    def per_level():
+        for k, s in enumerate(srcs):
+            ops.resize_bilinear(s, (hf, hf), out=up[:, k * CH:(k + 1) * CH])
+        ops.absmax(up, out=slots[:ops.AMAX_SUB])
+    res['concat'] = rate(alternate(dict(fused=lambda: ops.fpn_resize_concat(srcs, up, amax=slots[ops.AMAX_SUB:]), per_level=per_level),
+                                   args.rounds, args.inner), 'fused', ['per_level'], moved)
+    cat.normal_()
+    outs = [torch.empty_like(s) for s in srcs]
+
+    def per_level_bwd():
+        for k, o in enumerate(outs):
+            ops.resize_bilinear_bwd(up[:, k * CH:(k + 1) * CH], tuple(o.shape[2:]), out=o)
+    res['concat_bwd'] = rate(alternate(dict(fused=lambda: ops.fpn_resize_concat_bwd(up, outs), per_level=per_level_bwd), args.rounds, args.inner),
+                             'fused', ['per_level'], moved)
+    return res
+
+
 def step_bench(args):
     import torch
     from pfst_amd.optim import build_optimizer
@@ -115,8 +176,11 @@ def step_bench(args):
     batch = synth_batch(args.tiles, args.size, 6, 3, seed=1234, device='cuda')
     batch = {k: v for k, v in batch.items() if not k.startswith('target_')}
     cfgs = dict(deeplabv3plus=model_cfg(6, 3), pspnet=baseline_model_cfg('pspnet', 6, 3), deeplabv3=baseline_model_cfg('deeplabv3', 6, 3),
-                fcn=baseline_model_cfg('fcn', 6, 3))
+                fcn=baseline_model_cfg('fcn', 6, 3), upernet=baseline_model_cfg('upernet', 6, 3))
+    if args.models:
+        cfgs = {k: cfgs[k] for k in args.models.split(',')}
     times = {k: [] for k in cfgs}
+    peak = {k: 0 for k in cfgs}
     blocks, per_block = 3, -(-args.steps // 3)
     # one model resident at a time (activations of an 8 x 1024^2 step are tens of GB): blocks of one kind run back to back, kinds in turn
     for blk in range(blocks):
@@ -126,6 +190,7 @@ def step_bench(args):
             model.init_weights()
             model.cuda()
             opt = build_optimizer(model, dict(SGD_OPTIMIZER, lr=6e-5))
+            torch.cuda.reset_peak_memory_stats()
             for _ in range(2):
                 model.train_step(batch, opt)
             torch.cuda.synchronize()
@@ -134,10 +199,12 @@ def step_bench(args):
                 model.train_step(batch, opt)
             torch.cuda.synchronize()
             times[kind].append(1000.0 * (time.perf_counter() - t0) / per_block)
+            peak[kind] = max(peak[kind], torch.cuda.max_memory_allocated())
             del model, opt
     out = dict(tiles=args.tiles, size=args.size, steps_per_block=per_block, blocks=blocks)
     for kind, v in times.items():
-        out[kind] = dict(median_ms_per_step=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2))
+        out[kind] = dict(median_ms_per_step=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2),
+                         peak_allocated_GB=round(peak[kind] / 1e9, 2))
     return out
 
 
@@ -149,7 +216,9 @@ def main(argv=None):
     p.add_argument('--rounds', type=int, default=7)
     p.add_argument('--inner', type=int, default=5)
     p.add_argument('--steps', type=int, default=12, help='timed supervised steps per model')
+    p.add_argument('--models', default=None, help='comma-separated kinds of the supervised-step part (deeplabv3plus,pspnet,deeplabv3,fcn,upernet); default all')
     p.add_argument('--no-step', action='store_true')
+    p.add_argument('--no-fpn', action='store_true')
     p.add_argument('--no-ops', action='store_true')
     p.add_argument('--out', default=None)
     args = p.parse_args(argv)
@@ -158,6 +227,9 @@ def main(argv=None):
     res = dict(device=torch.cuda.get_device_name(0))
     if not args.no_ops:
         res['ops'] = ops_bench(args)
+        torch.cuda.empty_cache()
+    if not args.no_fpn:
+        res['fpn'] = fpn_bench(args)
         torch.cuda.empty_cache()
     if not args.no_step:
         res['supervised_step'] = step_bench(args)
