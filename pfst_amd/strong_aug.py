@@ -18,11 +18,12 @@ def _blur_kernel_size(n):
 
 
 def _gauss_taps(k, sigma):
-    x = torch.arange(k, dtype=torch.float32) - k // 2
+    # evaluated in float64, rounded once: in float32 the rounding of the exponent alone (|arg| 2^-24) put the outer taps 2e-6 off
+    x = torch.arange(k, dtype=torch.float64) - k // 2
     if k % 2 == 0:
         x = x + 0.5
     g = torch.exp(-x.pow(2) / (2.0 * sigma * sigma))
-    return g / g.sum()
+    return (g / g.sum()).float()
 
 
 def apply_strong_aug(mixed_img, img_metas, jitter_draw, jitter_p, jitter_s, blur_draw, denorm_type='mean_std'):

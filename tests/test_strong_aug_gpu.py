@@ -1,63 +1,16 @@
-"""Strong-augmentation kernels (colour jitter, gaussian blur) against a PyTorch restatement of the SAME documented
-kornia-0.6 formulas written here (kornia itself is not installed: parity with the reference's third-party arithmetic is
-'unpinned'; this test pins the kernels to the restated formulas and checks their invariants)."""
-import math
-
+"""Strong-augmentation kernels (colour jitter, gaussian blur) against a restatement of the SAME documented kornia-0.6 formulas
+(kornia itself is not installed: parity with the reference's third-party arithmetic is 'unpinned'; this test pins the
+kernels to the restated formulas -- the jitter to the float64 ones of tests/strong_aug_oracle.py, the blur to F.conv2d -- and checks
+their invariants).  The edge cases live in tests/test_strong_aug_edges_gpu.py, the train step in tests/test_strong_aug_step_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import strong_aug_oracle as SO
+
 pytestmark = pytest.mark.gpu
 MEAN = torch.tensor([123.675, 116.28, 103.53]).view(1, 3, 1, 1)
 STD = torch.tensor([58.395, 57.12, 57.375]).view(1, 3, 1, 1)
-
-
-def rgb_to_hsv(img):
-    mx, arg = img.max(1)
-    mn = img.min(1)[0]
-    d = mx - mn
-    v = mx
-    s = d / (mx + 1e-8)
-    d = torch.where(d == 0, torch.ones_like(d), d)
-    r, g, b = img[:, 0], img[:, 1], img[:, 2]
-    rc, gc, bc = mx - r, mx - g, mx - b
-    h = torch.stack([bc - gc, (rc - bc) + 2 * d, (gc - rc) + 4 * d], 1).gather(1, arg.unsqueeze(1)).squeeze(1)
-    h = ((h / d) / 6.0) % 1.0
-    return torch.stack([2 * math.pi * h, s, v], 1)
-
-
-def hsv_to_rgb(hsv):
-    h, s, v = hsv[:, 0] / (2 * math.pi), hsv[:, 1], hsv[:, 2]
-    h6 = h * 6
-    fl = torch.floor(h6)
-    hi = fl.long() % 6
-    f = h6 - fl
-    p, q, t = v * (1 - s), v * (1 - f * s), v * (1 - (1 - f) * s)
-    table = torch.stack([torch.stack([v, t, p], 1), torch.stack([q, v, p], 1), torch.stack([p, v, t], 1),
-                         torch.stack([p, q, v], 1), torch.stack([t, p, v], 1), torch.stack([v, p, q], 1)], 1)   # [N,6,3,H,W]
-    idx = hi.unsqueeze(1).unsqueeze(1).expand(-1, 1, 3, -1, -1)
-    return table.gather(1, idx).squeeze(1)
-
-
-def ref_jitter(img, prm):
-    out = []
-    for i in range(img.shape[0]):
-        x = (img[i:i + 1] * STD + MEAN) / 255.0
-        bf, cf, sf, hf = [float(v) for v in prm[i, :4]]
-        for op in prm[i, 4:].long().tolist():
-            if op == 0:
-                x = (x + bf - 1).clamp(0, 1)
-            elif op == 1:
-                x = (x * cf).clamp(0, 1)
-            else:
-                hsv = rgb_to_hsv(x)
-                if op == 2:
-                    hsv[:, 1] = (hsv[:, 1] * sf).clamp(0, 1)
-                else:
-                    hsv[:, 0] = torch.remainder(hsv[:, 0] + hf, 2 * math.pi)
-                x = hsv_to_rgb(hsv)
-        out.append((x * 255.0 - MEAN) / STD)
-    return torch.cat(out)
 
 
 def test_color_jitter_matches_restated_formulas():
@@ -66,11 +19,15 @@ def test_color_jitter_matches_restated_formulas():
     n, S = 3, 48
     img = torch.randn(n, 3, S, S, generator=g)
     prm = torch.tensor([[1.1, 0.9, 1.15, 0.3, 0, 1, 2, 3], [0.85, 1.2, 0.8, -0.7, 3, 2, 1, 0], [1.0, 1.0, 1.0, 0.0, 2, 0, 3, 1]])
-    ref = ref_jitter(img, prm)
     out = ops.color_jitter_(img.clone().cuda(), prm.cuda(), MEAN.flatten().cuda(), STD.flatten().cuda(), True).cpu()
-    err = (out - ref).abs()
-    # hue arithmetic is discontinuous at sector borders: allow a handful of pixels to differ, the rest must be tight
-    assert float((err > 1e-3).float().mean()) < 2e-3 and float(err.median()) < 1e-5
+    # the fp64 reference and the out-of-gamut bound of tests/strong_aug_oracle.py (64 x 2^-24 x 255 / std x the factors above 1 x
+    # max(1, |s|)), EVERY pixel: the composed map is continuous across sector borders and hue ties, so no pixel is exempt.  (This test
+    # used to let 0.2 % of the pixels be off by more than 1e-3; on the MI355X none is off by more than 4.1e-6, 0.2 of this bound.)
+    ratio, ref, _ = SO.jitter_ratio(out, img, prm, True, out_of_gamut=True)
+    assert float(SO.jitter_ex(img, prm)[2].max()) < 8.0, 'condition on the input: |s| stays off the singularity, the bound is not vacuous'
+    print(f'colour jitter on the N(0, 1) image: {ratio:.3g} of the bound')
+    err = (out.double() - ref).abs()
+    assert ratio < 1.0 and float(err.median()) < 1e-5
     # identity parameters leave in-gamut pixels unchanged
     ident = torch.tensor([[1.0, 1.0, 1.0, 0.0, 0, 1, 2, 3]])
     x = (torch.rand(1, 3, S, S, generator=g) * 255.0 - MEAN) / STD
