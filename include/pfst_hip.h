@@ -390,7 +390,7 @@ int pfst_softmax_nchw(const float* x, long long x_bs, float* y, long long y_bs, 
 int pfst_window_accumulate(const float* crop, float* preds, float* count, int N, int C, int Hc, int Wc, int H, int W, int y1, int x1,
                            pfst_stream_t stream);
 int pfst_window_normalize(float* preds, const float* count, int N, int C, int HW, pfst_stream_t stream);      /* preds / count_mat (:256) */
-/* seg_logit.argmax(dim=1) (:332, :368): first maximal class per pixel, uint8 */
+/* seg_logit.argmax(dim=1) (:332, :368): first maximal class per pixel, the first NaN class if there is one (torch.argmax), uint8 */
 int pfst_argmax_nchw(const float* x, long long x_bs, unsigned char* label_u8, int N, int C, int HW, pfst_stream_t stream);
 /* output.flip(dims=(3,)) / (2,) (:316-325) on `planes` H x W maps, out of place */
 int pfst_flip_planes(const float* x, float* y, int planes, int H, int W, int horizontal, int vertical, pfst_stream_t stream);

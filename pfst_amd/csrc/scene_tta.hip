@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void scene_tta_finalize_kernel(const float* __
       for (int k = 0; k < 4; ++k) {
         v[k] = __fdiv_rn(v[k], views);
         if (c == 0) best[k] = v[k];
-        else if (v[k] > best[k]) { best[k] = v[k]; arg[k] = (unsigned char)c; }
+        else if (v[k] > best[k] || (v[k] != v[k] && best[k] == best[k])) { best[k] = v[k]; arg[k] = (unsigned char)c; }   // the first NaN wins
       }
       if (probs) {
         float* qp = probs + (i64)c * HW + p;

@@ -405,7 +405,7 @@ __global__ void window_normalize_kernel(float* __restrict__ preds, const float* 
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x)
     preds[((i64)n * C + c) * HW + i] = __fdiv_rn(preds[((i64)n * C + c) * HW + i], count[(i64)n * HW + i]);
 }
-__global__ void argmax_nchw_kernel(const float* __restrict__ x, i64 x_bs, unsigned char* __restrict__ lab, int C, int HW) {  // first maximal class
+__global__ void argmax_nchw_kernel(const float* __restrict__ x, i64 x_bs, unsigned char* __restrict__ lab, int C, int HW) {  // first maximal class; the first NaN class wins (torch.argmax)
   const int n = blockIdx.y;
   const float* xp = x + (i64)n * x_bs;
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
@@ -413,7 +413,7 @@ __global__ void argmax_nchw_kernel(const float* __restrict__ x, i64 x_bs, unsign
     int arg = 0;
     for (int c = 1; c < C; ++c) {
       const float v = xp[(i64)c * HW + p];
-      if (v > best) { best = v; arg = c; }
+      if (v > best || (v != v && best == best)) { best = v; arg = c; }
     }
     lab[(i64)n * HW + p] = (unsigned char)arg;
   }
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __rest
   }
 }
 // seg_logit /= views (div_scalar_kernel's __fdiv_rn, BEFORE the comparison: ties made by the rounding resolve as in div + argmax), then the
-// first maximal class (argmax_nchw_kernel).  Only the labels are written.  Four pixels per thread, 16-byte loads when HW % 4 == 0.
+// first maximal class, the first NaN winning (argmax_nchw_kernel).  Only the labels are written.  Four pixels per thread, 16-byte loads when HW % 4 == 0.
 __global__ __launch_bounds__(256) void tta_finalize_kernel(const float* __restrict__ acc, int C, int HW, float views,
                                                            unsigned char* __restrict__ lab) {
   const int n = blockIdx.y;
@@ -546,10 +546,10 @@ __global__ __launch_bounds__(256) void tta_finalize_kernel(const float* __restri
     for (int c = 1; c < C; ++c) {
       const float4 v = *reinterpret_cast<const float4*>(ap + (i64)c * HW);
       const float x = __fdiv_rn(v.x, views), y = __fdiv_rn(v.y, views), z = __fdiv_rn(v.z, views), w = __fdiv_rn(v.w, views);
-      if (x > best.x) { best.x = x; arg.x = (unsigned char)c; }
-      if (y > best.y) { best.y = y; arg.y = (unsigned char)c; }
-      if (z > best.z) { best.z = z; arg.z = (unsigned char)c; }
-      if (w > best.w) { best.w = w; arg.w = (unsigned char)c; }
+      if (x > best.x || (x != x && best.x == best.x)) { best.x = x; arg.x = (unsigned char)c; }
+      if (y > best.y || (y != y && best.y == best.y)) { best.y = y; arg.y = (unsigned char)c; }
+      if (z > best.z || (z != z && best.z == best.z)) { best.z = z; arg.z = (unsigned char)c; }
+      if (w > best.w || (w != w && best.w == best.w)) { best.w = w; arg.w = (unsigned char)c; }
     }
     *reinterpret_cast<uchar4*>(lp) = arg;
     return;
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(256) void tta_finalize_kernel(const float* __restri
     int arg = 0;
     for (int c = 1; c < C; ++c) {
       const float v = __fdiv_rn(ap[(i64)c * HW + k], views);
-      if (v > best) { best = v; arg = c; }
+      if (v > best || (v != v && best == best)) { best = v; arg = c; }
     }
     lp[k] = (unsigned char)arg;
   }

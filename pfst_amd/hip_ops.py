@@ -1166,7 +1166,7 @@ def window_normalize_(preds, count):
 
 
 def argmax_nchw(x):
-    """x.argmax(dim=1) as uint8 [N, H, W] (first maximal class)"""
+    """x.argmax(dim=1) as uint8 [N, H, W] (first maximal class; the first NaN class where a pixel holds one, as torch.argmax)"""
     n, c, h, w = x.shape
     lab = torch.empty(n, h, w, dtype=U8, device=x.device)
     call('pfst_argmax_nchw', x.data_ptr(), _bs(x), lab.data_ptr(), n, c, h * w, _stream())
