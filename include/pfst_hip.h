@@ -136,6 +136,14 @@ int pfst_wino_output(const float* Mbuf, float* y, long long y_bs, int N, int Cou
 int pfst_wino_stats_slots(int H, int W, int dil, int m);
 int pfst_wino_dy(const float* dy, long long dy_bs, float* dM, int N, int Cout, int H, int W, int dil, int m, float* dm_amax,
                  const float* pack_dy_amax, pfst_stream_t stream);
+/* the data gradient from the weight gradient's transform (f16x3): P [X][N][Cin][T] = pfst_wino_gemm_f16x3(dM packed by pfst_wino_dy, the
+ * UNFLIPPED forward filter sets packed in the data-gradient layout (K = Cout, rows = Cin), the forward sets' maxima, v_packed = 1);
+ * pfst_wino_dx forms the R x R patches B P B^T and overlap-adds them at stride m into dx [N][Cin][H][W] as a gather with a fixed
+ * summation order (no atomics).  partials / bnb_*: as pfst_wino_output's stats / bnb_* -- the BatchNorm-backward partials
+ * [Cin][N * pfst_wino_dx_slots(H, W, dil, m)][2] of the layer that owns dx (both given or both NULL) */
+int pfst_wino_dx_slots(int H, int W, int dil, int m);
+int pfst_wino_dx(const float* P, float* dx, long long dx_bs, int N, int Cin, int H, int W, int dil, int accumulate, float* partials,
+                 const float* bnb_x, long long bnb_x_bs, const float* bnb_coef, int bnb_relu, int m, pfst_stream_t stream);
 int pfst_wino_wgrad(const float* V, const float* dM, float* dU, float* dw, int N, int Cin, int Cout, int T, int m,
                     int split, const float* v_amax, const float* dm_amax, int packed, pfst_stream_t stream);
 /* split = 1: the transform-domain products with the fp32-faithful bf16x6 split on the bf16 matrix cores; split = 2: with the f16x3 split,

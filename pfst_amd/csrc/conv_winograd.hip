@@ -8,6 +8,10 @@
 // Data gradient = the same pipeline on dY with the flipped / transposed filter.  Weight gradient:
 //   dU_xi[co][ci] = sum_{n,t} dM_xi[n][co][t] V_xi[n][ci][t]   (one grouped launch of the 1x1 K-quad wgrad kernel),  dM = A dY A^T,
 //   dW = G^T dU G.
+// Data gradient from the SAME dM (the f16x3 layers whose weight gradient runs here; pfst_wino_dx): the exact adjoint of the forward map,
+//   dX patch (R x R) = B [ sum_co (G g G^T)[co][ci] (.) dM[co] ] B^T,   patches overlap-added at stride m (rows / columns -1 .. m of a tile),
+// i.e. the GEMM on dM with the UNFLIPPED forward filter sets, transposed (K = Cout, rows = Cin; same per-set maxima as the forward
+// sets), and wino_dx_kernel in place of the output transform: dY is transformed once per layer instead of twice (no B^T dY B).
 // Dilation d: a dilated 3x3 convolution is d*d independent dilation-1 convolutions on the interleaved sub-grids
 // (y mod d, x mod d); the tile index enumerates them (column offset fastest), so the same kernels serve d = 1, 2, 4.
 // Transform matrices (Lavin & Gray 2016, correlation form; interpolation points 0, +-1 [, +-2], inf):
@@ -422,6 +426,266 @@ __global__ __launch_bounds__(256) void wino_dy_kernel(const float* __restrict__ 
   if (amax && !pack_amax) amax_publish(amax, am);
 }
 
+// ---- adjoint of the input transform: dX = overlap-add of the R x R patches B p B^T at stride M (patch rows / columns -1 .. M of a
+// tile), p = P[.][n][ci][t] the transform-domain product of dM with the transposed forward filter sets.  The overlap-add is a GATHER:
+// one thread per tile owns the tile's M x M pixels = the interior of its own patch + the facing rim row / column of its four edge
+// neighbours + one corner element of its four diagonal neighbours, always summed in that order (no atomics; the result does not
+// depend on how tiles are grouped into workgroups).  A workgroup covers a strip of DxBlocks::OH tile rows x OW columns of one
+// sub-grid row sy (columns count the d interleaved sub-grids, cx = tx * d + sx: the strip is one contiguous tile range per row);
+// every thread publishes its patch's rim (2 R + 2 M values) to LDS, and a tile on the strip's rim forms the few rim values of
+// its outside neighbours itself: column 0 / R-1 of B^T holds one non-zero, so a rim row needs ONE row of p (R values of R*R), a rim
+// column one column, a corner one element -- the re-read is 2 (R + 2) / (OH R R) of P for full-width strips (5 % at OH = 8).
+struct DxBlocks {
+  int OW, OH, nbx, nby;            // tiles per workgroup (columns, rows), workgroups per sub-grid row (columns, rows)
+};
+inline DxBlocks dx_blocks(const WinoGeom& g) {
+  const int Wd = g.Tw * g.d;
+  DxBlocks b;
+  b.OW = Wd < 256 ? Wd : 256;
+  b.OH = 256 / b.OW < g.Th ? 256 / b.OW : g.Th;
+  b.nbx = (Wd + b.OW - 1) / b.OW;
+  b.nby = (g.Th + b.OH - 1) / b.OH;
+  return b;
+}
+// q[b] = (p B^T)[b] of one row of p; patch[a] = (B q)[a] of one column of q -- the two halves of B p B^T, shared by the full transform
+// and the rim-only forms so that both round alike
+template <int M, int B>
+__device__ __forceinline__ float dx_row_tf(const float (&p)[M + 2]) {
+  float a = 0.f;
+#pragma unroll
+  for (int l = 0; l < M + 2; ++l) a = cmac(a, Wino<M>::bt(l, B), p[l]);
+  return a;
+}
+template <int M, int A>
+__device__ __forceinline__ float dx_col_tf(const float (&q)[M + 2]) {
+  float a = 0.f;
+#pragma unroll
+  for (int k = 0; k < M + 2; ++k) a = cmac(a, Wino<M>::bt(k, A), q[k]);
+  return a;
+}
+template <int M, int I = 0>
+__device__ __forceinline__ void dx_rows(const float (&p)[M + 2], float (&q)[M + 2]) {          // q = p B^T, every column
+  if constexpr (I < M + 2) {
+    q[I] = dx_row_tf<M, I>(p);
+    dx_rows<M, I + 1>(p, q);
+  }
+}
+template <int M, int I = 0>
+__device__ __forceinline__ void dx_cols(const float (&q)[M + 2], float (&o)[M + 2]) {          // o = B q, every row
+  if constexpr (I < M + 2) {
+    o[I] = dx_col_tf<M, I>(q);
+    dx_cols<M, I + 1>(q, o);
+  }
+}
+// rim row A (0 or R-1) of the patch of tile tn from row A of its p: out[b], b = 0 .. R-1
+template <int M, int A>
+__device__ __forceinline__ void dx_rim_row(const float* __restrict__ pp, i64 plane, int tn, float (&out)[M + 2]) {
+  constexpr int R = M + 2;
+  float p[R], q[R], z[R];
+#pragma unroll
+  for (int l = 0; l < R; ++l) p[l] = pp[(i64)(A * R + l) * plane + tn];
+  dx_rows<M>(p, q);
+#pragma unroll
+  for (int b = 0; b < R; ++b) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) z[k] = k == A ? q[b] : 0.f;          // (B^T's column A is zero off the diagonal: rows k != A never enter)
+    out[b] = dx_col_tf<M, A>(z);
+  }
+}
+// rim column B (0 or R-1) of the patch of tile tn from column B of its p: out[a], a = 0 .. R-1
+template <int M, int B>
+__device__ __forceinline__ void dx_rim_col(const float* __restrict__ pp, i64 plane, int tn, float (&out)[M + 2]) {
+  constexpr int R = M + 2;
+  float q[R], z[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+#pragma unroll
+    for (int l = 0; l < R; ++l) z[l] = l == B ? pp[(i64)(k * R + B) * plane + tn] : 0.f;
+    q[k] = dx_row_tf<M, B>(z);
+  }
+  dx_cols<M>(q, out);
+}
+// corner (A, B) of the patch of tile tn from the one element of p it depends on
+template <int M, int A, int B>
+__device__ __forceinline__ float dx_rim_corner(const float* __restrict__ pp, i64 plane, int tn) {
+  constexpr int R = M + 2;
+  float z[R], y[R];
+#pragma unroll
+  for (int l = 0; l < R; ++l) z[l] = l == B ? pp[(i64)(A * R + B) * plane + tn] : 0.f;
+  const float q = dx_row_tf<M, B>(z);
+#pragma unroll
+  for (int k = 0; k < R; ++k) y[k] = k == A ? q : 0.f;
+  return dx_col_tf<M, A>(y);
+}
+
+// grid: (d * nby * nbx strips, Cin, N); 256 threads.  partials / bnb_*: as wino_output_kernel's stats / bnb_* (BatchNorm-backward sums of the
+// layer that owns dx, one slot per workgroup: [Cin][N * gridDim.x][2])
+template <int M>
+__global__ __launch_bounds__(256) void wino_dx_kernel(const float* __restrict__ P, float* __restrict__ dx, i64 dx_bs, int N, int C, WinoGeom g,
+                                                      DxBlocks bl, int accumulate, int vec, float* __restrict__ partials,
+                                                      const float* __restrict__ bnb_x, i64 bnb_x_bs, const float4* __restrict__ bnb_coef, int bnb_relu) {
+  constexpr int R = M + 2;
+  constexpr int TOP = 0, BOT = R, LEFT = 2 * R, RIGHT = 2 * R + M;          // rim[.][tile]: patch rows 0 and R-1 (R values), columns 0 and R-1 (rows 1 .. M)
+  typedef float vecM __attribute__((ext_vector_type(M)));
+  __shared__ float rim[2 * R + 2 * M][256];
+  __shared__ double red[32];
+  const int c = blockIdx.y, n = blockIdx.z;
+  int b = blockIdx.x;
+  const int bx = b % bl.nbx; b /= bl.nbx;
+  const int by = b % bl.nby;
+  const int sy = b / bl.nby;
+  const int Wd = g.Tw * g.d;
+  const int lr = threadIdx.x / bl.OW, lc = threadIdx.x - lr * bl.OW;
+  const int ty = by * bl.OH + lr, cx = bx * bl.OW + lc;
+  const bool live = lr < bl.OH && ty < g.Th && cx < Wd;
+  const i64 plane = (i64)N * C * g.T;
+  const float* pp = P + ((i64)n * C + c) * g.T;
+  const int t = (sy * g.Th + ty) * Wd + cx;                   // = tile_coord's index of (sy, sx = cx % d, ty, tx = cx / d)
+  float o[M][M];
+  if (live) {
+    float q[R][R];                                            // p B^T
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      float p[R];
+#pragma unroll
+      for (int l = 0; l < R; ++l) p[l] = __builtin_nontemporal_load(&pp[(i64)(k * R + l) * plane + t]);
+      dx_rows<M>(p, q[k]);
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {                             // B (p B^T), column by column
+      float col[R], pc[R];
+#pragma unroll
+      for (int k = 0; k < R; ++k) col[k] = q[k][j];
+      dx_cols<M>(col, pc);
+      rim[TOP + j][threadIdx.x] = pc[0];
+      rim[BOT + j][threadIdx.x] = pc[R - 1];
+      if (j == 0 || j == R - 1) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) rim[(j == 0 ? LEFT : RIGHT) + i][threadIdx.x] = pc[1 + i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < M; ++i) o[i][j - 1] = pc[1 + i];
+      }
+    }
+  }
+  __syncthreads();
+  float st_s = 0.f, st_q = 0.f;
+  if (live) {
+    // neighbour (ty + dty, cx + dcs * d): 0 = no such tile, 1 = in this workgroup (rim[.][nt]), 2 = outside it (tile index nt of P)
+    int nt;
+    auto nbr = [&](int dty, int dcs) {
+      const int nty = ty + dty, ncx = cx + dcs * g.d;
+      if (nty < 0 || nty >= g.Th || ncx < 0 || ncx >= Wd) return 0;
+      const int nlr = lr + dty, nlc = lc + dcs * g.d;
+      if (nlr >= 0 && nlr < bl.OH && nlc >= 0 && nlc < bl.OW) {
+        nt = nlr * bl.OW + nlc;
+        return 1;
+      }
+      nt = (sy * g.Th + nty) * Wd + ncx;
+      return 2;
+    };
+    float e[R];
+    int k;
+    if ((k = nbr(-1, 0)) != 0) {                              // above: its bottom rim row onto this tile's first row
+      if (k == 1) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) e[1 + j] = rim[BOT + 1 + j][nt];
+      } else {
+        dx_rim_row<M, R - 1>(pp, plane, nt, e);
+      }
+#pragma unroll
+      for (int j = 0; j < M; ++j) o[0][j] += e[1 + j];
+    }
+    if ((k = nbr(1, 0)) != 0) {                               // below: its top rim row onto the last row
+      if (k == 1) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) e[1 + j] = rim[TOP + 1 + j][nt];
+      } else {
+        dx_rim_row<M, 0>(pp, plane, nt, e);
+      }
+#pragma unroll
+      for (int j = 0; j < M; ++j) o[M - 1][j] += e[1 + j];
+    }
+    if ((k = nbr(0, -1)) != 0) {                              // left: its right rim column onto the first column
+      if (k == 1) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) e[1 + i] = rim[RIGHT + i][nt];
+      } else {
+        dx_rim_col<M, R - 1>(pp, plane, nt, e);
+      }
+#pragma unroll
+      for (int i = 0; i < M; ++i) o[i][0] += e[1 + i];
+    }
+    if ((k = nbr(0, 1)) != 0) {                               // right: its left rim column onto the last column
+      if (k == 1) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) e[1 + i] = rim[LEFT + i][nt];
+      } else {
+        dx_rim_col<M, 0>(pp, plane, nt, e);
+      }
+#pragma unroll
+      for (int i = 0; i < M; ++i) o[i][M - 1] += e[1 + i];
+    }
+    if ((k = nbr(-1, -1)) != 0) o[0][0] += k == 1 ? rim[BOT + R - 1][nt] : dx_rim_corner<M, R - 1, R - 1>(pp, plane, nt);
+    if ((k = nbr(-1, 1)) != 0) o[0][M - 1] += k == 1 ? rim[BOT][nt] : dx_rim_corner<M, R - 1, 0>(pp, plane, nt);
+    if ((k = nbr(1, -1)) != 0) o[M - 1][0] += k == 1 ? rim[TOP + R - 1][nt] : dx_rim_corner<M, 0, R - 1>(pp, plane, nt);
+    if ((k = nbr(1, 1)) != 0) o[M - 1][M - 1] += k == 1 ? rim[TOP][nt] : dx_rim_corner<M, 0, 0>(pp, plane, nt);
+
+    float* yp = dx + (i64)n * dx_bs + (i64)c * g.H * g.W;
+    const float* bxp = bnb_x ? bnb_x + (i64)n * bnb_x_bs + (i64)c * g.H * g.W : nullptr;
+    const float bsc = bnb_x ? bnb_coef[c].z : 0.f, bsh = bnb_x ? bnb_coef[c].w : 0.f;
+    const int tx = cx / g.d, sx = cx - tx * g.d;
+    const int x0 = sx + g.d * (M * tx);
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      const int yy = sy + g.d * (M * ty + i);
+      if (yy >= g.H) continue;
+      if (vec) {
+        vecM* qd = reinterpret_cast<vecM*>(yp + (i64)yy * g.W + x0);
+        vecM v;
+#pragma unroll
+        for (int j = 0; j < M; ++j) v[j] = o[i][j];
+        if (accumulate) v += *qd;
+        *qd = v;
+        if (bxp) {
+          const vecM xv = *reinterpret_cast<const vecM*>(bxp + (i64)yy * g.W + x0);
+#pragma unroll
+          for (int j = 0; j < M; ++j) {
+            const float dz = (!bnb_relu || __fmaf_rn(xv[j], bsc, bsh) > 0.f) ? v[j] : 0.f;
+            st_s += dz;
+            st_q = fmaf(dz, xv[j], st_q);
+          }
+        }
+        continue;
+      }
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        const int xx = x0 + g.d * j;
+        if (xx < g.W) {
+          float* qd = yp + (i64)yy * g.W + xx;
+          const float v = accumulate ? *qd + o[i][j] : o[i][j];
+          *qd = v;
+          if (bxp) {
+            const float xs = bxp[(i64)yy * g.W + xx];
+            const float dz = (!bnb_relu || __fmaf_rn(xs, bsc, bsh) > 0.f) ? v : 0.f;
+            st_s += dz;
+            st_q = fmaf(dz, xs, st_q);
+          }
+        }
+      }
+    }
+  }
+  if (partials) {                                    // partials[c][n * gridDim.x + blockIdx.x][2] for pfst_bn_backward(bwd_partials)
+    double bs = (double)st_s, bq = (double)st_q;
+    block_sum2_d<true>(bs, bq, red);
+    if (threadIdx.x == 0) {
+      const i64 T = (i64)gridDim.x * gridDim.z;
+      float2* dst = reinterpret_cast<float2*>(partials) + ((i64)c * T + (i64)n * gridDim.x + blockIdx.x);
+      *dst = make_float2((float)bs, (float)bq);
+    }
+  }
+}
+
 // ---- dW += G^T dU G.   dU [R*R][Cout][Cin] (row-major as the 1x1 wgrad kernel writes it).  One thread per (co, ci)
 template <int M>
 __global__ void wino_dw_kernel(const float* __restrict__ dU, float* __restrict__ dw, int Cout, int Cin) {
@@ -633,6 +897,33 @@ extern "C" int pfst_wino_dy(const float* dy, long long dy_bs, float* dM, int N, 
   const dim3 grid(tile_blocks(g.T), Cout, N);
   PFST_WINO_M(m, hipLaunchKernelGGL(wino_dy_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, dy, dy_bs, dM, N, Cout, g, dm_amax, pack_dy_amax, shift_dy),
               hipLaunchKernelGGL(wino_dy_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, dy, dy_bs, dM, N, Cout, g, dm_amax, pack_dy_amax, shift_dy));
+  PFST_CHECK_LAUNCH();
+  return PFST_OK;
+}
+
+extern "C" int pfst_wino_dx_slots(int H, int W, int dil, int m) {
+  if (H <= 0 || W <= 0 || dil < 1 || (m != 2 && m != 4)) return 0;
+  const WinoGeom g = wino_geom(H, W, dil, m);
+  const DxBlocks bl = dx_blocks(g);
+  return dil * bl.nby * bl.nbx;
+}
+
+// the data gradient out of the weight gradient's transform: P [X][N][Cin][T] = pfst_wino_gemm_f16x3(dM, transposed forward filter sets) -> dx
+extern "C" int pfst_wino_dx(const float* P, float* dx, long long dx_bs, int N, int Cin, int H, int W, int dil, int accumulate, float* partials,
+                            const float* bnb_x, long long bnb_x_bs, const float* bnb_coef, int bnb_relu, int m, pfst_stream_t stream) {
+  PFST_CHECK_ARG(P && dx && N > 0 && N <= 65535 && Cin > 0 && Cin <= 65535 && H > 0 && W > 0 && dil >= 1 && dx_bs >= (i64)Cin * H * W);
+  PFST_CHECK_ARG(!bnb_x == !partials);
+  PFST_CHECK_ARG(!bnb_x || (bnb_coef && bnb_x_bs >= (i64)Cin * H * W && (bnb_x_bs % 4) == 0 && ((uintptr_t)bnb_x & 15) == 0));
+  PFST_CHECK_TILE(m);
+  const WinoGeom g = wino_geom(H, W, dil, m);
+  const DxBlocks bl = dx_blocks(g);
+  PFST_CHECK_ARG((i64)dil * bl.nby * bl.nbx < (1ll << 31));
+  const int vec = dil == 1 && W % m == 0 && dx_bs % m == 0 && ((uintptr_t)dx & (4 * m - 1)) == 0;
+  const dim3 grid(dil * bl.nby * bl.nbx, Cin, N);
+  PFST_WINO_M(m, hipLaunchKernelGGL(wino_dx_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, P, dx, (i64)dx_bs, N, Cin, g, bl, accumulate, vec, partials, bnb_x,
+                                 (i64)bnb_x_bs, reinterpret_cast<const float4*>(bnb_coef), bnb_relu),
+              hipLaunchKernelGGL(wino_dx_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, P, dx, (i64)dx_bs, N, Cin, g, bl, accumulate, vec, partials, bnb_x,
+                                 (i64)bnb_x_bs, reinterpret_cast<const float4*>(bnb_coef), bnb_relu));
   PFST_CHECK_LAUNCH();
   return PFST_OK;
 }

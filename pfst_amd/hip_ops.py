@@ -550,9 +550,15 @@ def wino_pack_weight_split(w, want_fprop=True, want_dgrad=True, out_f=None, out_
     return uf, ud
 
 
-def wino_pack_weight_f16(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None, m=None):
+def wino_pack_weight_f16(w, want_fprop=True, want_dgrad=True, out_f=None, out_d=None, m=None, shared_dy=False):
     """transform-domain filters for the f16x3 GEMM: X two-piece fp16 sets (uint8 buffers of X * 4 * Cout * Cin bytes) + the X slots with
-    each set's absolute maximum; -> (uf, ud, amax_f, amax_d)"""
+    each set's absolute maximum; -> (uf, ud, amax_f, amax_d).
+    shared_dy: the data-gradient image is the one wino_dgrad_shared reads -- the UNFLIPPED forward sets in the data-gradient layout
+    (K = Cout, rows = Cin), scaled by the forward sets' maxima (amax_d is amax_f) -- instead of the flipped sets wino_conv reads"""
+    if shared_dy and want_dgrad:
+        m, nx, co, ci, pf, _ = _wino_filter_plain(w, True, False, m)
+        uf, ud, af = pack_weight_f16x2(pf[:nx * co * ci].view(nx, co, ci), want_fprop, True, out_f=out_f, out_d=out_d, sets=nx)
+        return uf, ud, (af if want_fprop else None), af
     m, nx, co, ci, pf, pd = _wino_filter_plain(w, want_fprop, want_dgrad, m)
     uf = ud = af = ad = None
     if want_fprop:
@@ -616,15 +622,67 @@ def wino_conv(x, u, cout, dil, out=None, accumulate=False, keep_v=False, want_st
     return res if len(res) > 1 else res[0]
 
 
-def wino_wgrad_(dw, x, dy, dil, v=None, m=None, split=False, v_amax=None, x_amax=None, dy_amax=None):
+def wino_dy(dy, dil, dy_amax=None, m=None):
+    """dM = A dY A^T of an f16x3 Winograd layer, PRE-SPLIT, in a tensor of its own (not the 'M' scratch: the data-gradient GEMM's result
+    lives there while the weight gradient still reads dM on its side stream) -> (dM, dm_amax), for wino_dgrad_shared and
+    wino_wgrad_(dm=...); dy_amax: the slot group with max |dy| (computed here otherwise)"""
+    n, co, h, w = dy.shape
+    m, nx = _wino_m(m)
+    t = wino_tiles(h, w, dil, m)
+    dm = torch.empty(nx * n * co * t, dtype=F32, device=dy.device)
+    dm_amax = amax_slots(dy.device)
+    if dy_amax is None:
+        dy_amax = absmax(dy)
+    call('pfst_wino_dy', dy.data_ptr(), _bs(dy), dm.data_ptr(), n, co, h, w, dil, m, dm_amax.data_ptr(), dy_amax.data_ptr(), _stream())
+    return dm, dm_amax
+
+
+def wino_dx_slots(h, w, dil, m=None):
+    return lib().pfst_wino_dx_slots(h, w, dil, _wino_m(m)[0])
+
+
+def wino_dx(p, cin, hw, dil, n, out=None, accumulate=False, m=None, bnb=None):
+    """dx [n, cin, h, w] from the transform-domain product P [X][n][cin][T] of dM with the transposed forward filter sets: the patches
+    B P B^T overlap-added at stride m (pfst_wino_dx: a gather in a fixed order, bitwise reproducible); out / accumulate / bnb as wino_conv"""
+    h, w = hw
+    m, nx = _wino_m(m)
+    assert p.numel() >= nx * n * cin * wino_tiles(h, w, dil, m)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(n, cin, h, w, device=p.device)
+    assert tuple(out.shape) == (n, cin, h, w)
+    st, slots, bx, bx_bs, bcoef, brelu = None, 0, 0, 0, 0, 0
+    if bnb is not None:
+        pre, coef, relu = bnb
+        assert tuple(pre.shape) == (n, cin, h, w) and tuple(coef.shape) == (cin, 4)
+        slots = n * wino_dx_slots(h, w, dil, m)
+        st = torch.empty(2 * cin * slots, dtype=F32, device=p.device)         # owned by the layer's context until its bn_backward ran
+        bx, bx_bs, bcoef, brelu = pre.data_ptr(), _bs(pre), _dense(coef).data_ptr(), int(relu)
+    call('pfst_wino_dx', p.data_ptr(), out.data_ptr(), _bs(out), n, cin, h, w, dil, int(accumulate), _p(st), bx, bx_bs, bcoef, brelu, m, _stream())
+    return (out, st, slots) if bnb is not None else out
+
+
+def wino_dgrad_shared(dm, dm_amax, ut, ut_amax, n, cout, cin, hw, dil, out=None, accumulate=False, m=None, bnb=None):
+    """the data gradient of an f16x3 Winograd layer from the weight gradient's transform dM (wino_dy): the f16x3 GEMM of dM with the
+    transposed forward filter sets (wino_pack_weight_f16(shared_dy=True): ut, ut_amax) into the 'M' scratch, then wino_dx"""
+    h, w = hw
+    m, nx = _wino_m(m)
+    t = wino_tiles(h, w, dil, m)
+    assert dm.numel() >= nx * n * cout * t and ut.dtype == U8 and ut.numel() == nx * 4 * cin * cout, 'filter set was packed for another tile size'
+    pb = _scratch(dm.device, 'M', nx * n * cin * t)
+    call('pfst_wino_gemm_f16x3', dm.data_ptr(), ut.data_ptr(), ut_amax.data_ptr(), dm_amax.data_ptr(), pb.data_ptr(), n, cout, cin, t, m, 1, _stream())
+    return wino_dx(pb, cin, hw, dil, n, out=out, accumulate=accumulate, m=m, bnb=bnb)
+
+
+def wino_wgrad_(dw, x, dy, dil, v=None, m=None, split=False, v_amax=None, x_amax=None, dy_amax=None, dm=None, dm_amax=None):
     """dw += dL/dw of the 'same' 3x3 stride-1 convolution; v: the transformed input kept from the forward pass (same m);
-    split: the transform-domain products with the fp32-faithful bf16x6 split instead of the fp32-input MFMA"""
+    split: the transform-domain products with the fp32-faithful bf16x6 split instead of the fp32-input MFMA;
+    dm, dm_amax: the packed transform of dy the data gradient already made (wino_dy; f16x3 only) -- no pfst_wino_dy here"""
     n, ci, h, w = x.shape
     co = dy.shape[1]
     m, nx = _wino_m(m)
     assert dy.shape == (n, co, h, w) and dw.numel() == co * ci * 9
     t = wino_tiles(h, w, dil, m)
-    dm = _scratch(x.device, 'M', nx * n * co * t)
     du = _scratch(x.device, 'U', nx * co * ci)
     # split: False / 0 fp32-input MFMA, True / 1 bf16x6, 2 f16x3 (falls back to bf16x6 for <= 64 rows).  f16x3: both operands PRE-SPLIT by
     # their transforms (v given: the packed V and its bound group kept from the f16x3 forward pass)
@@ -638,10 +696,14 @@ def wino_wgrad_(dw, x, dy, dil, v=None, m=None, split=False, v_amax=None, x_amax
             x_amax = absmax(x)
         call('pfst_wino_input', x.data_ptr(), _bs(x), v.data_ptr(), n, ci, h, w, dil, m, _p(v_amax), _p(x_amax) if f16 else 0, 0, _stream())
     assert v.numel() >= nx * n * ci * t
-    dm_amax = amax_slots(x.device) if f16 else None
-    if f16 and dy_amax is None:
-        dy_amax = absmax(dy)
-    call('pfst_wino_dy', dy.data_ptr(), _bs(dy), dm.data_ptr(), n, co, h, w, dil, m, _p(dm_amax), _p(dy_amax) if f16 else 0, _stream())
+    if dm is not None:
+        assert f16 and dm_amax is not None and dm.numel() >= nx * n * co * t, 'a supplied dM is the packed transform of the f16x3 route'
+    else:
+        dm = _scratch(x.device, 'M', nx * n * co * t)
+        dm_amax = amax_slots(x.device) if f16 else None
+        if f16 and dy_amax is None:
+            dy_amax = absmax(dy)
+        call('pfst_wino_dy', dy.data_ptr(), _bs(dy), dm.data_ptr(), n, co, h, w, dil, m, _p(dm_amax), _p(dy_amax) if f16 else 0, _stream())
     call('pfst_wino_wgrad', v.data_ptr(), dm.data_ptr(), du.data_ptr(), _dense(dw).data_ptr(), n, ci, co, t, m,
          2 if f16 else int(bool(split)), _p(v_amax), _p(dm_amax), int(f16), _stream())
     return dw

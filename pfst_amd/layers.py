@@ -97,6 +97,11 @@ FUSE_BN_BWD_WINO = True
 # a residual layer's gate inside the fused sums: from bn_apply's 1-bit mask of y instead of y (a compile-time variant of the f16x3 epilogue;
 # -0.8 ms per step, profiles/r05_ab_bnb_mask.txt)
 BNB_GATE_FROM_MASK = True
+# f16x3 Winograd layers whose weight gradient runs in the transform domain: the data gradient is built from the weight gradient's
+# dM = A dY A^T (the exact adjoint of the forward map: GEMM with the transposed forward filter sets, then ops.wino_dx) instead of a
+# second transform B^T dY B of the same dY -- one pfst_wino_input launch and its 2.25 N of writes less per layer and backward pass
+# (profiles/wino_shared_dy_ab.txt).  False: the flipped-filter pipeline on dY, pfst_wino_dy on the weight-gradient stream
+WINO_SHARE_DY = True
 
 
 class BnBackwardCtx:
@@ -158,6 +163,7 @@ class Conv2dP(nn.Module):
     w4f = w4d = w_amax = uf_amax = ud_amax = None
     pf = pd = None                            # plain transform-domain filter sets (WeightBatch keeps them per layer)
     wino = False
+    wino_dx = False                           # the data gradient comes from the weight gradient's dM (WINO_SHARE_DY): `ud` holds the transposed FORWARD sets
     saved_v = None
 
     def _wino_eligible(self):
@@ -273,16 +279,21 @@ class Conv2dP(nn.Module):
             return 'quad_bf16x6'
         return 'generic'
 
-    def dgrad(self, dy, in_hw, out, accumulate, bn=None, dy_amax=None, gate=None):
+    def dgrad(self, dy, in_hw, out, accumulate, bn=None, dy_amax=None, gate=None, dm=None):
         """bn: BnBackwardCtx of the layer that produced this conv's input, when this launch completes that gradient;
         dy_amax: slot group with max |dy| (f16x3 layers; computed here when the producer did not publish it);
-        gate: (g, mask) added where the mask has the bit (Var.pending of a residual block's input; only where dgrad_can_gate)"""
+        gate: (g, mask) added where the mask has the bit (Var.pending of a residual block's input; only where dgrad_can_gate);
+        dm: (dM, dm_amax) = ops.wino_dy(dy) where the caller made it already (a wino_dx layer: conv_backward shares it with the weight gradient)"""
         assert gate is None or (self.f16_d and not self.wino and not accumulate)
         kw = dict(out=out, accumulate=accumulate)
         if self.wino:
             if bn is not None:           # the output transform emits the BatchNorm-backward sums of the layer that owns `out` (no residual there)
                 assert bn.y is None
                 kw['bnb'] = (bn.pre, bn.coef, bn.relu)
+        if self.wino and self.wino_dx:
+            dm, dm_amax = dm if dm is not None else ops.wino_dy(dy, self.dilation, dy_amax)
+            res = ops.wino_dgrad_shared(dm, dm_amax, self.ud, self.ud_amax, dy.shape[0], self.cout, self.cin, in_hw, self.dilation, **kw)
+        elif self.wino:
             res = ops.wino_conv(dy, self.ud, self.cin, self.dilation, u_amax=self.ud_amax if self.wino_f16 else None,
                                 x_amax=dy_amax if self.wino_f16 else None, **kw)
         else:
@@ -325,6 +336,9 @@ class Conv2dP(nn.Module):
         """adopt plan(need_dgrad): the mode attributes fprop / dgrad / wgrad_route dispatch on (no buffers, no launches: repack does those)"""
         p = self.plan(need_dgrad)
         self.wino, self.wino_f16, self.f16_f, self.f16_d, self.split_f, self.split_d = p[:6]
+        # (a layer property, like the images: wgrad_route answers 'wino_f16x3' for every plane of such a layer with whole tile quads; on any
+        # other plane the data gradient still takes dM -- made for it alone -- since `ud` holds no flipped sets)
+        self.wino_dx = bool(WINO_SHARE_DY and p.wino_f16 and need_dgrad and self.cin * self.cout >= WINO_MIN_CC_WGRAD)
         return p
 
     def _buffer(self, name, shape, dtype=torch.float32):
@@ -357,7 +371,7 @@ class Conv2dP(nn.Module):
             if p.wino_f16 and batch is not None:
                 batch.add_wino(self, need_dgrad)
             elif p.wino_f16:
-                _, _, self.uf_amax, self.ud_amax = ops.wino_pack_weight_f16(w, True, need_dgrad, uf, ud)
+                _, _, self.uf_amax, self.ud_amax = ops.wino_pack_weight_f16(w, True, need_dgrad, uf, ud, shared_dy=self.wino_dx)
             else:
                 launch(ops.wino_pack_weight_split if split else ops.wino_pack_weight, w, True, need_dgrad, uf, ud)
         taps = self.k * self.k
@@ -379,7 +393,7 @@ class Conv2dP(nn.Module):
 def repack_key(need_dgrad):
     """everything Conv2dP.repack's decisions depend on besides the layer itself: a model replays its recorded packing launches while this (and
     its weight buffers) stay the same"""
-    return (CONV_MATH, bool(need_dgrad), WINOGRAD, WINO_MIN_CC, WINO_MIN_CC_WGRAD, ops.WINO_TILE, ops.F16X3_MIN_ROWS, WeightBatch.enabled)
+    return (CONV_MATH, bool(need_dgrad), WINOGRAD, WINO_MIN_CC, WINO_MIN_CC_WGRAD, ops.WINO_TILE, ops.F16X3_MIN_ROWS, WeightBatch.enabled, WINO_SHARE_DY)
 
 
 class WeightBatch:
@@ -402,14 +416,16 @@ class WeightBatch:
     def add_wino(self, conv, need_dgrad):
         n = (ops.WINO_TILE + 2) ** 2 * conv.cout * conv.cin
         conv._buffer('pf', (n,))                # plain transform-domain sets, resident per layer
-        if need_dgrad:
+        if need_dgrad and not conv.wino_dx:     # (a wino_dx layer's data-gradient image is packed from the forward sets)
             conv._buffer('pd', (n,))
+        else:
+            conv.pd = None                      # (a flipped set kept from an earlier plan is dropped, not left resident)
         self.items.append((conv, ops.WINO_TILE, need_dgrad))
 
     def flush(self):
         if not self.items:
             return
-        key = tuple((id(c), m, dg, c.weight.data_ptr(), c.f16_f, c.f16_d) + tuple(ops._p(getattr(c, a)) for a in ('w4f', 'w4d', 'uf', 'ud', 'pf', 'pd'))
+        key = tuple((id(c), m, dg, c.weight.data_ptr(), c.f16_f, c.f16_d, c.wino_dx) + tuple(ops._p(getattr(c, a)) for a in ('w4f', 'w4d', 'uf', 'ud', 'pf', 'pd'))
                     for c, m, dg in self.items)
         if key != self.key:
             self._build()
@@ -432,7 +448,7 @@ class WeightBatch:
 
     def _build(self):
         dev = self.items[0][0].weight.device
-        groups = sum(1 if m == 0 else (m + 2) ** 2 * (2 if dg else 1) for _, m, dg in self.items)
+        groups = sum(1 if m == 0 else (m + 2) ** 2 * (2 if dg and not c.wino_dx else 1) for c, m, dg in self.items)
         self.slots = torch.empty(groups * ops.AMAX_SUB, device=dev)
         self.views, prep, pack, at = [], [], [], 0
 
@@ -451,6 +467,13 @@ class WeightBatch:
                                  T=c.k * c.k, **dims))
             else:
                 x = (m + 2) ** 2
+                if dg and c.wino_dx:
+                    # the data gradient reads the forward sets transposed: both images from the one transform, one maximum per set
+                    af = take(x)
+                    self.views += [(c, 'uf_amax', af), (c, 'ud_amax', af)]
+                    prep.append(dict(src=c.weight.data, dst_f=c.pf, amax_f=af, T=9, m=m, **dims))
+                    pack.append(dict(src=c.pf, dst_f=c.uf, dst_d=c.ud, amax_f=af, T=1, sets=x, **dims))
+                    continue
                 af, ad = take(x), take(x) if dg else None
                 self.views += [(c, 'uf_amax', af), (c, 'ud_amax', ad)]
                 prep.append(dict(src=c.weight.data, dst_f=c.pf, dst_d=c.pd if dg else None, amax_f=af, amax_d=ad, T=9, m=m, **dims))
@@ -795,19 +818,21 @@ def join_side_stream():
             main.wait_stream(side)
 
 
-def _wgrad(conv, xd, dy, saved_v, x_amax=None, dy_amax=None, x_bnl=None, route=None):
+def _wgrad(conv, xd, dy, saved_v, x_amax=None, dy_amax=None, x_bnl=None, route=None, dm=None):
     """weight gradient of a dense convolution into conv.weight.grad (fp32 atomics) on the kernel conv.wgrad_route names: Winograd-domain,
     1x1 / 3x3 K-quad or generic; in the split modes the 1x1 and Winograd-domain products use the fp32-faithful split on the bf16 / fp16
     matrix cores.  saved_v: (transformed input, its amax slot group) kept from the forward pass; x_amax / dy_amax: slot groups when the
     caller has them (f16x3); x_bnl: xd is the pre-normalisation tensor the forward GEMM normalised as it loaded it
-    (conv_bn_act(defer='amax') -> conv3), coef [C, 4] its record; route: conv.wgrad_route's answer where the caller has asked already"""
+    (conv_bn_act(defer='amax') -> conv3), coef [C, 4] its record; route: conv.wgrad_route's answer where the caller has asked already;
+    dm: (dM, dm_amax) the data gradient of a wino_dx layer made on the main stream (route 'wino_f16x3'): no pfst_wino_dy here"""
     if route is None:
         route = conv.wgrad_route(xd.shape[2], xd.shape[3], xd, dy, lazy=x_bnl is not None)
     if route.startswith('wino'):
         v, v_amax = saved_v if saved_v is not None else (None, None)
         f16w = route == 'wino_f16x3'
         ops.wino_wgrad_(conv.weight.grad, xd, dy, conv.dilation, v=v, split=2 if f16w else _split_mode(), v_amax=v_amax if f16w else None,
-                        x_amax=x_amax if f16w else None, dy_amax=dy_amax if f16w else None)
+                        x_amax=x_amax if f16w else None, dy_amax=dy_amax if f16w else None,
+                        dm=dm[0] if (f16w and dm is not None) else None, dm_amax=dm[1] if (f16w and dm is not None) else None)
     elif route in WGRAD_READS_AMAX:
         assert x_bnl is None or x_amax is not None
         x_amax = x_amax if x_amax is not None else ops.absmax(xd)
@@ -822,7 +847,7 @@ def _wgrad(conv, xd, dy, saved_v, x_amax=None, dy_amax=None, x_bnl=None, route=N
         ops.conv_wgrad_(conv.weight.grad, xd, dy, conv.k, conv.stride, conv.dilation, conv.padding)
 
 
-def _dgrad_into(x, conv, dy, final, dy_amax=None):
+def _dgrad_into(x, conv, dy, final, dy_amax=None, dm=None):
     """data gradient of `conv` into x's gradient buffer; when this launch completes the gradient of a conv -> BN layer's output
     (final) and runs on the K-quad kernel, it also emits that layer's BatchNorm-backward sums (x.bn.partials)"""
     fuse = final and x.bn is not None and x.parent is None and conv.can_fuse_bn_backward() and (not conv.wino or x.bn.y is None)
@@ -830,7 +855,7 @@ def _dgrad_into(x, conv, dy, final, dy_amax=None):
     if x.pending is not None and x.grad_unwritten() and conv.dgrad_can_gate(x.data.shape[-2:]):       # (a pending gate implies a materialised x)
         gate = x.take_pending()           # the identity branch's gated gradient rides in this launch's epilogue (else grad_target writes it out)
     buf, acc = x.grad_target(final=fuse)
-    conv.dgrad(dy, buf.shape[-2:], buf, acc, bn=x.bn if fuse else None, dy_amax=dy_amax, gate=gate)
+    conv.dgrad(dy, buf.shape[-2:], buf, acc, bn=x.bn if fuse else None, dy_amax=dy_amax, gate=gate, dm=dm)
 
 
 def conv_backward(x, conv, dy, saved_v=None, final=False, dy_amax=None, dw_bnb=None):
@@ -854,20 +879,24 @@ def conv_backward(x, conv, dy, saved_v=None, final=False, dy_amax=None, dw_bnb=N
         # the maxima its kernel scales by, on this stream in front of the launches (a transform kept from the forward pass stands in for x)
         x_amax = amax_of(x) if saved_v is None else None
         dy_amax = dy_amax if dy_amax is not None else ops.absmax(dy)
+    dm = None
+    if conv.wino and conv.wino_dx and x.requires_grad:
+        # ONE transform of dy, on this stream, for both gradients: the weight gradient (queued below, i.e. behind it) and the data gradient
+        dm = ops.wino_dy(dy, conv.dilation, dy_amax)
 
     def wg():
-        _wgrad(conv, xd, dy, saved_v, x_amax, dy_amax, wg_bnl, route)
+        _wgrad(conv, xd, dy, saved_v, x_amax, dy_amax, wg_bnl, route, dm)
     if WGRAD_STREAM:
         # (every tensor the side stream reads is recorded on it: the host drops its references when this closure returns, long before the
         # queued launch runs -- the coefficient rows of a normalise-on-load input included)
         _on_side_stream(wg, dy, xd, None if saved_v is None else saved_v[0], wg_bnl, x_amax, dy_amax,
-                        None if saved_v is None else saved_v[1])          # (the slot groups are views of an arena block that is replaced every ~10 steps)
+                        None if saved_v is None else saved_v[1], *(dm or ()))          # (the slot groups are views of an arena block that is replaced every ~10 steps)
     else:
         wg()
     if conv.bias is not None:
         ops.bias_grad_(conv.bias.grad, dy)
     if x.requires_grad:
-        _dgrad_into(x, conv, dy, final, dy_amax)
+        _dgrad_into(x, conv, dy, final, dy_amax, dm)
 
 
 _identity_rows = {}
