@@ -386,6 +386,41 @@ int pfst_topdown_merge_route(const float* lat, long long lat_bs, const float* co
                              int Hc, int Wc, int Hf, int Wf);
 int pfst_fpn_resize_concat_route(const float* y, long long y_bs, int Hf, int Wf);
 int pfst_fpn_resize_concat_bwd_route(const float* dy_plane, long long dy_bs, const float* d_src, long long src_bs, int Hc, int Wc, int Hf, int Wf);
+/* ---- Semantic FPN (csrc/fpn.hip): the FPN neck's nearest top-down path (necks/fpn.py) and FPNHead's level sum
+ * (decode_heads/fpn_head.py).  The conventions above hold: dense planes with batch strides, no atomics, one summation order.
+ * out[n][c][y][x] = lat[n][c][y][x] + coarse[n][c][sy(y)][sx(x)] with torch's legacy 'nearest' rule for a given output size,
+ * s(dst) = min((int)floorf(dst * scale), in - 1), scale = (float)in / (float)out in fp32: ONE rounded fp32 add, the bits of
+ * lat + F.interpolate(coarse, size, mode='nearest').  out is a buffer of its own; Hf >= Hc, Wf >= Wc.  y_amax: NULL, or the slot group that
+ * receives max |out|.  Adjoint: d_lat = d_out, d_coarse (+)= pfst_nearest_resize_bwd(d_out). */
+int pfst_topdown_merge_nearest(const float* lat, long long lat_bs, const float* coarse, long long coarse_bs, float* out, long long out_bs, int N,
+                               int C, int Hc, int Wc, int Hf, int Wf, float* y_amax, pfst_stream_t stream);
+/* the adjoint of that resize as a gather: dx[s] = (accumulate ? dx[s] : 0) + the plain fp32 sum of dy over the pre-image of s -- a contiguous row
+ * range times a contiguous column range (the rule is monotone), its ends found with the forward's own expression; rows ascending, columns
+ * ascending within a row */
+int pfst_nearest_resize_bwd(const float* dy, long long dy_bs, float* dx, long long dx_bs, int N, int C, int Hc, int Wc, int Hf, int Wf,
+                            int accumulate, pfst_stream_t stream);
+/* out = bilinear_x2(act(pre)) on Hc x Wc -> 2 Hc x 2 Wc, act(v) = max(fma(v, sc, sh), 0) with (sc, sh) = coef[c][2], coef[c][3] of a [C, 4] table
+ * (mean, invstd, sc, sh) -- the record a deferred conv -> BN -> ReLU layer leaves; coef NULL: the values are final.  Bit-identical to pfst_bn_apply
+ * followed by pfst_resize_bilinear.  y_amax: NULL, or the slot group that receives max |out|.  Adjoint: pfst_resize_bilinear_bwd. */
+int pfst_upsample2x_norm(const float* pre, long long pre_bs, const float* coef, float* out, long long out_bs, int N, int C, int Hc, int Wc,
+                         float* y_amax, pfst_stream_t stream);
+/* out = act0(pre0) + bilinear_x2((act1(m1) + act2(m2)) + act3(m3)) [+ addend] on H0 x W0, the K <= PFST_FPN_MAX_LEVELS members on exactly
+ * (H0 / 2, W0 / 2); summed in the order written, so bit-identical to pfst_bn_apply per operand, K - 1 fp32 adds on the half grid,
+ * pfst_resize_bilinear, one add, and one more for the addend.  K = 0: out = act0(pre0) [+ addend], any H0 x W0.  members / member_bs /
+ * member_coef: HOST arrays of K (device pointers, batch strides, tables or NULL); coef0 / addend may be NULL.  y_amax as above.  No adjoint kernel:
+ * d_pre0's upstream is d_out, every member's is ONE pfst_resize_bilinear_bwd(d_out). */
+int pfst_fpn_level_sum(const float* pre0, long long pre0_bs, const float* coef0, const float* const* members, const long long* member_bs,
+                       const float* const* member_coef, int K, const float* addend, long long addend_bs, float* out, long long out_bs, int N, int C,
+                       int H0, int W0, float* y_amax, pfst_stream_t stream);
+/* the form a launch of the four takes.  merge_nearest: 0 one pixel per thread, 1 four pixels with 16-byte accesses, 2 the exact x2 form (a coarse
+ * value feeds a 2 x 2 block); nearest_resize_bwd: 0 the generic gather, 1 x2 on 2 x 2 blocks; upsample2x_norm: 0 the pixel form, 1 the x2 walk;
+ * fpn_level_sum: 0 the pixel form, 1 16-byte accesses (the x2 walk, or for K = 0 a flat pass) */
+int pfst_topdown_merge_nearest_route(const float* lat, long long lat_bs, const float* coarse, long long coarse_bs, const float* out,
+                                     long long out_bs, int Hc, int Wc, int Hf, int Wf);
+int pfst_nearest_resize_bwd_route(const float* dy, long long dy_bs, const float* dx, long long dx_bs, int Hc, int Wc, int Hf, int Wf);
+int pfst_upsample2x_norm_route(const float* pre, long long pre_bs, const float* out, long long out_bs, int Hc, int Wc);
+int pfst_fpn_level_sum_route(const float* pre0, long long pre0_bs, const float* const* members, const long long* member_bs, int K,
+                             const float* addend, long long addend_bs, const float* out, long long out_bs, int H0, int W0);
 /* F.interpolate(mode='nearest') by an integer factor on [NC][h][w] maps and its adjoint (pfgst_loss.py:57-58) */
 int pfst_upsample_nearest(const float* x, float* y, int NC, int h, int w, int factor, pfst_stream_t stream);
 int pfst_upsample_nearest_bwd(const float* dy, float* dx, int NC, int h, int w, int factor, pfst_stream_t stream);

@@ -1176,6 +1176,135 @@ def fpn_resize_concat_bwd_routes(dy, outs, chan_off=None):
             for o, t in zip(chan_off, outs)]
 
 
+# ---------------------------------------------------------------- Semantic FPN: nearest top-down merge, level sum (csrc/fpn.hip)
+MERGE_NEAREST_ROUTES = ('pixel', 'quad', 'double')   # pfst_topdown_merge_nearest_route: one pixel per thread, four with 16-byte accesses, the exact x2 form
+NEAREST_BWD_ROUTES = ('gather', 'double')            # pfst_nearest_resize_bwd_route: the generic gather, x2 on 2 x 2 blocks
+UPSAMPLE2X_ROUTES = ('pixel', 'walk')                # pfst_upsample2x_norm_route
+LEVEL_SUM_ROUTES = ('pixel', 'quad')                 # pfst_fpn_level_sum_route: quad = the x2 walk (K >= 1) or a flat pass (K = 0), 16-byte accesses
+
+
+def nearest_src_index(n_out, n_in):
+    """the source index of every output index under torch's legacy 'nearest' for a given output size, as pfst_topdown_merge_nearest forms it:
+    min((int)floorf(dst * scale), n_in - 1) with scale = (float)n_in / (float)n_out, every step in fp32.  NumPy int64 [n_out], no device."""
+    import numpy as np
+    scale = np.float32(n_in) / np.float32(n_out)
+    src = np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64)
+    return np.minimum(src, n_in - 1)
+
+
+def topdown_merge_nearest(lat, coarse, out=None, amax=None):
+    """out = lat + F.interpolate(coarse, lat.shape[2:], mode='nearest') in one pass, bit for bit (one rounded fp32 add).  Operands as for
+    topdown_merge.  Adjoint: d_lat = d_out, d_coarse (+)= nearest_resize_bwd(d_out)."""
+    n, c, hc, wc, hf, wf = _merge_shapes(lat, coarse)
+    if out is None:
+        out = torch.empty(n, c, hf, wf, device=lat.device)
+    if tuple(out.shape) != tuple(lat.shape):
+        raise ValueError(f'topdown_merge_nearest: out {tuple(out.shape)} for lateral {tuple(lat.shape)}')
+    call('pfst_topdown_merge_nearest', lat.data_ptr(), _bs(lat), coarse.data_ptr(), _bs(coarse), out.data_ptr(), _bs(out), n, c, hc, wc, hf, wf,
+         _p(amax), _stream())
+    return out
+
+
+def topdown_merge_nearest_route(lat, coarse, out):
+    """the form pfst_topdown_merge_nearest takes for these operands, one of MERGE_NEAREST_ROUTES (no launch)"""
+    _, _, hc, wc, hf, wf = _merge_shapes(lat, coarse)
+    return MERGE_NEAREST_ROUTES[lib().pfst_topdown_merge_nearest_route(lat.data_ptr(), _bs(lat), coarse.data_ptr(), _bs(coarse), out.data_ptr(),
+                                                                        _bs(out), hc, wc, hf, wf)]
+
+
+def _nearest_bwd_shapes(dy, in_hw, out):
+    n, c, hf, wf = dy.shape
+    hc, wc = int(in_hw[0]), int(in_hw[1])
+    if not (1 <= hc <= hf and 1 <= wc <= wf):
+        raise ValueError(f'nearest_resize_bwd: a source grid {(hc, wc)} under dy {tuple(dy.shape)} (no finer than it)')
+    if out is not None and tuple(out.shape) != (n, c, hc, wc):
+        raise ValueError(f'nearest_resize_bwd: out {tuple(out.shape)}, expected {(n, c, hc, wc)}')
+    return n, c, hc, wc, hf, wf
+
+
+def nearest_resize_bwd(dy, in_hw, out=None, accumulate=False):
+    """the adjoint of F.interpolate(x [N, C, *in_hw], dy.shape[2:], mode='nearest'): out[s] = (accumulate ? out[s] : 0) + sum of dy over the
+    pre-image of s, a plain fp32 sum in ascending row, then column order (deterministic, no atomics)"""
+    n, c, hc, wc, hf, wf = _nearest_bwd_shapes(dy, in_hw, out)
+    if out is None:
+        if accumulate:
+            raise ValueError('nearest_resize_bwd: accumulate needs out')
+        out = torch.empty(n, c, hc, wc, device=dy.device)
+    call('pfst_nearest_resize_bwd', dy.data_ptr(), _bs(dy), out.data_ptr(), _bs(out), n, c, hc, wc, hf, wf, int(bool(accumulate)), _stream())
+    return out
+
+
+def nearest_resize_bwd_route(dy, out):
+    n, c, hc, wc, hf, wf = _nearest_bwd_shapes(dy, out.shape[2:], out)
+    return NEAREST_BWD_ROUTES[lib().pfst_nearest_resize_bwd_route(dy.data_ptr(), _bs(dy), out.data_ptr(), _bs(out), hc, wc, hf, wf)]
+
+
+def _coef_ptr(coef, c, name):
+    if coef is None:
+        return 0
+    _chk(coef, F32, 2)
+    if tuple(coef.shape) != (c, 4) or not coef.is_contiguous():
+        raise ValueError(f'{name}: a coefficient table is a contiguous [C, 4] tensor (mean, invstd, sc, sh), got {tuple(coef.shape)} for C = {c}')
+    return coef.data_ptr()
+
+
+def upsample2x_norm(pre, coef=None, out=None, amax=None):
+    """out = F.interpolate(relu(pre * sc + sh), scale 2, mode='bilinear', align_corners=False) with (sc, sh) = coef[:, 2], coef[:, 3] (the lazy
+    record of conv_bn_act; None: pre holds final values), bit-identical to bn_apply + resize_bilinear.  amax: the slot group that receives
+    max |out|.  Adjoint: resize_bilinear_bwd."""
+    n, c, hc, wc = pre.shape
+    if out is None:
+        out = torch.empty(n, c, 2 * hc, 2 * wc, device=pre.device)
+    if tuple(out.shape) != (n, c, 2 * hc, 2 * wc):
+        raise ValueError(f'upsample2x_norm: out {tuple(out.shape)} for a source {tuple(pre.shape)}')
+    call('pfst_upsample2x_norm', pre.data_ptr(), _bs(pre), _coef_ptr(coef, c, 'upsample2x_norm'), out.data_ptr(), _bs(out), n, c, hc, wc, _p(amax),
+         _stream())
+    return out
+
+
+def upsample2x_norm_route(pre, out):
+    return UPSAMPLE2X_ROUTES[lib().pfst_upsample2x_norm_route(pre.data_ptr(), _bs(pre), out.data_ptr(), _bs(out), pre.shape[2], pre.shape[3])]
+
+
+def _level_sum_args(pre0, members, coefs, addend, out):
+    n, c, h0, w0 = pre0.shape
+    k = len(members)
+    if k > FPN_MAX_LEVELS:
+        raise NotImplementedError(f'fpn_level_sum: up to {FPN_MAX_LEVELS} half-grid members per launch, got {k}')
+    coefs = [None] * k if coefs is None else list(coefs)
+    if len(coefs) != k:
+        raise ValueError(f'fpn_level_sum: {len(coefs)} tables for {k} members')
+    for m in members:
+        if m.dim() != 4 or tuple(m.shape) != (n, c, h0 // 2, w0 // 2) or h0 % 2 or w0 % 2:
+            raise ValueError(f'fpn_level_sum: member {tuple(m.shape)} is not on exactly half of level 0 {tuple(pre0.shape)}')
+    for t, what in ((addend, 'addend'), (out, 'out')):
+        if t is not None and tuple(t.shape) != tuple(pre0.shape):
+            raise ValueError(f'fpn_level_sum: {what} {tuple(t.shape)} for level 0 {tuple(pre0.shape)}')
+    return n, c, h0, w0, k, coefs
+
+
+def fpn_level_sum(pre0, coef0, members=(), coefs=None, addend=None, out=None, amax=None):
+    """out = act0(pre0) + resize_x2((act1(members[0]) + act2(members[1])) + act3(members[2])) [+ addend] in ONE launch, summed in that order:
+    bit-identical to bn_apply per operand, the fp32 adds on the half grid, resize_bilinear, one add, one more for the addend.  act_k normalises
+    on load from the [C, 4] table coef0 / coefs[k] (None: final values).  members: 0 to 3 maps on exactly half of pre0's grid.  amax: the slot
+    group that receives max |out|."""
+    members = list(members)
+    n, c, h0, w0, k, coefs = _level_sum_args(pre0, members, coefs, addend, out)
+    if out is None:
+        out = torch.empty(n, c, h0, w0, device=pre0.device)
+    call('pfst_fpn_level_sum', pre0.data_ptr(), _bs(pre0), _coef_ptr(coef0, c, 'fpn_level_sum'), _ptr_array(members),
+         _i64s([_bs(m) for m in members]), (ctypes.c_void_p * k)(*[_coef_ptr(t, c, 'fpn_level_sum') for t in coefs]), k, _p(addend),
+         0 if addend is None else _bs(addend), out.data_ptr(), _bs(out), n, c, h0, w0, _p(amax), _stream())
+    return out
+
+
+def fpn_level_sum_route(pre0, members, addend, out):
+    members = list(members)
+    n, c, h0, w0, k, _ = _level_sum_args(pre0, members, None, addend, out)
+    return LEVEL_SUM_ROUTES[lib().pfst_fpn_level_sum_route(pre0.data_ptr(), _bs(pre0), _ptr_array(members), _i64s([_bs(m) for m in members]), k,
+                                                           _p(addend), 0 if addend is None else _bs(addend), out.data_ptr(), _bs(out), h0, w0)]
+
+
 def upsample_nearest(x, factor):
     _dense(x)
     n, c, h, w = x.shape

@@ -317,7 +317,9 @@ class Conv2dP(nn.Module):
         if self.depthwise:
             return ConvPlan()
         f16, split = CONV_MATH == 'f16x3', _split_mode()
-        wino = self._wino_eligible()
+        # a biased layer (the FPN neck's bare 3x3 convolutions) stays off the Winograd route in EVERY direction: the transform-domain forward
+        # takes no bias, and a direct forward leaves no transform behind for the Winograd-domain weight gradient (open item)
+        wino = self._wino_eligible() and self.bias is None
         # (the transform-domain GEMMs have no 64-row tile: more than 64 rows in both directions)
         wino_f16 = (wino and f16 and ops.f16x3_eligible(self.cin, self.cout) and self.cout > 64
                     and (not need_dgrad or (ops.f16x3_eligible(self.cout, self.cin) and self.cin > 64)))

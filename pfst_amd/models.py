@@ -17,8 +17,8 @@ from . import layers as layers_mod
 from .engine import Var
 from .layers import (BatchNorm2dP, Conv2dP, ConvModule, DepthwiseSeparableConvModule, WeightBatch, bn_eval, conv_bn_act,
                      conv_forward, dwsep_branches)
-from .registry import (BACKBONES, HEADS, LOSSES, PIXEL_SAMPLERS, SEGMENTORS, add_prefix, build_backbone, build_head, build_loss,
-                       build_pixel_sampler)
+from .registry import (BACKBONES, HEADS, LOSSES, NECKS, PIXEL_SAMPLERS, SEGMENTORS, add_prefix, build_backbone, build_head, build_loss,
+                       build_neck, build_pixel_sampler)
 
 
 # False: the decode head's Dropout2d as a scaling pass of its own (the fold on / off test); default: folded into sep_bottleneck[1]'s normalisation
@@ -893,6 +893,213 @@ class UPerHead(BaseDecodeHead):
         return (logits, feats) if return_features else logits
 
 
+class NeckConvModule(nn.Module):
+    """mmcv's ConvModule as the FPN neck builds it: `conv` with a bias and nothing else when norm_cfg is None (the default), conv (no bias) ->
+    `bn` [-> ReLU] with norm_cfg=dict(type='BN').  The state-dict keys are the reference's (`conv.weight`, `conv.bias` / `bn.*`)."""
+
+    def __init__(self, cin, cout, k, padding=0, norm=False, act=False):
+        super().__init__()
+        if act and not norm:
+            raise NotImplementedError('FPN: act_cfg without norm_cfg (a bare convolution followed by a ReLU) is outside the PFST path')
+        self.conv = Conv2dP(cin, cout, k, 1, padding, bias=not norm)
+        self.bn = BatchNorm2dP(cout) if norm else None
+        self.act = bool(act)
+        nn.init.xavier_uniform_(self.conv.weight)          # init_cfg=dict(type='Xavier', layer='Conv2d', distribution='uniform'); the bias stays 0
+
+    def forward(self, x, tape):
+        if self.bn is None:
+            return conv_forward(x, self.conv, tape)
+        return conv_bn_act(x, self.conv, self.bn, tape, relu=self.act)
+
+
+@NECKS.register_module()
+class FPN(nn.Module):
+    """necks/fpn.py: a 1x1 lateral per backbone level, the top-down path merged[i - 1] = lateral[i - 1] + resize(merged[i] -> grid of i - 1) from
+    the top, a 3x3 fpn_conv per merged level.  The top-down resize is 'nearest' by default as in the reference (torch's legacy rule for a given
+    output size; csrc/fpn.hip pfst_topdown_merge_nearest, one pass per merge that also publishes max |.| of the merged map) or 'bilinear'
+    (ops.topdown_merge).  Module names and their order are the reference's, so its checkpoints load key for key.  What the shipped config
+    (configs/_base_/models/fpn_r50.py) does not use raises NotImplementedError: extra levels, a level range, scale_factor, conv_cfg.
+    The 3x3 layers carry a bias and therefore run on the direct GEMM, not through the Winograd domain (open item)."""
+
+    def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, add_extra_convs=False, extra_convs_on_inputs=False,
+                 relu_before_extra_convs=False, no_norm_on_lateral=False, conv_cfg=None, norm_cfg=None, act_cfg=None,
+                 upsample_cfg=dict(mode='nearest'), init_cfg=None):
+        super().__init__()
+        if not (isinstance(in_channels, (list, tuple)) and len(in_channels) >= 1 and all(isinstance(c, int) and c > 0 for c in in_channels)):
+            raise TypeError(f'FPN: in_channels is a list of channel counts, one per level, got {in_channels!r}')
+        if add_extra_convs or extra_convs_on_inputs or relu_before_extra_convs:
+            raise NotImplementedError('FPN: add_extra_convs (extra levels) is outside the PFST path')
+        if num_outs != len(in_channels):
+            raise NotImplementedError(f'FPN: num_outs == len(in_channels) (no extra levels), got {num_outs} for {len(in_channels)} levels')
+        if start_level != 0 or end_level != -1:
+            raise NotImplementedError(f'FPN: every backbone level (start_level=0, end_level=-1), got {start_level}, {end_level}')
+        if conv_cfg is not None:
+            raise NotImplementedError('FPN: conv_cfg is outside the PFST path')
+        if norm_cfg is not None:
+            _check_norm(norm_cfg)
+        if act_cfg is not None and act_cfg.get('type') != 'ReLU':
+            raise NotImplementedError(f"FPN: act_cfg None or dict(type='ReLU'), got {act_cfg!r}")
+        up = dict(upsample_cfg)
+        if 'scale_factor' in up or up.get('mode') not in ('nearest', 'bilinear') or up.get('align_corners') or set(up) - {'mode', 'align_corners'}:
+            raise NotImplementedError(f"FPN: upsample_cfg dict(mode='nearest') or dict(mode='bilinear') for the lateral's size, got {upsample_cfg!r}")
+        if len(in_channels) - 1 > ops.FPN_MAX_LEVELS:
+            raise NotImplementedError(f'FPN: up to {ops.FPN_MAX_LEVELS + 1} levels (the merge chain), got {len(in_channels)}')
+        self.in_channels, self.out_channels, self.num_outs = list(in_channels), out_channels, num_outs
+        self.num_ins = len(in_channels)
+        self.no_norm_on_lateral, self.upsample_cfg = bool(no_norm_on_lateral), up
+        norm, act = norm_cfg is not None, act_cfg is not None
+        self.lateral_convs, self.fpn_convs = nn.ModuleList(), nn.ModuleList()
+        for c in in_channels:
+            self.lateral_convs.append(NeckConvModule(c, out_channels, 1, norm=norm and not self.no_norm_on_lateral,
+                                                     act=act and norm and not self.no_norm_on_lateral))
+            self.fpn_convs.append(NeckConvModule(out_channels, out_channels, 3, padding=1, norm=norm, act=act))
+
+    def forward(self, inputs, tape=None):
+        assert len(inputs) == len(self.in_channels)
+        nl = len(inputs)
+        nearest = self.upsample_cfg['mode'] == 'nearest'
+        f16 = layers_mod.CONV_MATH == 'f16x3'
+        lats = [self.lateral_convs[i](inputs[i], tape) for i in range(nl)]
+        # top-down, from the top: merged[i] in a buffer of its own (the lateral layer's backward may read its output).  Recorded before the
+        # fpn_convs, so in backward a merge runs AFTER the fpn_conv of its output level and finds dL/dmerged[i] complete; it hands that buffer to the
+        # lateral as its gradient and adds its adjoint resize to the level above -- the last writer of its coarser operand, hence the claim
+        merged = [None] * (nl - 1) + [lats[-1]]
+        for i in range(nl - 2, -1, -1):
+            lat, coarse = lats[i], merged[i + 1]
+            coarse.claim_first_use()
+            m = Var(None, tape is not None)
+            if f16:
+                m.amax = ops.amax_slots(lat.data.device)          # fpn_convs[i]'s f16x3 scale: published by the merge, no pass of its own
+            m.data = (ops.topdown_merge_nearest if nearest else ops.topdown_merge)(lat.data, coarse.data, amax=m.amax)
+            merged[i] = m
+            if tape is not None:
+                def bwd_merge(m=m, lat=lat, coarse=coarse):
+                    g = m.grad
+                    buf, acc = coarse.grad_target()
+                    (ops.nearest_resize_bwd if nearest else ops.resize_bilinear_bwd)(g, coarse.data.shape[-2:], out=buf, accumulate=acc)
+                    lat._grad = g
+                    m.free_grad()
+                tape.record(bwd_merge, dict(op='fpn_merge', x=coarse, lat=lat, out=m))
+        return [self.fpn_convs[i](merged[i], tape) for i in range(nl)]
+
+
+class Upsample2x(nn.Module):
+    """the parameter-less place of the reference's `Upsample(scale_factor=2, mode='bilinear')` inside FPNHead's scale_heads: it keeps the
+    Sequential's indices (the ConvModules at the even positions), the up-sampling itself is fused into the head's kernels"""
+
+
+@HEADS.register_module()
+class FPNHead(BaseDecodeHead):
+    """decode_heads/fpn_head.py (Semantic FPN): per level head_length x (3x3 conv -> BN -> ReLU [-> x2 bilinear up-sampling]), every level resized to
+    level 0's grid and summed, cls_seg.  `in_channels` / `in_index` are lists: the head selects its levels itself (the reference's
+    'multiple_select'; the `input_transform` argument stays refused like for every head).  Module names are the reference's: scale_heads.{i} is
+    a Sequential with the ConvModules at its even positions.  csrc/fpn.hip: an intermediate conv -> BN -> ReLU -> x2 is
+    never written normalised (pfst_upsample2x_norm normalises on load); level 0's last map and every level whose last convolution lives on
+    exactly half of level 0's grid meet in ONE pfst_fpn_level_sum launch -- up-sampling is linear, so y0 + sum_k up2x(y_k) = y0 + up2x(sum_k y_k)
+    -- and in backward ONE adjoint resize serves all of them.  A level elsewhere takes the composition of the existing ops into an addend the
+    launch adds.  Returns the level sum as the decoded features (pre-dropout, as ASPPHead); Dropout2d stays a pass of its own."""
+
+    def __init__(self, feature_strides, **kwargs):
+        super().__init__(**kwargs)
+        ci, idx = self.in_channels, self.in_index
+        if not (isinstance(ci, (list, tuple)) and isinstance(idx, (list, tuple)) and len(ci) == len(idx) and len(ci) >= 1
+                and all(isinstance(c, int) and c > 0 for c in ci) and all(isinstance(i, int) for i in idx)):
+            raise TypeError(f'FPNHead: in_channels and in_index are lists of equal length (one entry per level), got {ci!r} and {idx!r}')
+        assert len(feature_strides) == len(ci)
+        assert min(feature_strides) == feature_strides[0]
+        self.in_channels, self.in_index, self.feature_strides = list(ci), list(idx), list(feature_strides)
+        self.scale_heads = nn.ModuleList()
+        for i, s in enumerate(feature_strides):
+            head_length = max(1, int(np.log2(s) - np.log2(feature_strides[0])))
+            mods = []
+            for k in range(head_length):
+                mods.append(ConvModule(ci[i] if k == 0 else self.channels, self.channels, 3, padding=1))
+                if s != feature_strides[0]:
+                    mods.append(Upsample2x())
+            self.scale_heads.append(nn.Sequential(*mods))
+
+    def forward(self, inputs, return_features=False, tape=None, training=True):
+        xs = [inputs[i] for i in self.in_index]
+        dev = xs[0].data.device
+        f16 = layers_mod.CONV_MATH == 'f16x3'
+        rec = tape is not None
+        src = lambda v: (v.data, None) if v.lazy is None else (v.lazy[0], v.lazy[1])          # (tensor, table) of a layer's output, written or deferred
+        lasts = []
+        for i, x in enumerate(xs):
+            convs = [m for m in self.scale_heads[i] if isinstance(m, ConvModule)]
+            ups = self.feature_strides[i] != self.feature_strides[0]
+            for k, cm in enumerate(convs):
+                if k == len(convs) - 1:
+                    lasts.append((x, cm, ups))
+                    break
+                # conv -> BN -> ReLU -> x2: the up-sampling normalises the pre-BN tensor as it loads it and publishes max |.| for the next conv
+                y = cm(x, tape, defer=True)
+                up = Var(None, rec)
+                if f16:
+                    up.amax = ops.amax_slots(dev)
+                pre, coef = src(y)
+                up.data = ops.upsample2x_norm(pre, coef, amax=up.amax)
+                if rec:
+                    def bwd_up(y=y, up=up, hw=tuple(pre.shape[-2:])):
+                        y._grad = ops.resize_bilinear_bwd(up.grad, hw)
+                        up.free_grad()
+                    tape.record(bwd_up, dict(op='upsample2x_norm', x=y, out=up))
+                x = up
+        # the last conv -> BN -> ReLU of every level.  Level 0's map and the maps on exactly half of its grid are read by the sum alone (deferred);
+        # any other is written and resized by the existing ops
+        x0, cm0, _ = lasts[0]
+        h0, w0 = (x0.data if x0.lazy is None else x0.lazy[0]).shape[-2:]
+        y0 = cm0(x0, tape, defer=True)
+        members, others = [], []
+        for x, cm, ups in lasts[1:]:
+            h, w = x.data.shape[-2:]
+            fused = ups and (2 * h, 2 * w) == (h0, w0) and len(members) < ops.FPN_MAX_LEVELS
+            y = cm(x, tape, defer=fused)
+            (members if fused else others).append((y, ups))
+        addend = None
+        for y, ups in others:
+            t = y.data
+            if ups:
+                t = ops.resize_bilinear(t, (2 * t.shape[2], 2 * t.shape[3]))
+            if tuple(t.shape[-2:]) != (h0, w0):
+                t = ops.resize_bilinear(t, (h0, w0))
+            if addend is None:
+                addend = t if t is not y.data else t.clone()
+            else:
+                ops.axpy_(addend, t)
+        feats = Var(None, rec)
+        if f16:
+            feats.amax = ops.amax_slots(dev)                  # conv_seg's f16x3 scale: published by the sum
+        pre0, coef0 = src(y0)
+        srcs = [src(y) for y, _ in members]
+        feats.data = ops.fpn_level_sum(pre0, coef0, [s[0] for s in srcs], [s[1] for s in srcs], addend=addend, amax=feats.amax)
+        if rec:
+            def bwd_sum():
+                # dL/dy0 is dL/dout itself; ONE adjoint resize is the gradient of every half-grid member: their BatchNorm backward passes read
+                # the shared buffer (ops.bn_backward writes a dx of its own), each Var only drops its reference; the addend's levels get the
+                # adjoints of their compositions
+                g = feats.grad
+                y0._grad = g
+                if members:
+                    gh = ops.resize_bilinear_bwd(g, (h0 // 2, w0 // 2))
+                    for y, _ in members:
+                        y._grad = gh
+                for y, ups in others:
+                    h, w = y.data.shape[-2:]
+                    t = g
+                    if ups:
+                        if (2 * h, 2 * w) != (h0, w0):
+                            t = ops.resize_bilinear_bwd(t, (2 * h, 2 * w))
+                        t = ops.resize_bilinear_bwd(t, (h, w))
+                    elif (h, w) != (h0, w0):
+                        t = ops.resize_bilinear_bwd(t, (h, w))
+                    y._grad = t
+                feats.free_grad()
+            tape.record(bwd_sum, dict(op='fpn_level_sum', x=y0, members=[y for y, _ in members], others=[y for y, _ in others], out=feats))
+        logits = self.cls_seg(feats, tape, training)
+        return (logits, feats) if return_features else logits
+
+
 @HEADS.register_module()
 class FCNHead(BaseDecodeHead):
     """fcn_head.py: num_convs conv -> BN -> ReLU layers (kernel 1 or 3, any dilation), optionally conv_cat over [x, feats]"""
@@ -940,12 +1147,15 @@ class EncoderDecoder(nn.Module):
     def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None,
                  pretrained=None, init_cfg=None):
         super().__init__()
-        if neck is not None or isinstance(auxiliary_head, (list, tuple)):
-            raise NotImplementedError('neck / multiple auxiliary heads are outside the PFST path')
+        if isinstance(auxiliary_head, (list, tuple)):
+            raise NotImplementedError('multiple auxiliary heads are outside the PFST path')
         if pretrained is not None:
             backbone = dict(backbone)
             backbone['pretrained'] = pretrained
         self.backbone = build_backbone(backbone)
+        # encoder_decoder.py:35-36: the neck is registered between backbone and decode_head -- the order of the state dict and of the parameter
+        # arena, whose 'heads' cut (supervised.py, uda.py) is the first name outside `backbone.`: the neck belongs to the heads' side
+        self.neck = build_neck(neck) if neck is not None else None
         self.decode_head = build_head(decode_head)
         self.auxiliary_head = build_head(auxiliary_head) if auxiliary_head is not None else None
         self.align_corners = self.decode_head.align_corners
@@ -1020,8 +1230,15 @@ class EncoderDecoder(nn.Module):
         self.__dict__['_repack_plan'] = (key, rec) if rec is not None else None
 
     def extract_feat(self, img, tape=None, grad_ready=None):
+        """backbone [-> neck] (encoder_decoder.py:64-69).  With a neck and a `grad_ready` callback the marker 'heads' is recorded HERE, after the
+        backbone's last op and before the neck's first: in backward it fires once every gradient of neck and heads is complete"""
         x = img if isinstance(img, Var) else Var(img, False)
-        return self.backbone(x, tape, grad_ready) if grad_ready is not None else self.backbone(x, tape)
+        x = self.backbone(x, tape, grad_ready) if grad_ready is not None else self.backbone(x, tape)
+        if self.neck is not None:
+            if grad_ready is not None and tape is not None:
+                tape.record(lambda: grad_ready('heads'))
+            x = self.neck(x, tape)
+        return x
 
     def encode_decode(self, img, img_metas=None):
         """teacher-style forward: no tape, dropout off, BN still in train mode; returns the LOW-resolution
@@ -1283,10 +1500,10 @@ class EncoderDecoder(nn.Module):
                       return_decoded_feats=False, return_logits=False, return_states=False, tape=None, grad_scale=1.0,
                       grad_ready=None):
         """gt_semantic_seg: uint8 [N,1,H,W]; returns the losses dict (device tensors) like the reference.
-        grad_ready: see ResNetV1c.forward; the marker `heads` covers both heads"""
+        grad_ready: see ResNetV1c.forward; the marker `heads` covers both heads and the neck"""
         x = self.extract_feat(img, tape, grad_ready)
-        if grad_ready is not None and tape is not None:
-            tape.record(lambda: grad_ready('heads'))
+        if grad_ready is not None and tape is not None and self.neck is None:
+            tape.record(lambda: grad_ready('heads'))          # (with a neck: recorded by extract_feat, in front of the neck)
         losses, states = dict(), dict()
         loss_decode, state = self.decode_head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg, seg_weight,
                                                             tape=tape, grad_scale=grad_scale)

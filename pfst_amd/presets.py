@@ -24,14 +24,15 @@ def model_cfg(num_classes=6, in_channels=3, dropout=0.1):
         train_cfg=dict(), test_cfg=dict(mode='whole'))
 
 
-BASELINE_KINDS = ('pspnet', 'deeplabv3', 'fcn', 'upernet')
+BASELINE_KINDS = ('pspnet', 'deeplabv3', 'fcn', 'upernet', 'fpn')
 
 
 def baseline_model_cfg(kind, num_classes, in_channels, depth=50, dropout=0.1):
     """The comparison models of the reference (configs/_base_/models/pspnet_r50-d8.py, deeplabv3_r50-d8.py, fcn_r50-d8.py): the same
     ResNetV1c-d8 backbone and auxiliary FCN head on layer3 as model_cfg, under a PSPHead, an ASPPHead or a two-layer FCNHead with
     concat_input; 'upernet' (upernet_r50.py) is a UPerHead over all four levels of the stride-32 backbone, strides (1, 2, 2, 2) without
-    dilation, with the same auxiliary head.  Plain BN, as the reference's DeepLabV3+ file; `depth` 50 or 101 (the reference's PSPNet file runs 101).  The class
+    dilation, with the same auxiliary head; 'fpn' (fpn_r50.py, Semantic FPN) is that stride-32 backbone under an FPN neck (256 channels, four
+    levels, nearest top-down path) and an FPNHead (128 channels, feature strides 4 .. 32) -- WITHOUT an auxiliary head, as the reference's file.  Plain BN, as the reference's DeepLabV3+ file; `depth` 50 or 101 (the reference's PSPNet file runs 101).  The class
     weights of the reference's two-class PSPNet edit are a property of its data set: add `class_weight` to the loss dicts where wanted."""
     if kind not in BASELINE_KINDS:
         raise ValueError(f'baseline_model_cfg: kind must be one of {BASELINE_KINDS}, got {kind!r}')
@@ -40,12 +41,21 @@ def baseline_model_cfg(kind, num_classes, in_channels, depth=50, dropout=0.1):
     common = dict(in_channels=2048, in_index=3, channels=512, dropout_ratio=dropout, num_classes=num_classes, norm_cfg=dict(NORM_CFG),
                   align_corners=False, loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0))
     head = dict(pspnet=dict(type='PSPHead', pool_scales=(1, 2, 3, 6)), deeplabv3=dict(type='ASPPHead', dilations=(1, 12, 24, 36)),
-                fcn=dict(type='FCNHead', num_convs=2, concat_input=True), upernet=dict(type='UPerHead', pool_scales=(1, 2, 3, 6)))[kind]
+                fcn=dict(type='FCNHead', num_convs=2, concat_input=True), upernet=dict(type='UPerHead', pool_scales=(1, 2, 3, 6)),
+                fpn=dict(type='FPNHead'))[kind]
     cfg['decode_head'] = dict(head, **common)
     if kind == 'upernet':
         # configs/_base_/models/upernet_r50.py: the stride-32 backbone (no dilation) under a head that reads all four levels
         cfg['backbone'].update(strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1))
         cfg['decode_head'].update(in_channels=[256, 512, 1024, 2048], in_index=[0, 1, 2, 3])
+    if kind == 'fpn':
+        # configs/_base_/models/fpn_r50.py: the same stride-32 backbone, an FPN neck, FPNHead over its four outputs, no auxiliary head
+        cfg['backbone'].update(strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1))
+        cfg['neck'] = dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=4)
+        cfg['decode_head'] = dict(type='FPNHead', in_channels=[256, 256, 256, 256], in_index=[0, 1, 2, 3], feature_strides=[4, 8, 16, 32],
+                                  channels=128, dropout_ratio=dropout, num_classes=num_classes, norm_cfg=dict(NORM_CFG), align_corners=False,
+                                  loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0))
+        del cfg['auxiliary_head']
     return cfg
 
 

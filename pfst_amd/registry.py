@@ -64,6 +64,11 @@ def build_backbone(cfg):
     return BACKBONES.build(cfg)
 
 
+def build_neck(cfg):
+    """rsiseg/models/builder.py: the neck of an EncoderDecoder (FPN)"""
+    return NECKS.build(cfg)
+
+
 def build_head(cfg):
     return HEADS.build(cfg)
 

@@ -114,6 +114,9 @@ def feature_dilation(cfg, feature, dilation, downscale):
         level = int(level[0])
     level = level % len(tuple(backbone.get('out_indices', (0, 1, 2, 3))))
     fs = _feature_stride(backbone, level)
+    if feature == 'decoded' and model.get('neck') is not None and 'feature_strides' in model['decode_head']:
+        # behind a neck (Semantic FPN) level i is still backbone level i's grid; the head decodes on the grid of its first feature stride
+        fs = int(model['decode_head']['feature_strides'][0])
     if fs % loss_stride != 0:
         raise NotImplementedError(f'feature {feature!r} (stride {fs}) is finer than the loss grid (stride {loss_stride})')
     u = fs // loss_stride

@@ -5,7 +5,7 @@ device ops in the same process (four adaptive_avg_pool2d; four interpolate + cat
 timed region), (b) the resize halves through the library's generic pfst_resize_bilinear / _bwd, one launch per scale, and (c) the bytes each
 launch must move at the measured copy rate.  Variants alternate inside every round; per variant the median, minimum and maximum over the
 rounds of the mean of --inner back-to-back runs between two device events.  Then a supervised step (EncoderDecoder.train_step under SGD) of
-the comparison models (--models, default all: pspnet, deeplabv3, fcn, upernet) and the flagship at 8 x 1024^2, alternating blocks, host clock
+the comparison models (--models, default all: pspnet, deeplabv3, fcn, upernet, fpn) and the flagship at 8 x 1024^2, alternating blocks, host clock
 between device synchronisations, with the peak device allocation of each.  One JSON line (and --out FILE).
 
 The feature-pyramid kernels of UPerHead (csrc/fpn.hip) at its grids for that tile -- 512 channels, 256^2 / 128^2 / 64^2 /
@@ -13,8 +13,12 @@ The feature-pyramid kernels of UPerHead (csrc/fpn.hip) at its gr
 temporary + axpy_ + absmax, fpn_resize_concat against one resize_bilinear(out=slice) per level + absmax of the slices,
 fpn_resize_concat_bwd against one resize_bilinear_bwd per level; achieved bytes per second from the bytes the shapes say must move.
 
+The Semantic FPN kernels (csrc/fpn.hip) at the grids of that tile -- the neck's nearest merges at 256 channels, the head's
+upsample2x_norm and fpn_level_sum at 128 -- each beside the composition of library ops it replaces: upsample_nearest + axpy_ + absmax;
+bn_apply + resize_bilinear + absmax; bn_apply x 4 + three resize_bilinear + three axpy_ + absmax; one adjoint resize against three.
+
   python tools/heads_bench.py [--tiles 8] [--grid 128] [--rounds 7] [--inner 5] [--steps 12] [--models a,b] [--no-step] [--no-ops] [--no-fpn]
-                              [--out FILE]"""
+                              [--no-sfpn] [--out FILE]"""
 import argparse
 import json
 import os
@@ -167,6 +171,85 @@ def fpn_bench(args):
     return res
 
 
+def sfpn_bench(args):
+    import torch
+    from pfst_amd import hip_ops as ops
+    N, CN, CH, G0 = args.tiles, 256, 128, args.size // 4
+    grids = [G0 >> i for i in range(4)]
+    torch.manual_seed(0)
+    res = dict(tiles=N, neck_channels=CN, head_channels=CH, grids=grids, rounds=args.rounds, inner=args.inner)
+
+    def rate(r, ours, others, moved):
+        verdict(r, ours, others, moved)
+        r['achieved_TB_s'] = round(moved / (r[ours]['median_ms'] * 1e-3) / 1e12, 3)
+        return r
+
+    def table(c):            # (mean, invstd, sc, sh) rows as bn_apply forms them from (0, 1, gamma, beta)
+        gamma, beta = torch.rand(c, device='cuda') + 0.5, torch.randn(c, device='cuda') * 0.2
+        return torch.stack([torch.zeros_like(gamma), torch.ones_like(gamma), gamma, beta], 1).contiguous()
+
+    def norm(x, t, out=None):
+        return ops.bn_apply(x, t[:, 0].contiguous(), t[:, 1].contiguous(), t[:, 2].contiguous(), t[:, 3].contiguous(), True, out=out)
+    # ---- the neck's three nearest merges (exact x2 at these grids), max |out| published
+    for i in (2, 1, 0):
+        hf, hc = grids[i], grids[i + 1]
+        lat = torch.randn(N, CN, hf, hf, device='cuda')
+        coarse = torch.randn(N, CN, hc, hc, device='cuda')
+        out = torch.empty_like(lat)
+        slots = ops.amax_slots(lat.device, 2)
+
+        def composed():
+            tmp = ops.upsample_nearest(coarse, 2)
+            ops.axpy_(tmp, lat)
+            ops.absmax(tmp, out=slots[:ops.AMAX_SUB])
+        res[f'merge_nearest_{hc}_to_{hf}'] = rate(alternate(dict(fused=lambda: ops.topdown_merge_nearest(lat, coarse, out=out, amax=slots[ops.AMAX_SUB:]),
+                                                                 composed=composed), args.rounds, args.inner),
+                                                  'fused', ['composed'], 4 * N * CN * (2 * hf * hf + hc * hc))
+        dc = torch.empty_like(coarse)
+        res[f'nearest_bwd_{hf}_to_{hc}'] = rate(alternate(dict(fused=lambda: ops.nearest_resize_bwd(lat, (hc, hc), out=dc),
+                                                               composed=lambda: ops.upsample_nearest_bwd(lat, 2)), args.rounds, args.inner),
+                                                'fused', ['composed'], 4 * N * CN * (hf * hf + hc * hc))
+        del lat, coarse, out, dc
+    # ---- conv -> BN -> ReLU -> x2 of the head's deeper levels: the pre-BN tensor normalised on load
+    for hc in (grids[3], grids[2]):
+        pre, t = torch.randn(N, CH, hc, hc, device='cuda'), table(CH)
+        out, tmp = torch.empty(N, CH, 2 * hc, 2 * hc, device='cuda'), torch.empty(N, CH, hc, hc, device='cuda')
+        slots = ops.amax_slots(pre.device, 2)
+
+        def composed():
+            norm(pre, t, out=tmp)
+            ops.resize_bilinear(tmp, (2 * hc, 2 * hc), out=out)
+            ops.absmax(out, out=slots[:ops.AMAX_SUB])
+        res[f'upsample2x_norm_{hc}'] = rate(alternate(dict(fused=lambda: ops.upsample2x_norm(pre, t, out=out, amax=slots[ops.AMAX_SUB:]),
+                                                           composed=composed), args.rounds, args.inner),
+                                            'fused', ['composed'], 4 * N * CH * 5 * hc * hc)
+        del pre, out, tmp
+    # ---- the level sum: level 0's last map and three maps on half of its grid
+    h0, hh = grids[0], grids[1]
+    pre0, members = torch.randn(N, CH, h0, h0, device='cuda'), [torch.randn(N, CH, hh, hh, device='cuda') for _ in range(3)]
+    tabs = [table(CH) for _ in range(4)]
+    out, acc, full, half = torch.empty_like(pre0), torch.empty_like(pre0), torch.empty_like(pre0), torch.empty_like(members[0])
+    slots = ops.amax_slots(pre0.device, 2)
+
+    def composed_sum():
+        norm(pre0, tabs[0], out=acc)
+        for m, t in zip(members, tabs[1:]):
+            norm(m, t, out=half)
+            ops.resize_bilinear(half, (h0, h0), out=full)
+            ops.axpy_(acc, full)
+        ops.absmax(acc, out=slots[:ops.AMAX_SUB])
+    res['level_sum'] = rate(alternate(dict(fused=lambda: ops.fpn_level_sum(pre0, tabs[0], members, tabs[1:], out=out, amax=slots[ops.AMAX_SUB:]),
+                                           composed=composed_sum), args.rounds, args.inner),
+                            'fused', ['composed'], 4 * N * CH * (2 * h0 * h0 + 3 * hh * hh))
+    # ---- its backward: one adjoint resize serves the three half-grid members
+    g = torch.randn(N, CH, h0, h0, device='cuda')
+    ds = [torch.empty_like(m) for m in members]
+    res['level_sum_bwd'] = rate(alternate(dict(fused=lambda: ops.resize_bilinear_bwd(g, (hh, hh), out=ds[0]),
+                                               composed=lambda: [ops.resize_bilinear_bwd(g, (hh, hh), out=d) for d in ds]), args.rounds, args.inner),
+                                'fused', ['composed'], 4 * N * CH * (h0 * h0 + hh * hh))
+    return res
+
+
 def step_bench(args):
     import torch
     from pfst_amd.optim import build_optimizer
@@ -176,7 +259,7 @@ def step_bench(args):
     batch = synth_batch(args.tiles, args.size, 6, 3, seed=1234, device='cuda')
     batch = {k: v for k, v in batch.items() if not k.startswith('target_')}
     cfgs = dict(deeplabv3plus=model_cfg(6, 3), pspnet=baseline_model_cfg('pspnet', 6, 3), deeplabv3=baseline_model_cfg('deeplabv3', 6, 3),
-                fcn=baseline_model_cfg('fcn', 6, 3), upernet=baseline_model_cfg('upernet', 6, 3))
+                fcn=baseline_model_cfg('fcn', 6, 3), upernet=baseline_model_cfg('upernet', 6, 3), fpn=baseline_model_cfg('fpn', 6, 3))
     if args.models:
         cfgs = {k: cfgs[k] for k in args.models.split(',')}
     times = {k: [] for k in cfgs}
@@ -216,10 +299,11 @@ def main(argv=None):
     p.add_argument('--rounds', type=int, default=7)
     p.add_argument('--inner', type=int, default=5)
     p.add_argument('--steps', type=int, default=12, help='timed supervised steps per model')
-    p.add_argument('--models', default=None, help='comma-separated kinds of the supervised-step part (deeplabv3plus,pspnet,deeplabv3,fcn,upernet); default all')
+    p.add_argument('--models', default=None, help='comma-separated kinds of the supervised-step part (deeplabv3plus,pspnet,deeplabv3,fcn,upernet,fpn); default all')
     p.add_argument('--no-step', action='store_true')
     p.add_argument('--no-fpn', action='store_true')
     p.add_argument('--no-ops', action='store_true')
+    p.add_argument('--no-sfpn', action='store_true')
     p.add_argument('--out', default=None)
     args = p.parse_args(argv)
     import torch
@@ -230,6 +314,9 @@ def main(argv=None):
         torch.cuda.empty_cache()
     if not args.no_fpn:
         res['fpn'] = fpn_bench(args)
+        torch.cuda.empty_cache()
+    if not args.no_sfpn:
+        res['semantic_fpn'] = sfpn_bench(args)
         torch.cuda.empty_cache()
     if not args.no_step:
         res['supervised_step'] = step_bench(args)
