@@ -421,6 +421,28 @@ int pfst_nearest_resize_bwd_route(const float* dy, long long dy_bs, const float*
 int pfst_upsample2x_norm_route(const float* pre, long long pre_bs, const float* out, long long out_bs, int Hc, int Wc);
 int pfst_fpn_level_sum_route(const float* pre0, long long pre0_bs, const float* const* members, const long long* member_bs, int K,
                              const float* addend, long long addend_bs, const float* out, long long out_bs, int H0, int W0);
+/* ---- HRNet's exchange unit (csrc/hrnet.hip): the sum that ends every HRModule (backbones/hrnet.py:199-213).  The
+ * conventions above hold: bilinear, align_corners=False, dense planes with batch strides, no atomics, one summation order.
+ * out[n][c] = max(((t_0 + t_1) + t_2) + t_3, 0) over B <= PFST_HR_MAX_BRANCHES operands in the order given, one rounded fp32 add each.  ops /
+ * op_bs / op_coef / op_h / op_w: HOST arrays of B (device pointer, batch stride, [C, 4] table (mean, invstd, sc, sh) or NULL, grid).  An operand
+ * on the output grid contributes fma(v, sc, sh) (no ReLU), or v itself under a NULL table; an operand on exactly (Hf / r, Wf / r), r in {2, 4, 8}
+ * -- at most PFST_FPN_MAX_LEVELS of them -- contributes the bilinear interpolation of its normalised values.  Bit-identical to pfst_bn_apply
+ * (relu = 0) per tabled operand, pfst_resize_bilinear per coarser one, the adds in that order and a ReLU.  out is a buffer of its own.  y_amax:
+ * NULL, or the slot group that receives max |out|. */
+#define PFST_HR_MAX_BRANCHES 4
+int pfst_hr_fuse(const float* const* ops, const long long* op_bs, const float* const* op_coef, const int* op_h, const int* op_w, int B, float* out,
+                 long long out_bs, int N, int C, int Hf, int Wf, float* y_amax, pfst_stream_t stream);
+/* its adjoint in at most two launches: gy = (out > 0 ? d_out : 0), the upstream gradient of EVERY output-grid operand (gy may be d_out itself),
+ * then d_coarse[k] = (accumulate[k] ? d_coarse[k] : 0) + resize^T(gy) for the K <= PFST_FPN_MAX_LEVELS coarser operands in one gather launch, each
+ * bit-identical to pfst_resize_bilinear_bwd(gy).  d_coarse / coarse_bs / coarse_h / coarse_w / accumulate: HOST arrays of K (unread for K = 0).  The
+ * tabled operands' BatchNorm backward is pfst_bn_backward from their pre-normalisation tensors. */
+int pfst_hr_fuse_bwd(const float* d_out, long long d_out_bs, const float* out, long long out_bs, float* gy, long long gy_bs, float* const* d_coarse,
+                     const long long* coarse_bs, const int* coarse_h, const int* coarse_w, const int* accumulate, int K, int N, int C, int Hf,
+                     int Wf, pfst_stream_t stream);
+/* the form a pfst_hr_fuse launch takes: 0 one pixel per thread, 1 four pixels with 16-byte accesses (Wf % 4 == 0; out and every output-grid operand
+ * 16-byte aligned with a batch stride % 4 == 0) */
+int pfst_hr_fuse_route(const float* const* ops, const long long* op_bs, const int* op_h, const int* op_w, int B, const float* out, long long out_bs,
+                       int Hf, int Wf);
 /* F.interpolate(mode='nearest') by an integer factor on [NC][h][w] maps and its adjoint (pfgst_loss.py:57-58) */
 int pfst_upsample_nearest(const float* x, float* y, int NC, int h, int w, int factor, pfst_stream_t stream);
 int pfst_upsample_nearest_bwd(const float* dy, float* dx, int NC, int h, int w, int factor, pfst_stream_t stream);

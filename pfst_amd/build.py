@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libpfst_hip.so')
-SOURCES = ['conv_mfma.hip', 'conv_igemm_q.hip', 'conv_wgrad_q.hip', 'conv_winograd.hip', 'conv_split.hip', 'conv_f16x3.hip', 'adv_conv.hip', 'adv_tail.hip', 'dwconv.hip', 'bn.hip', 'spatial.hip', 'pyramid.hip', 'fpn.hip', 'scene.hip', 'scene_tta.hip', 'loss.hip', 'dice_loss.hip', 'sigmoid_loss.hip', 'lovasz_loss.hip', 'entropy_labels.hip', 'entropy_loss.hip', 'ohem.hip', 'pfgst_loss.hip', 'optim.hip', 'strong_aug.hip', 'api.cpp']
+SOURCES = ['conv_mfma.hip', 'conv_igemm_q.hip', 'conv_wgrad_q.hip', 'conv_winograd.hip', 'conv_split.hip', 'conv_f16x3.hip', 'adv_conv.hip', 'adv_tail.hip', 'dwconv.hip', 'bn.hip', 'spatial.hip', 'pyramid.hip', 'fpn.hip', 'hrnet.hip', 'scene.hip', 'scene_tta.hip', 'loss.hip', 'dice_loss.hip', 'sigmoid_loss.hip', 'lovasz_loss.hip', 'entropy_labels.hip', 'entropy_loss.hip', 'ohem.hip', 'pfgst_loss.hip', 'optim.hip', 'strong_aug.hip', 'api.cpp']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-Wno-unused-result']
 # No packed-fp32 (v_pk_*_f32) code in the streaming kernels: round 5 found the depthwise backward kernel (dwconv3x3_kernel<3, true>: a packed add
 # on a pair of weight-gradient accumulators) returning WRONG sums -- one accumulator of a few channels off by O(1) -- whenever it ran on the
@@ -16,7 +16,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-val
 # profiles/r05_packed_fp32_corruption.txt).  Without the SLP vectoriser clang forms no <2 x float> operations, the kernels are exact under any
 # co-residency and 5-14 % FASTER (they are LDS / HBM bound, the packed forms bought nothing).  The matrix kernels keep the default: their
 # packed epilogue arithmetic is worth 9 ms per step and is pinned bit for bit by the deterministic-mode test under stream overlap.
-NO_SLP = {'adv_tail.hip', 'dwconv.hip', 'bn.hip', 'spatial.hip', 'pyramid.hip', 'fpn.hip', 'scene.hip', 'scene_tta.hip', 'loss.hip', 'dice_loss.hip', 'sigmoid_loss.hip', 'lovasz_loss.hip', 'entropy_labels.hip', 'entropy_loss.hip', 'ohem.hip', 'pfgst_loss.hip', 'optim.hip', 'strong_aug.hip', 'conv_winograd.hip'}
+NO_SLP = {'adv_tail.hip', 'dwconv.hip', 'bn.hip', 'spatial.hip', 'pyramid.hip', 'fpn.hip', 'hrnet.hip', 'scene.hip', 'scene_tta.hip', 'loss.hip', 'dice_loss.hip', 'sigmoid_loss.hip', 'lovasz_loss.hip', 'entropy_labels.hip', 'entropy_loss.hip', 'ohem.hip', 'pfgst_loss.hip', 'optim.hip', 'strong_aug.hip', 'conv_winograd.hip'}
 
 
 def _flags(src_name):

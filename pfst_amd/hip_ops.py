@@ -1305,6 +1305,78 @@ def fpn_level_sum_route(pre0, members, addend, out):
                                                            _p(addend), 0 if addend is None else _bs(addend), out.data_ptr(), _bs(out), h0, w0)]
 
 
+# ---------------------------------------------------------------- HRNet's exchange unit (csrc/hrnet.hip)
+HR_MAX_BRANCHES = 4         # PFST_HR_MAX_BRANCHES
+HR_FUSE_ROUTES = ('pixel', 'quad')                   # pfst_hr_fuse_route: one pixel per thread, four with 16-byte accesses
+HR_RATIOS = (2, 4, 8)
+
+
+def hr_fuse_exact(out_hw, op_hw):
+    """an operand on grid op_hw can enter the fused exchange for an output on out_hw: the same grid, or out_hw / r exactly, r in HR_RATIOS"""
+    return any(op_hw[0] * r == out_hw[0] and op_hw[1] * r == out_hw[1] for r in (1,) + HR_RATIOS)
+
+
+def _hr_fuse_args(ops, coefs, out):
+    n, c, hf, wf = out.shape
+    ops = list(ops)
+    coefs = [None] * len(ops) if coefs is None else list(coefs)
+    if not 1 <= len(ops) <= HR_MAX_BRANCHES or len(coefs) != len(ops):
+        raise ValueError(f'hr_fuse: 1 to {HR_MAX_BRANCHES} operands with one table (or None) each, got {len(ops)} and {len(coefs)}')
+    for t in ops:
+        if t.dim() != 4 or tuple(t.shape[:2]) != (n, c) or not hr_fuse_exact((hf, wf), t.shape[2:]):
+            raise ValueError(f'hr_fuse: operand {tuple(t.shape)} for an output {tuple(out.shape)} (same N, C; the same grid or exactly 1/2, 1/4, 1/8 of it)')
+    if sum(tuple(t.shape[2:]) != (hf, wf) for t in ops) > FPN_MAX_LEVELS:
+        raise NotImplementedError(f'hr_fuse: up to {FPN_MAX_LEVELS} coarser operands per launch')
+    return n, c, hf, wf, ops, coefs
+
+
+def hr_fuse(ops, coefs=None, out=None, out_hw=None, amax=None):
+    """out = relu(((t_0 + t_1) + t_2) + t_3) in ONE launch, the operands in the order given (hrnet.py:199-213).  ops[j] on out's grid: its values,
+    or pre * sc + sh under a [C, 4] table coefs[j] (no ReLU); ops[j] on exactly 1/2, 1/4 or 1/8 of it: the bilinear (align_corners=False)
+    interpolation of its (normalised) values.  Bit-identical to bn_apply(relu=False) per tabled operand, resize_bilinear per coarser one, the fp32
+    adds in that order and a ReLU.  out: default a new tensor on out_hw (default: ops[0]'s grid).  amax: the slot group that receives max |out|."""
+    if out is None:
+        hw = tuple(ops[0].shape[2:]) if out_hw is None else tuple(out_hw)
+        out = torch.empty(ops[0].shape[0], ops[0].shape[1], hw[0], hw[1], device=ops[0].device)
+    n, c, hf, wf, ops, coefs = _hr_fuse_args(ops, coefs, out)
+    call('pfst_hr_fuse', _ptr_array(ops), _i64s([_bs(t) for t in ops]), (ctypes.c_void_p * len(ops))(*[_coef_ptr(t, c, 'hr_fuse') for t in coefs]),
+         _pyr_ints([t.shape[2] for t in ops]), _pyr_ints([t.shape[3] for t in ops]), len(ops), out.data_ptr(), _bs(out), n, c, hf, wf, _p(amax),
+         _stream())
+    return out
+
+
+def hr_fuse_route(ops, out):
+    """the form pfst_hr_fuse takes for these operands, one of HR_FUSE_ROUTES (no launch)"""
+    n, c, hf, wf, ops, _ = _hr_fuse_args(ops, None, out)
+    return HR_FUSE_ROUTES[lib().pfst_hr_fuse_route(_ptr_array(ops), _i64s([_bs(t) for t in ops]), _pyr_ints([t.shape[2] for t in ops]),
+                                                   _pyr_ints([t.shape[3] for t in ops]), len(ops), out.data_ptr(), _bs(out), hf, wf)]
+
+
+def hr_fuse_bwd(d_out, out, coarse=(), accumulate=False, gy=None):
+    """the adjoint of hr_fuse in at most two launches.  Returns gy = d_out where out > 0, else 0 -- the upstream gradient of every operand on the
+    output grid (gy: the buffer to write, default a new tensor; d_out itself is allowed) -- after coarse[k] = (accumulate[k] ? coarse[k] : 0) +
+    resize_bilinear_bwd(gy) for the coarser operands' gradient buffers, all in one gather launch, each bit-identical to resize_bilinear_bwd.
+    accumulate: one flag, or one per coarse buffer"""
+    n, c, hf, wf = out.shape
+    coarse = list(coarse)
+    if tuple(d_out.shape) != tuple(out.shape) or (gy is not None and tuple(gy.shape) != tuple(out.shape)):
+        raise ValueError(f'hr_fuse_bwd: d_out {tuple(d_out.shape)} / gy for an output {tuple(out.shape)}')
+    if len(coarse) > FPN_MAX_LEVELS:
+        raise NotImplementedError(f'hr_fuse_bwd: up to {FPN_MAX_LEVELS} coarser operands per launch')
+    for t in coarse:
+        if t.dim() != 4 or tuple(t.shape[:2]) != (n, c) or tuple(t.shape[2:]) == (hf, wf) or not hr_fuse_exact((hf, wf), t.shape[2:]):
+            raise ValueError(f'hr_fuse_bwd: gradient buffer {tuple(t.shape)} under an output {tuple(out.shape)} (exactly 1/2, 1/4, 1/8 of its grid)')
+    acc = [bool(accumulate)] * len(coarse) if isinstance(accumulate, (bool, int)) else [bool(a) for a in accumulate]
+    if len(acc) != len(coarse):
+        raise ValueError(f'hr_fuse_bwd: {len(acc)} accumulate flags for {len(coarse)} buffers')
+    if gy is None:
+        gy = torch.empty(n, c, hf, wf, device=out.device)
+    call('pfst_hr_fuse_bwd', d_out.data_ptr(), _bs(d_out), out.data_ptr(), _bs(out), gy.data_ptr(), _bs(gy), _ptr_array(coarse),
+         _i64s([_bs(t) for t in coarse]), _pyr_ints([t.shape[2] for t in coarse]), _pyr_ints([t.shape[3] for t in coarse]), _pyr_ints(acc),
+         len(coarse), n, c, hf, wf, _stream())
+    return gy
+
+
 def upsample_nearest(x, factor):
     _dense(x)
     n, c, h, w = x.shape

@@ -166,6 +166,311 @@ class ResNetV1c(nn.Module):
         return tuple(outs)
 
 
+def _load_pretrained_backbone(module, pretrained):
+    """mmcv's 'Pretrained' init from a LOCAL checkpoint (backbone keys, strict=False); model-zoo URLs cannot be resolved here and fail loudly"""
+    if not (isinstance(pretrained, str) and os.path.exists(pretrained)):
+        raise FileNotFoundError(f'pretrained={pretrained!r} is not a local checkpoint file (no network here): pass a file, '
+                                'use --load-from, or set pretrained=None for random initialisation')
+    ckpt = torch.load(pretrained, map_location='cpu', weights_only=False)
+    sd = ckpt.get('state_dict', ckpt)
+    sd = {(k[len('backbone.'):] if k.startswith('backbone.') else k): v for k, v in sd.items()}
+    module.load_state_dict(sd, strict=False)
+
+
+class BasicBlock(nn.Module):
+    """backbones/resnet.py BasicBlock: conv3x3 -> bn1 -> ReLU -> conv3x3 -> bn2 (+ identity) -> ReLU"""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=False):
+        super().__init__()
+        self.conv1 = Conv2dP(inplanes, planes, 3, stride, dilation, dilation)
+        self.bn1 = BatchNorm2dP(planes)
+        self.conv2 = Conv2dP(planes, planes, 3, 1, 1, 1)
+        self.bn2 = BatchNorm2dP(planes)
+        self.downsample = None
+        if downsample:
+            self.downsample = nn.Sequential(Conv2dP(inplanes, planes, 1, stride), BatchNorm2dP(planes))
+
+    def forward(self, x, tape):
+        o = conv_bn_act(x, self.conv1, self.bn1, tape)
+        idt = x
+        if self.downsample is not None:
+            idt = conv_bn_act(x, self.downsample[0], self.downsample[1], tape, relu=False, defer=layers_mod.folds_into_residual())
+        return conv_bn_act(o, self.conv2, self.bn2, tape, relu=True, residual=idt)
+
+
+def _make_res_layer(block, inplanes, planes, blocks, stride=1):
+    layers = [block(inplanes, planes, stride, downsample=(stride != 1 or inplanes != planes * block.expansion))]
+    layers += [block(planes * block.expansion, planes) for _ in range(1, blocks)]
+    return nn.Sequential(*layers)
+
+
+def _conv_bn_seq(cin, cout, k, stride, relu):
+    """(0: conv, 1: BN[, 2: the parameter-less place of the reference's ReLU]) -- the indices of the reference's Sequentials"""
+    return nn.Sequential(Conv2dP(cin, cout, k, stride, k // 2), BatchNorm2dP(cout), *([nn.Identity()] if relu else []))
+
+
+# False: the exchange unit's backward writes the gated gradient into a buffer of its own and adds it to dL/dx_i with one more pass per output
+# (tests/test_hrnet_gpu.py compares the two wirings bit for bit)
+HR_SHARE_GATED = True
+
+
+class UpsamplePlace(nn.Module):
+    """the parameter-less place of the reference's `Upsample(scale_factor=2^(j-i), mode='bilinear')` at index 2 of an up path's Sequential: it keeps
+    the indices, the interpolation itself happens inside the exchange launch"""
+
+    def __init__(self, scale_factor):
+        super().__init__()
+        self.scale_factor = scale_factor
+
+
+class HRModule(nn.Module):
+    """backbones/hrnet.py:14-214: num_branches parallel branches of blocks, then the exchange unit -- output i is
+    relu(sum_j t_ij), t_ii = x_i, t_ij = BN(conv3x3/s2 chain(x_j)) for j < i, t_ij = bilinear_up(BN(conv1x1(x_j)), 2^(j-i)) for j > i, summed in
+    branch order.  One pfst_hr_fuse launch per output (csrc/hrnet.hip): the last conv -> BN of every fuse path is deferred,
+    its normalised tensor never written; the coarser members are interpolated as they are read.  Where a coarser member's grid times 2^(j-i) is
+    not the output grid (inputs whose sides are no multiple of 32) the reference interpolates twice, and the output takes the composition of
+    the existing ops instead (correct and slow)."""
+
+    def __init__(self, num_branches, block, num_blocks, in_channels, num_channels, multiscale_output=True):
+        super().__init__()
+        if not (num_branches == len(num_blocks) == len(num_channels) == len(in_channels)):
+            raise ValueError(f'NUM_BRANCHES({num_branches}) <> NUM_BLOCKS({len(num_blocks)}) / NUM_CHANNELS({len(num_channels)}) / '
+                             f'NUM_INCHANNELS({len(in_channels)})')
+        if num_branches > ops.HR_MAX_BRANCHES:
+            raise NotImplementedError(f'HRModule: up to {ops.HR_MAX_BRANCHES} branches, got {num_branches}')
+        self.num_branches, self.multiscale_output = num_branches, multiscale_output
+        self.in_channels = in_channels                    # the caller's list, updated in place as the reference does
+        self.branches = nn.ModuleList()
+        for b in range(num_branches):
+            self.branches.append(_make_res_layer(block, in_channels[b], num_channels[b], num_blocks[b]))
+            in_channels[b] = num_channels[b] * block.expansion
+        self.fuse_layers = None
+        if num_branches > 1:
+            self.fuse_layers = nn.ModuleList()
+            for i in range(num_branches if multiscale_output else 1):
+                row = []
+                for j in range(num_branches):
+                    if j > i:
+                        row.append(nn.Sequential(Conv2dP(in_channels[j], in_channels[i], 1), BatchNorm2dP(in_channels[i]), UpsamplePlace(2 ** (j - i))))
+                    elif j == i:
+                        row.append(None)
+                    else:
+                        row.append(nn.Sequential(*[_conv_bn_seq(in_channels[j], in_channels[i] if k == i - j - 1 else in_channels[j], 3, 2,
+                                                                relu=k != i - j - 1) for k in range(i - j)]))
+                self.fuse_layers.append(nn.ModuleList(row))
+
+    def _path(self, i, j, x, tape, defer):
+        """fuse path (i, j) up to and including its last conv -> BN (no ReLU there): deferred on the fused route"""
+        fl = self.fuse_layers[i][j]
+        if j > i:
+            return conv_bn_act(x, fl[0], fl[1], tape, relu=False, defer=defer)
+        for k, seq in enumerate(fl):
+            last = k == len(fl) - 1
+            x = conv_bn_act(x, seq[0], seq[1], tape, relu=not last, defer=defer if last else False)
+        return x
+
+    def forward(self, xs, tape):
+        xs = list(xs)
+        for b in range(self.num_branches):
+            for blk in self.branches[b]:
+                xs[b] = blk(xs[b], tape)
+        if self.fuse_layers is None:
+            return xs
+        B, n_out = self.num_branches, len(self.fuse_layers)
+        hws = [tuple(x.data.shape[-2:]) for x in xs]
+        fused = [all(ops.hr_fuse_exact(hws[i], hws[j]) for j in range(i + 1, B)) and B - 1 - i <= ops.FPN_MAX_LEVELS for i in range(n_out)]
+        defer = [layers_mod.folds_into_residual() if f else False for f in fused]
+        # Recording order.  In backward the exchange of output i hands ONE buffer gy_i to x_i (as its gradient, where nothing was written yet) and
+        # to every same-grid member of output i (as upstream gradient): nothing may add to dL/dx_i before the paths (i, j < i) have read gy_i.  The
+        # writers of dL/dx_i are the paths (i', i).  Recorded as: up paths, down paths by DESCENDING output, then the exchanges -- backward runs
+        # every exchange first, then the down paths by ascending output (path (i, j) reads gy_i before any (i' > i, i) adds to it, and adds to
+        # gy_j only after the paths (j, .) have read it), then the up paths.
+        t = [[None] * B for _ in range(n_out)]
+        for i in range(n_out):
+            for j in range(i + 1, B):
+                t[i][j] = self._path(i, j, xs[j], tape, defer[i])
+        for i in reversed(range(n_out)):
+            for j in range(i):
+                t[i][j] = self._path(i, j, xs[j], tape, defer[i])
+        for i in range(n_out):
+            for j in range(i):
+                got = tuple((t[i][j].data if t[i][j].lazy is None else t[i][j].lazy[0]).shape[-2:])
+                if got != hws[i]:
+                    raise ValueError(f'HRModule: the stride-2 chain from branch {j} ends on {got}, branch {i} is on {hws[i]}')
+        return [(self._exchange if fused[i] else self._exchange_composed)(i, xs, t[i], tape) for i in range(n_out)]
+
+    @staticmethod
+    def _out_var(dev, tape):
+        out = Var(None, tape is not None)
+        if layers_mod.CONV_MATH == 'f16x3':
+            out.amax = ops.amax_slots(dev)                # the next block's f16x3 GEMM reads it: published by the launch that writes the output
+        return out
+
+    def _exchange(self, i, xs, members, tape):
+        src = lambda v: (v.data, None) if v.lazy is None else (v.lazy[0], v.lazy[1])
+        operands = [(xs[i].data, None) if j == i else src(members[j]) for j in range(self.num_branches)]
+        out = self._out_var(xs[i].data.device, tape)
+        out.data = ops.hr_fuse([o[0] for o in operands], [o[1] for o in operands], out_hw=xs[i].data.shape[-2:], amax=out.amax)
+        if tape is not None:
+            xi, same, coarser = xs[i], [members[j] for j in range(i)], [members[j] for j in range(i + 1, self.num_branches)]
+
+            def bwd_exchange():
+                d_out = out.grad
+                for y in coarser:
+                    y._grad = torch.empty_like(src(y)[0])
+                alias = HR_SHARE_GATED and xi.requires_grad and xi.grad_unwritten() and xi.pending is None
+                # gated in place where x_i's gradient starts here: dL/dout's buffer becomes dL/dx_i
+                gy = ops.hr_fuse_bwd(d_out, out.data, [y._grad for y in coarser], gy=d_out if alias else None)
+                if alias:
+                    xi._grad = gy
+                elif xi.requires_grad:
+                    buf, acc = xi.grad_target()
+                    ops.copy_planes(gy, buf, accumulate=acc)
+                for y in same:
+                    y._grad = gy
+                out.free_grad()
+            tape.record(bwd_exchange, dict(op='hr_fuse', x=xi, members=[m for m in members if m is not None], out=out))
+        return out
+
+    def _exchange_composed(self, i, xs, members, tape):
+        """the same sum from the existing ops, for grids the fused form does not take: every member written by its normalisation pass, a coarser
+        one resized as the reference does (Upsample(scale_factor) to 2^(j-i) times its grid, then resize to the output grid), the adds in branch
+        order; the last add and the ReLU are one normalisation pass with identity coefficients (relu(fma(t, 1, 0) + partial sum))"""
+        B = self.num_branches
+        hi, wi = xs[i].data.shape[-2:]
+        dev = xs[i].data.device
+        terms = []
+        for j in range(B):
+            tj = xs[i].data if j == i else members[j].data
+            if j > i:
+                r = 2 ** (j - i)
+                up = (tj.shape[2] * r, tj.shape[3] * r)
+                tj = ops.resize_bilinear(tj, up)
+                if up != (hi, wi):
+                    tj = ops.resize_bilinear(tj, (hi, wi))
+            terms.append(tj)
+        part = ops.copy_planes(terms[0], torch.empty_like(terms[0]))
+        for tj in terms[1:-1]:
+            ops.axpy_(part, tj)
+        c = part.shape[1]
+        one, zero = ops.const_tensor([1.0] * c, dev), ops.const_tensor([0.0] * c, dev)
+        out = self._out_var(dev, tape)
+        out.data = ops.bn_apply(terms[-1], zero, one, one, zero, True, residual=part, amax=out.amax)
+        if tape is not None:
+            xi = xs[i]
+
+            def bwd_composed():
+                gy = ops.hr_fuse_bwd(out.grad, out.data)                 # the gate pass alone
+                if xi.requires_grad:
+                    buf, acc = xi.grad_target()
+                    ops.copy_planes(gy, buf, accumulate=acc)
+                for j in range(B):
+                    if j < i:
+                        members[j]._grad = gy
+                    elif j > i:
+                        h, w = members[j].data.shape[-2:]
+                        r = 2 ** (j - i)
+                        g = gy if (h * r, w * r) == (hi, wi) else ops.resize_bilinear_bwd(gy, (h * r, w * r))
+                        members[j]._grad = ops.resize_bilinear_bwd(g, (h, w))
+                out.free_grad()
+            tape.record(bwd_composed, dict(op='hr_fuse_composed', x=xi, members=[m for m in members if m is not None], out=out))
+        return out
+
+
+@BACKBONES.register_module()
+class HRNet(nn.Module):
+    """backbones/hrnet.py:217-643: stem (two 3x3 stride-2 conv -> BN -> ReLU), layer1, three transitions and three stages of HRModules; returns
+    the tuple of branch outputs (strides 4, 8, 16, 32).  Module names are the reference's (conv1, bn1, conv2, bn2, layer1, transition{1,2,3},
+    stage{2,3,4}.{m}.branches.{b}.{k} / .fuse_layers.{i}.{j}) so checkpoints load by key."""
+    blocks_dict = {'BASIC': BasicBlock, 'BOTTLENECK': Bottleneck}
+
+    def __init__(self, extra, in_channels=3, conv_cfg=None, norm_cfg=dict(type='BN', requires_grad=True), norm_eval=False, with_cp=False,
+                 frozen_stages=-1, zero_init_residual=False, multiscale_output=True, pretrained=None, init_cfg=None):
+        super().__init__()
+        _check_norm(norm_cfg)
+        bad = [k for k, v in dict(norm_eval=norm_eval, with_cp=with_cp, frozen_stages=frozen_stages >= 0, conv_cfg=conv_cfg is not None).items() if v]
+        if bad:
+            raise NotImplementedError(f'HRNet options outside the implemented path: {bad}')
+        if not (pretrained is None or isinstance(pretrained, str)):
+            raise TypeError('pretrained must be a str or None')
+        assert 'stage1' in extra and 'stage2' in extra and 'stage3' in extra and 'stage4' in extra
+        for s in range(4):
+            cfg = extra[f'stage{s + 1}']
+            assert len(cfg['num_blocks']) == cfg['num_branches'] and len(cfg['num_channels']) == cfg['num_branches']
+        self.extra, self.pretrained, self.zero_init_residual = extra, pretrained, zero_init_residual
+        self.conv1 = Conv2dP(in_channels, 64, 3, 2, 1)
+        self.bn1 = BatchNorm2dP(64)
+        self.conv2 = Conv2dP(64, 64, 3, 2, 1)
+        self.bn2 = BatchNorm2dP(64)
+        cfg = extra['stage1']
+        block = self.blocks_dict[cfg['block']]
+        self.layer1 = _make_res_layer(block, 64, cfg['num_channels'][0], cfg['num_blocks'][0])
+        pre = [cfg['num_channels'][0] * block.expansion]
+        for s in (2, 3, 4):
+            cfg = extra[f'stage{s}']
+            block = self.blocks_dict[cfg['block']]
+            cur = [c * block.expansion for c in cfg['num_channels']]
+            setattr(self, f'transition{s - 1}', self._make_transition_layer(pre, cur))
+            mods = [HRModule(cfg['num_branches'], block, cfg['num_blocks'], cur, cfg['num_channels'],
+                             multiscale_output or s != 4 or m != cfg['num_modules'] - 1) for m in range(cfg['num_modules'])]
+            setattr(self, f'stage{s}', nn.Sequential(*mods))
+            pre = cur
+
+    @staticmethod
+    def _make_transition_layer(pre, cur):
+        layers = []
+        for i in range(len(cur)):
+            if i < len(pre):
+                layers.append(_conv_bn_seq(pre[i], cur[i], 3, 1, relu=True) if cur[i] != pre[i] else None)
+            else:
+                n = i + 1 - len(pre)
+                layers.append(nn.Sequential(*[_conv_bn_seq(pre[-1], cur[i] if k == n - 1 else pre[-1], 3, 2, relu=True) for k in range(n)]))
+        return nn.ModuleList(layers)
+
+    def init_weights(self):
+        """hrnet.py:313-329 with pretrained=None: Kaiming convolutions (done at construction), BatchNorm weight 1 / bias 0; zero_init_residual
+        starts the last norm of every block at 0.  A local `pretrained` checkpoint is loaded instead; URLs fail loudly."""
+        if self.pretrained is not None:
+            _load_pretrained_backbone(self, self.pretrained)
+            return
+        for m in self.modules():
+            if isinstance(m, BatchNorm2dP):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+        if self.zero_init_residual:
+            for m in self.modules():
+                if isinstance(m, BasicBlock):
+                    nn.init.zeros_(m.bn2.weight)
+                elif isinstance(m, Bottleneck):
+                    nn.init.zeros_(m.bn3.weight)
+
+    @staticmethod
+    def _transit(layer, x, tape):
+        if isinstance(layer[0], Conv2dP):
+            return conv_bn_act(x, layer[0], layer[1], tape)
+        for seq in layer:
+            x = conv_bn_act(x, seq[0], seq[1], tape)
+        return x
+
+    def forward(self, x, tape=None, grad_ready=None):
+        """grad_ready is accepted and unused: the backbone records no stage markers (the branches of a stage run side by side, no prefix of the
+        tape completes a stage), so a data-parallel reducer sends the whole backbone with its final flush"""
+        x = conv_bn_act(x, self.conv1, self.bn1, tape)
+        x = conv_bn_act(x, self.conv2, self.bn2, tape)
+        for blk in self.layer1:
+            x = blk(x, tape)
+        ys = [x]
+        for s in (2, 3, 4):
+            trans = getattr(self, f'transition{s - 1}')
+            # hrnet.py:607-628: an entry that exists reads the LAST branch of the previous stage, a None entry passes branch i through
+            xs = [ys[i] if layer is None else self._transit(layer, ys[-1], tape) for i, layer in enumerate(trans)]
+            for mod in getattr(self, f'stage{s}'):
+                xs = mod(xs, tape)
+            ys = xs
+        return tuple(ys)
+
+
 def get_class_weight(class_weight):
     """losses/utils.py:10-25: a list is taken as is; a str is a file -- .npy via NumPy, otherwise what mmcv.load reads by
     extension (.json, .yaml / .yml, .pkl / .pickle)."""
@@ -512,8 +817,10 @@ class BaseDecodeHead(nn.Module):
                  sampler=None, align_corners=False, init_cfg=None):
         super().__init__()
         _check_norm(norm_cfg)
-        if input_transform is not None or align_corners or conv_cfg is not None:
+        if (input_transform is not None and not self._takes_input_transform(in_channels, in_index, input_transform)) or align_corners \
+                or conv_cfg is not None:
             raise NotImplementedError('decode head options outside the PFST path')
+        self.input_transform = input_transform
         if not isinstance(loss_decode, (dict, list, tuple)):
             raise TypeError(f'loss_decode must be a dict or a sequence of dicts, but got {type(loss_decode)}')
         self.in_channels, self.channels, self.num_classes = in_channels, channels, num_classes
@@ -530,6 +837,11 @@ class BaseDecodeHead(nn.Module):
         nn.init.normal_(self.conv_seg.weight, 0, 0.01)
         self.dropout_enabled = True            # the teacher switches this off (pfgst.py:247-251)
         self.injected_dropout_mask = None      # parity tests inject the (n, C) keep/scale mask
+
+    @staticmethod
+    def _takes_input_transform(in_channels, in_index, input_transform):
+        """does this head class implement `input_transform` for these arguments?  (FCNHead: 'resize_concat' over lists; nobody else)"""
+        return False
 
     def dropout_mask(self, n, training):
         """the (n, C) keep / (1 - p) factors of nn.Dropout2d (decode_head.py:103-107), or None when dropout is off (evaluation, the
@@ -1104,8 +1416,18 @@ class FPNHead(BaseDecodeHead):
 class FCNHead(BaseDecodeHead):
     """fcn_head.py: num_convs conv -> BN -> ReLU layers (kernel 1 or 3, any dilation), optionally conv_cat over [x, feats]"""
 
+    @staticmethod
+    def _takes_input_transform(in_channels, in_index, input_transform):
+        return (input_transform == 'resize_concat' and isinstance(in_channels, (list, tuple)) and isinstance(in_index, (list, tuple))
+                and len(in_channels) == len(in_index) >= 1 and all(isinstance(c, int) and c > 0 for c in in_channels)
+                and all(isinstance(i, int) for i in in_index))
+
     def __init__(self, num_convs=2, kernel_size=3, concat_input=True, dilation=1, **kwargs):
         super().__init__(**kwargs)
+        if self.input_transform is not None:
+            # decode_head.py _init_inputs / _transform_inputs, 'resize_concat': the levels in_index resized to the first one's grid and concatenated
+            self.level_channels, self.in_index = list(self.in_channels), list(self.in_index)
+            self.in_channels = sum(self.level_channels)
         if not (isinstance(num_convs, int) and num_convs >= 0 and isinstance(dilation, int) and dilation > 0):
             raise ValueError(f'FCNHead: num_convs >= 0 and dilation >= 1, got {num_convs!r}, {dilation!r}')
         if kernel_size not in (1, 3):
@@ -1120,10 +1442,41 @@ class FCNHead(BaseDecodeHead):
         if self.concat_input:
             self.conv_cat = ConvModule(self.in_channels + self.channels, self.channels, kernel_size, padding=kernel_size // 2)
 
+    def _resize_concat(self, inputs, tape):
+        """level 0 copied, every further level resized (bilinear, align_corners=False) into its channel slice of ONE buffer on level 0's grid;
+        every writer publishes max |.| into the buffer's slot group.  One pfst_fpn_resize_concat launch per level: that entry point takes one
+        channel count per call and the levels differ in width"""
+        xs = [inputs[i] for i in self.in_index]
+        cat = _concat_var(xs[0], self.in_channels, tape)
+        offs = [sum(self.level_channels[:k]) for k in range(len(xs) + 1)]
+        for k, x in enumerate(xs):
+            if x.data.shape[1] != self.level_channels[k]:
+                raise ValueError(f'FCNHead: level {self.in_index[k]} has {x.data.shape[1]} channels, in_channels says {self.level_channels[k]}')
+            dst = cat.data[:, offs[k]:offs[k + 1]]
+            if k == 0:
+                ops.copy_planes(x.data, dst, amax=cat.amax)
+            else:
+                ops.fpn_resize_concat([x.data], dst, chan_off=[0], amax=cat.amax)
+        if tape is not None:
+            def bwd_concat():
+                g = cat.grad
+                for k, x in enumerate(xs):
+                    if not x.requires_grad:
+                        continue
+                    buf, acc = x.grad_target()
+                    gk = g[:, offs[k]:offs[k + 1]]
+                    if k == 0:
+                        ops.copy_planes(gk, buf, accumulate=acc)
+                    else:
+                        ops.fpn_resize_concat_bwd(gk, [buf], chan_off=[0], accumulate=acc)
+                cat.free_grad()
+            tape.record(bwd_concat, dict(op='resize_concat', xs=xs, out=cat))
+        return cat
+
     def forward(self, inputs, return_features=False, tape=None, training=True):
         # (the features this head returns are the PRE-dropout ones, fcn_head.py:92-98, so its Dropout2d stays a pass of its own -- an eighth
         # of the decode head's tensor; the decode head returns the ASPP bottleneck output and folds its dropout, see above)
-        x = inputs[self.in_index]
+        x = inputs[self.in_index] if self.input_transform is None else self._resize_concat(inputs, tape)
         if self.num_convs == 1 and not self.concat_input:
             feats = self.convs[0](x, tape)
         else:

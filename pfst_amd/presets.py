@@ -24,18 +24,34 @@ def model_cfg(num_classes=6, in_channels=3, dropout=0.1):
         train_cfg=dict(), test_cfg=dict(mode='whole'))
 
 
-BASELINE_KINDS = ('pspnet', 'deeplabv3', 'fcn', 'upernet', 'fpn')
+BASELINE_KINDS = ('pspnet', 'deeplabv3', 'fcn', 'upernet', 'fpn', 'hrnet')
 
 
-def baseline_model_cfg(kind, num_classes, in_channels, depth=50, dropout=0.1):
+def baseline_model_cfg(kind, num_classes, in_channels, depth=50, dropout=0.1, width=18):
     """The comparison models of the reference (configs/_base_/models/pspnet_r50-d8.py, deeplabv3_r50-d8.py, fcn_r50-d8.py): the same
     ResNetV1c-d8 backbone and auxiliary FCN head on layer3 as model_cfg, under a PSPHead, an ASPPHead or a two-layer FCNHead with
     concat_input; 'upernet' (upernet_r50.py) is a UPerHead over all four levels of the stride-32 backbone, strides (1, 2, 2, 2) without
     dilation, with the same auxiliary head; 'fpn' (fpn_r50.py, Semantic FPN) is that stride-32 backbone under an FPN neck (256 channels, four
     levels, nearest top-down path) and an FPNHead (128 channels, feature strides 4 .. 32) -- WITHOUT an auxiliary head, as the reference's file.  Plain BN, as the reference's DeepLabV3+ file; `depth` 50 or 101 (the reference's PSPNet file runs 101).  The class
-    weights of the reference's two-class PSPNet edit are a property of its data set: add `class_weight` to the loss dicts where wanted."""
+    weights of the reference's two-class PSPNet edit are a property of its data set: add `class_weight` to the loss dicts where wanted.
+    'hrnet' (fcn_hr18.py) is another backbone altogether: HRNet-W`width` (18, or 48 for fcn_hr48) under a one-layer 1x1 FCNHead that reads all
+    four branches through input_transform='resize_concat', channels = the sum of the widths, dropout_ratio -1 (no dropout), no auxiliary
+    head; plain BN; `depth` and `dropout` do not apply."""
     if kind not in BASELINE_KINDS:
         raise ValueError(f'baseline_model_cfg: kind must be one of {BASELINE_KINDS}, got {kind!r}')
+    if kind == 'hrnet':
+        widths = [width, 2 * width, 4 * width, 8 * width]
+        extra = dict(stage1=dict(num_modules=1, num_branches=1, block='BOTTLENECK', num_blocks=(4,), num_channels=(64,)),
+                     stage2=dict(num_modules=1, num_branches=2, block='BASIC', num_blocks=(4, 4), num_channels=tuple(widths[:2])),
+                     stage3=dict(num_modules=4, num_branches=3, block='BASIC', num_blocks=(4, 4, 4), num_channels=tuple(widths[:3])),
+                     stage4=dict(num_modules=3, num_branches=4, block='BASIC', num_blocks=(4, 4, 4, 4), num_channels=tuple(widths)))
+        return dict(type='EncoderDecoder', pretrained=None,
+                    backbone=dict(type='HRNet', norm_cfg=dict(NORM_CFG), norm_eval=False, extra=extra, in_channels=in_channels),
+                    decode_head=dict(type='FCNHead', in_channels=widths, in_index=[0, 1, 2, 3], channels=sum(widths),
+                                     input_transform='resize_concat', kernel_size=1, num_convs=1, concat_input=False, dropout_ratio=-1,
+                                     num_classes=num_classes, norm_cfg=dict(NORM_CFG), align_corners=False,
+                                     loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0)),
+                    train_cfg=dict(), test_cfg=dict(mode='whole'))
     cfg = model_cfg(num_classes, in_channels, dropout)
     cfg['backbone']['depth'] = depth
     common = dict(in_channels=2048, in_index=3, channels=512, dropout_ratio=dropout, num_classes=num_classes, norm_cfg=dict(NORM_CFG),

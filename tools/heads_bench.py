@@ -5,7 +5,7 @@ device ops in the same process (four adaptive_avg_pool2d; four interpolate + cat
 timed region), (b) the resize halves through the library's generic pfst_resize_bilinear / _bwd, one launch per scale, and (c) the bytes each
 launch must move at the measured copy rate.  Variants alternate inside every round; per variant the median, minimum and maximum over the
 rounds of the mean of --inner back-to-back runs between two device events.  Then a supervised step (EncoderDecoder.train_step under SGD) of
-the comparison models (--models, default all: pspnet, deeplabv3, fcn, upernet, fpn) and the flagship at 8 x 1024^2, alternating blocks, host clock
+the comparison models (--models, default all: pspnet, deeplabv3, fcn, upernet, fpn, hrnet) and the flagship at 8 x 1024^2, alternating blocks, host clock
 between device synchronisations, with the peak device allocation of each.  One JSON line (and --out FILE).
 
 The feature-pyramid kernels of UPerHead (csrc/fpn.hip) at its grids for that tile -- 512 channels, 256^2 / 128^2 / 64^2 /
@@ -259,7 +259,8 @@ def step_bench(args):
     batch = synth_batch(args.tiles, args.size, 6, 3, seed=1234, device='cuda')
     batch = {k: v for k, v in batch.items() if not k.startswith('target_')}
     cfgs = dict(deeplabv3plus=model_cfg(6, 3), pspnet=baseline_model_cfg('pspnet', 6, 3), deeplabv3=baseline_model_cfg('deeplabv3', 6, 3),
-                fcn=baseline_model_cfg('fcn', 6, 3), upernet=baseline_model_cfg('upernet', 6, 3), fpn=baseline_model_cfg('fpn', 6, 3))
+                fcn=baseline_model_cfg('fcn', 6, 3), upernet=baseline_model_cfg('upernet', 6, 3), fpn=baseline_model_cfg('fpn', 6, 3),
+                hrnet=baseline_model_cfg('hrnet', 6, 3))
     if args.models:
         cfgs = {k: cfgs[k] for k in args.models.split(',')}
     times = {k: [] for k in cfgs}
@@ -299,7 +300,7 @@ def main(argv=None):
     p.add_argument('--rounds', type=int, default=7)
     p.add_argument('--inner', type=int, default=5)
     p.add_argument('--steps', type=int, default=12, help='timed supervised steps per model')
-    p.add_argument('--models', default=None, help='comma-separated kinds of the supervised-step part (deeplabv3plus,pspnet,deeplabv3,fcn,upernet,fpn); default all')
+    p.add_argument('--models', default=None, help='comma-separated kinds of the supervised-step part (deeplabv3plus,pspnet,deeplabv3,fcn,upernet,fpn,hrnet); default all')
     p.add_argument('--no-step', action='store_true')
     p.add_argument('--no-fpn', action='store_true')
     p.add_argument('--no-ops', action='store_true')

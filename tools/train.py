@@ -12,7 +12,7 @@ Supervised training (source-only / target-only baselines, a source-trained start
 builds a bare EncoderDecoder (registry.build_train_model) whose own train_step runs; `cfg.data.train` is then a plain dataset dict
 (type / data_root / img_dir / ann_dir / pipeline) and the optimizer usually the SGD of configs/_base_/schedules/schedule_*.py.
 `--supervised` drops the `uda` section of a config or preset (a UDADataset in data.train is replaced by its `source` entry; a preset takes
-schedule_40k's SGD + poly schedule); `--supervised --model pspnet|deeplabv3|fcn|upernet|fpn` swaps in the reference's comparison models (PSPNet,
+schedule_40k's SGD + poly schedule); `--supervised --model pspnet|deeplabv3|fcn|upernet|fpn|hrnet` swaps in the reference's comparison models (PSPNet,
 DeepLabV3, FCN on the same backbone, UPerNet and Semantic FPN -- neck included -- on the stride-32 one: presets.baseline_model_cfg), `--synthetic` included.  Checkpoints of such a run have bare keys: tools/test.py reads them without key revision, and
 `--init-student-from CKPT` starts a self-training run (a `uda` config) with them in both the student and the EMA teacher.
 
@@ -39,10 +39,10 @@ def parse_args(argv=None):
     p.add_argument('--init-student-from', help='a bare-keyed segmentor checkpoint (backbone.* / decode_head.* / auxiliary_head.*, e.g. of a '
                                                'supervised run) loaded into the student AND the EMA teacher of a `uda` config; every key must match')
     p.add_argument('--supervised', action='store_true', help='drop the `uda` section: train the bare segmentor on img / gt_semantic_seg')
-    p.add_argument('--model', choices=['pspnet', 'deeplabv3', 'fcn', 'upernet', 'fpn'],
+    p.add_argument('--model', choices=['pspnet', 'deeplabv3', 'fcn', 'upernet', 'fpn', 'hrnet'],
                    help='with --supervised: replace cfg.model by the comparison model of that name (presets.baseline_model_cfg: PSPHead / ASPPHead / '
                         'two-layer FCNHead on the same backbone and auxiliary head; upernet / fpn: the stride-32 backbone, fpn with its FPN neck and no '
-                        'auxiliary head), keeping num_classes, in_channels and the backbone depth')
+                        'auxiliary head; hrnet: HRNet-W18 under a one-layer FCNHead over its four branches, no auxiliary head), keeping num_classes and in_channels, and -- for the ResNetV1c models -- the backbone depth and the dropout ratio (hrnet has neither: width 18, no dropout)')
     p.add_argument('--uda', choices=['dacs'],
                    help='replace the `uda` section of the config or preset by the DACS self-training baseline (presets.dacs_uda_cfg: the values of '
                         "the reference's configs/_base_/uda/dacs.py, no auxiliary losses), keeping strong_aug_denorm_type, a property of the data")
